@@ -20,6 +20,13 @@ outside the timed region.
 
 value = NR iterations summed over all instances of all ranks in the K timed
 steps / max-over-ranks wall time of those steps.
+
+A plain run does only what that figure needs: set-up, W warm-up steps, the K
+timed steps, the gather of the probe voltages and the result line.  `--full`
+adds the other measurements: the mid- and large-batch legs (--mid-batch,
+--large-batch) and the CPU baselines (--no-cpu, --cpu-threads).
+`--dump-outputs DIR` writes what the timed path handed back after its last
+step (state, NR counts, status flags of every instance) as DIR/<name>.npy.
 """
 import argparse
 import ctypes as C
@@ -38,6 +45,7 @@ FP64_VECTOR_PEAK_TFLOPS = 78.6 # MI355X FP64 vector peak (256 CUs x 4 SIMDs x 16
 N_SIMDS = 1024                 # 256 CUs x 4 SIMDs
 PEAK_CLOCK_HZ = 2.4e9
 VALU_ISSUE_CYCLES = 4          # one wave64 VALU instruction (FP64 FMA: 16 lanes/clk/SIMD) holds a SIMD's issue for 4 cycles
+DUMP_LIMIT = 64 << 20          # bytes --dump-outputs may write in all
 
 
 def dense_flops(n):
@@ -95,6 +103,22 @@ def valu_roof(units_per_s, counters, B, lanes_per_instance, flops_exec):
         rec["achieved_frac"] = units_per_s * ipu * VALU_ISSUE_CYCLES / (N_SIMDS * PEAK_CLOCK_HZ)
         rec["source"] = counters.get("source")
     return rec
+
+
+def dump_outputs(path, x, iters, status):
+    """--dump-outputs: what a caller of the timed path holds after its last step, one float64 .npy per array --
+    state.npy [N][B] (node voltages and branch currents), nr_iters.npy [B] (NR iterations of each instance,
+    summed over the warm-up and timed steps), status.npy [B] (status bits), instance.npy [B] (global instance
+    index of each column).  When the whole batch exceeds DUMP_LIMIT, a fixed sample of instances (seed 0) is
+    written instead."""
+    n, b = x.shape
+    cols = np.arange(b)
+    per_inst = (n + 3) * 8
+    if b * per_inst > DUMP_LIMIT:
+        cols = np.sort(np.random.default_rng(0).choice(b, DUMP_LIMIT // per_inst, replace=False))
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("state", x[:, cols]), ("nr_iters", iters[cols]), ("status", status[cols]), ("instance", cols)):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def self_launch(n):
@@ -214,7 +238,7 @@ def main():
     ap.add_argument("--sigma", type=float, default=0.05)
     ap.add_argument("--kernel", default="auto", choices=["auto", "general", "scheduled", "faithful"])
     ap.add_argument("--cpu-iters", type=float, default=3.0e6, help="approx. NR iterations of the CPU sample (~15 s)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the all-cores CPU leg (0 = every core this process may run on; 1 = skip the leg)")
     ap.add_argument("--cpu-seconds", type=float, default=4.0, help="target run time of the all-cores CPU leg")
@@ -227,9 +251,16 @@ def main():
     ap.add_argument("--async", dest="async_calls", action="store_true",
                     help="engine option hybrid_sync=0: the transient calls only enqueue, the host never waits inside them")
     ap.add_argument("--large-batch", type=int, default=65536,
-                    help="also time this many instances per GPU (one wave per SIMD needs >= 65536); 0 = skip")
+                    help="with --full: also time this many instances per GPU (one wave per SIMD needs >= 65536); 0 = skip")
     ap.add_argument("--mid-batch", type=int, default=16384,
-                    help="also time this many instances per GPU (the four-lanes-per-instance kernel's range); 0 = skip")
+                    help="with --full: also time this many instances per GPU (the four-lanes-per-instance kernel's range); "
+                         "0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements the headline figure does not need: the mid- and large-batch legs and "
+                         "the CPU baselines")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the final state, NR counts and status flags of the timed batch to "
+                         "DIR/<name>.npy (float64; a fixed sample of instances if they exceed %d MB)" % (DUMP_LIMIT >> 20))
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:       # started bare: be the launcher (no GPU call in this process)
@@ -354,6 +385,12 @@ def main():
     torch.cuda.synchronize()
     gather_ms = (time.perf_counter() - t0) * 1e3
 
+    if args.dump_outputs:
+        out = [shard.all_gather_instances(t.double(), B * world, device=dev).cpu().numpy() for t in (x, iters, status)]
+        if rank == 0:
+            dump_outputs(args.dump_outputs, *out)
+        del out
+
     # ---- second leg: a batch that gives every SIMD a wave (same circuit, same kernels) ------
     def second_leg(BL):
         pl = eng.mc_params(args.seed, args.sigma, rank * BL, BL)
@@ -378,8 +415,8 @@ def main():
                 "kernel_avg_ms": e0.elapsed_time(e1) / nl_steps,
                 "flagged_instances": int((stl & 0xA7).ne(0).sum().item())}
 
-    mid = second_leg(args.mid_batch) if args.mid_batch and args.mid_batch != B else None
-    large = second_leg(args.large_batch) if args.large_batch and args.large_batch != B else None
+    mid = second_leg(args.mid_batch) if args.full and args.mid_batch and args.mid_batch != B else None
+    large = second_leg(args.large_batch) if args.full and args.large_batch and args.large_batch != B else None
 
     if args.dump_gathered and rank == 0:
         np.savez(args.dump_gathered, gathered=all_v.cpu().numpy(), total_iters=np.int64(total_iters))
@@ -477,7 +514,7 @@ def main():
                 large["roofline_valu"] = valu_roof(large["value"] / world, profiled_counters(nl, lkey, large["batch_per_gpu"]),
                                                    large["batch_per_gpu"], ll, flops_exec)
             rec[key] = large
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             # CPU baseline: the oracle (port of the reference algorithm), 1 thread,
             # on the first instances of the same parameter table
             ncores, quota = cpu_share()
