@@ -1,6 +1,7 @@
 // codegen.cpp -- see codegen.hpp.  Symbolic execution of stamp + pivoted LU +
 // substitution over {zero, exact constant, run-time value}; emits HIP source.
 #include "codegen.hpp"
+#include "codegen_sym.hpp"
 #include "group_plan.hpp"
 
 #include <algorithm>
@@ -8,14 +9,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <sstream>
 
 namespace csim {
-
-// codegen_linear.cpp
-void emitTranSourceValue(std::ostream& src, const std::string& i2, const csim_ir& ir, int e,
-                         const std::function<std::string(int)>& P, const std::string& target);
 
 // ------------------------------------------------------------ schedule utils
 
@@ -186,140 +182,9 @@ uint64_t scheduleHash(const csim_ir& ir, const PivotSchedule& sch)
     return h;
 }
 
-// ------------------------------------------------------------ abstract values
+// ------------------------------------------------------------ names
 
 namespace {
-
-struct AV {
-    enum Kind { ZERO, CONST, DYN } kind = ZERO;
-    double c = 0.0;          // CONST
-    std::string v;           // DYN: variable name
-    bool neg = false;        // DYN: value is -(v)
-    static AV zero() { return AV(); }
-    static AV konst(double x) { AV a; if (x == 0.0) return a; a.kind = CONST; a.c = x; return a; }
-    static AV dyn(const std::string& name, bool n = false) { AV a; a.kind = DYN; a.v = name; a.neg = n; return a; }
-    bool isZero() const { return kind == ZERO; }
-};
-
-std::string lit(double x)
-{
-    char buf[64];
-    std::snprintf(buf, sizeof buf, "%a", x);
-    return std::string("(") + buf + ")";
-}
-
-struct Gen {
-    const csim_ir& ir;
-    const AssemblyPlan& ap;
-    std::ostringstream out;
-    // deferred entries: ordered term lists not yet turned into code (lazy assembly keeps
-    // an entry out of the register file until the elimination first touches it)
-    std::vector<std::vector<std::vector<AV>>> pending;
-    int tmp = 0;
-    CodegenStats st;
-    std::string ind = "            ";
-
-    Gen(const csim_ir& i, const AssemblyPlan& a) : ir(i), ap(a) {}
-
-    std::string fresh() { return "v" + std::to_string(tmp++); }
-    std::string ref(const AV& a) const
-    {
-        if (a.kind == AV::CONST) return lit(a.c);
-        if (a.kind == AV::DYN) return a.neg ? "(-" + a.v + ")" : a.v;
-        return "0.0";
-    }
-    AV emit(const std::string& expr)
-    {
-        const std::string n = fresh();
-        out << ind << "const double " << n << " = " << expr << ";\n";
-        return AV::dyn(n);
-    }
-    AV negate(AV a)
-    {
-        if (a.kind == AV::CONST) a.c = -a.c;
-        else if (a.kind == AV::DYN) a.neg = !a.neg;
-        return a;
-    }
-    // a * b
-    AV mul(const AV& a, const AV& b)
-    {
-        if (a.isZero() || b.isZero()) return AV::zero();
-        if (a.kind == AV::CONST && b.kind == AV::CONST) return AV::konst(a.c * b.c);
-        if (a.kind == AV::CONST || b.kind == AV::CONST) {
-            const AV& k = a.kind == AV::CONST ? a : b;
-            const AV& d = a.kind == AV::CONST ? b : a;
-            if (k.c == 1.0) return d;
-            if (k.c == -1.0) return negate(d);
-            ++st.nMul;
-            return emit(lit(k.c) + " * " + ref(d));
-        }
-        ++st.nMul;
-        AV r = emit(a.v + " * " + b.v);
-        r.neg = a.neg != b.neg;
-        return r;
-    }
-    // a / b (faithful kernels: solver.hpp:71 and :126 divide)
-    AV div(const AV& a, const AV& b)
-    {
-        if (a.isZero()) return AV::zero();
-        if (a.kind == AV::CONST && b.kind == AV::CONST) return AV::konst(a.c / b.c);
-        if (b.kind == AV::CONST) {
-            if (b.c == 1.0) return a;
-            if (b.c == -1.0) return negate(a);
-            return emit(ref(a) + " / " + lit(b.c));
-        }
-        AV r = emit((a.kind == AV::CONST ? lit(a.c) : a.v) + " / " + b.v);
-        r.neg = (a.kind == AV::DYN && a.neg) != b.neg;
-        return r;
-    }
-    // a - f*u
-    AV fnma(const AV& a, const AV& f, const AV& u)
-    {
-        if (f.isZero() || u.isZero()) return a;
-        if (a.isZero()) return negate(mul(f, u));
-        // fold exact +-1 factors into an add/sub
-        const bool f1 = f.kind == AV::CONST && std::fabs(f.c) == 1.0;
-        const bool u1 = u.kind == AV::CONST && std::fabs(u.c) == 1.0;
-        if (f.kind == AV::CONST && u.kind == AV::CONST) {
-            const double p = f.c * u.c;
-            if (a.kind == AV::CONST) return AV::konst(a.c - p);
-            ++st.nAddSub;
-            return emit(ref(a) + " - " + lit(p));
-        }
-        if (f1 || u1) {
-            AV w = f1 ? u : f;
-            const double s = f1 ? f.c : u.c;
-            if (s < 0) w = negate(w);
-            ++st.nAddSub;
-            return emit(ref(a) + " - " + ref(w));
-        }
-        ++st.nFma;
-        return emit(ref(a) + " - " + ref(f) + " * " + ref(u));
-    }
-    // ordered sum of signed terms (the reference's accumulation order)
-    AV orderedSum(const std::vector<AV>& terms)
-    {
-        bool allConst = true;
-        for (const AV& t : terms) allConst = allConst && t.kind != AV::DYN;
-        if (allConst) {
-            double acc = 0.0;
-            for (const AV& t : terms) acc = acc + (t.kind == AV::CONST ? t.c : 0.0);
-            return AV::konst(acc);
-        }
-        std::vector<AV> nz;
-        for (const AV& t : terms) if (!t.isZero()) nz.push_back(t);
-        if (nz.size() == 1) return nz[0];
-        std::string e;
-        for (std::size_t i = 0; i < nz.size(); ++i) {
-            const AV& t = nz[i];
-            if (i == 0) { e = ref(t); continue; }
-            if (t.kind == AV::DYN) e = "(" + e + (t.neg ? " - " : " + ") + t.v + ")";
-            else e = "(" + e + " + " + lit(t.c) + ")";
-            ++st.nAddSub;
-        }
-        return emit(e);
-    }
-};
 
 // the iterate x lives in LDS, one private column per lane: X(i) = lds[i*64 + lane]
 std::string xname(int eq) { return eq >= 0 ? "X(" + std::to_string(eq) + ")" : std::string("0.0"); }
@@ -364,49 +229,50 @@ int emitKernel(std::ostringstream& src, const csim_ir& ir, const AssemblyPlan& a
     const int N = ir.n_unknowns;
     const int LD = ap.LD;
     const csim_consts& K = ir.k;
-    Gen g(ir, ap);
+    CodegenStats stats;
+    SymGen g("            ", "v", &stats);
     // near-threshold guard (codegen.hpp GeneratorOptions::nearBand): the fast kernels only
     const bool guard = !opt.faithful && (opt.dcMode ? gopt.nearBandDc : gopt.nearBand) > 0.0;
 
     // term -> abstract value.  Exact constants: the global ONE term and the
     // inductor incidence "one" (precondition L > 0 is checked per instance).
-    std::vector<AV> termAV(static_cast<std::size_t>(ap.nTerms));
-    for (int t = 0; t < ap.nTerms; ++t) termAV[static_cast<std::size_t>(t)] = AV::dyn(tname(t));
-    termAV[static_cast<std::size_t>(ap.termOne)] = AV::konst(1.0);
+    std::vector<Sym> termAV(sz(ap.nTerms));
+    for (int t = 0; t < ap.nTerms; ++t) termAV[sz(t)] = Sym::dyn(tname(t));
+    termAV[sz(ap.termOne)] = Sym::konst(1.0);
     for (int e = 0; e < ir.n_elems; ++e)
         if (ir.kind[e] == CSIM_L)
-            termAV[static_cast<std::size_t>(ap.termBase[static_cast<std::size_t>(e)] + T_L_ONE)] = AV::konst(1.0);
+            termAV[sz(ap.termBase[sz(e)] + T_L_ONE)] = Sym::konst(1.0);
 
     // terms that do not change inside the Newton loop (launch- or step-constant)
-    std::vector<char> invariant(static_cast<std::size_t>(ap.nTerms), 1);
+    std::vector<char> invariant(sz(ap.nTerms), 1);
     for (int e = 0; e < ir.n_elems; ++e)
         if (ir.kind[e] == CSIM_NMOS || ir.kind[e] == CSIM_PMOS)
             for (int o = T_M_GD; o <= T_M_CST; ++o)
-                invariant[static_cast<std::size_t>(ap.termBase[static_cast<std::size_t>(e)] + o)] = 0;
+                invariant[sz(ap.termBase[sz(e)] + o)] = 0;
 
     // ---- which terms are per-step (sources, history currents): they live in LDS too
-    std::vector<int> stepSlot(static_cast<std::size_t>(ap.nTerms), -1);
+    std::vector<int> stepSlot(sz(ap.nTerms), -1);
     int nStep = 0;
     for (int e = 0; e < ir.n_elems; ++e) {
-        const int tb = ap.termBase[static_cast<std::size_t>(e)];
+        const int tb = ap.termBase[sz(e)];
         switch (ir.kind[e]) {
-            case CSIM_V: case CSIM_I: stepSlot[static_cast<std::size_t>(tb + T_SRC_VAL)] = nStep++; break;
-            case CSIM_C: if (!opt.dcMode) stepSlot[static_cast<std::size_t>(tb + T_C_IH)] = nStep++; break;
-            case CSIM_L: if (!opt.dcMode) stepSlot[static_cast<std::size_t>(tb + T_L_VH)] = nStep++; break;
+            case CSIM_V: case CSIM_I: stepSlot[sz(tb + T_SRC_VAL)] = nStep++; break;
+            case CSIM_C: if (!opt.dcMode) stepSlot[sz(tb + T_C_IH)] = nStep++; break;
+            case CSIM_L: if (!opt.dcMode) stepSlot[sz(tb + T_L_VH)] = nStep++; break;
             case CSIM_NMOS: case CSIM_PMOS:
                 if (opt.dcMode) break;
-                for (int o = T_M_IHGS; o <= T_M_IHDB; ++o) stepSlot[static_cast<std::size_t>(tb + o)] = nStep++;
+                for (int o = T_M_IHGS; o <= T_M_IHDB; ++o) stepSlot[sz(tb + o)] = nStep++;
                 break;
             default: break;
         }
     }
     if (!opt.stepInLds) nStep = 0;     // per-step terms stay in registers: plain variables st<j>
     auto sname = [&](int t) {
-        const std::string j = std::to_string(stepSlot[static_cast<std::size_t>(t)]);
+        const std::string j = std::to_string(stepSlot[sz(t)]);
         return opt.stepInLds ? "S(" + j + ")" : "st" + j;
     };
     for (int t = 0; t < ap.nTerms; ++t)
-        if (stepSlot[static_cast<std::size_t>(t)] >= 0) termAV[static_cast<std::size_t>(t)] = AV::dyn(sname(t));
+        if (stepSlot[sz(t)] >= 0) termAV[sz(t)] = Sym::dyn(sname(t));
 
     // LDS layout: lds[slot*64 + lane]; slots 0..N-1 = x, N.. = per-step terms, then (rich
     // variant) launch constants, parameters used inside the loops and parked U rows.  Every
@@ -414,26 +280,26 @@ int emitKernel(std::ostringstream& src, const csim_ir& ir, const AssemblyPlan& a
     int ldsNext = N + nStep;       // next free LDS slot (doubles per lane)
     auto qslot = [&]() { return "Q(" + std::to_string(ldsNext++) + ")"; };
     // parameters / launch terms referenced inside the time loop: registers (lean) or LDS (rich)
-    std::vector<std::string> pRef(static_cast<std::size_t>(ir.n_params));
-    for (int p = 0; p < ir.n_params; ++p) pRef[static_cast<std::size_t>(p)] = pname(p);
-    std::vector<std::string> tRef(static_cast<std::size_t>(ap.nTerms));
-    for (int t = 0; t < ap.nTerms; ++t) tRef[static_cast<std::size_t>(t)] = tname(t);
+    std::vector<std::string> pRef(sz(ir.n_params));
+    for (int p = 0; p < ir.n_params; ++p) pRef[sz(p)] = pname(p);
+    std::vector<std::string> tRef(sz(ap.nTerms));
+    for (int t = 0; t < ap.nTerms; ++t) tRef[sz(t)] = tname(t);
     std::ostringstream ldsInit;    // stores that fill the rich variant's LDS copies
     auto toLdsParam = [&](int p) {
-        if (!opt.rich || pRef[static_cast<std::size_t>(p)][0] == 'Q') return;
+        if (!opt.rich || pRef[sz(p)][0] == 'Q') return;
         const std::string q = qslot();
         ldsInit << "    " << q << " = " << pname(p) << ";\n";
-        pRef[static_cast<std::size_t>(p)] = q;
+        pRef[sz(p)] = q;
     };
     auto toLdsTerm = [&](int t) {
         if (!opt.rich) return;
         const std::string q = qslot();
         ldsInit << "    " << q << " = " << tname(t) << ";\n";
-        tRef[static_cast<std::size_t>(t)] = q;
-        termAV[static_cast<std::size_t>(t)] = AV::dyn(q);
+        tRef[sz(t)] = q;
+        termAV[sz(t)] = Sym::dyn(q);
     };
     for (int e = 0; e < ir.n_elems; ++e) {
-        const int sl = ir.param_slot[e], tb = ap.termBase[static_cast<std::size_t>(e)];
+        const int sl = ir.param_slot[e], tb = ap.termBase[sz(e)];
         switch (ir.kind[e]) {
             case CSIM_R: toLdsTerm(tb + T_R_G); break;
             case CSIM_C: if (!opt.dcMode) toLdsTerm(tb + T_C_GC); break;
@@ -448,7 +314,7 @@ int emitKernel(std::ostringstream& src, const csim_ir& ir, const AssemblyPlan& a
                     // access did the same but compiled to flat_load (both wait counters): measured
                     // 6.59e8 -> 6.88e8 at B = 4096 and 8.97e9 -> 9.86e9 at B = 65 536
                     if (!opt.rich)
-                        pRef[static_cast<std::size_t>(sl + o)] = "params[" + std::to_string(sl + o) + "LL * SB + bb + vo]";
+                        pRef[sz(sl + o)] = "params[" + std::to_string(sl + o) + "LL * SB + bb + vo]";
                 }
                 break;
             case CSIM_NMOS: case CSIM_PMOS:
@@ -499,14 +365,14 @@ int emitKernel(std::ostringstream& src, const csim_ir& ir, const AssemblyPlan& a
 
     // ---- parameters
     for (int p = 0; p < ir.n_params; ++p) {
-        if (pRef[static_cast<std::size_t>(p)][0] == '(') continue;        // re-read at its use
+        if (pRef[sz(p)][0] == '(') continue;        // re-read at its use
         src << "    const double " << pname(p) << " = params[" << p << "LL * SB + bb];\n";
     }
 
     // ---- launch-constant terms (device_common.hpp terms_const<true>)
     src << "    bool viol = false;      // pivot schedule (or a precondition of it) violated -> general kernel\n";
     for (int e = 0; e < ir.n_elems; ++e) {
-        const int s = ir.param_slot[e], tb = ap.termBase[static_cast<std::size_t>(e)];
+        const int s = ir.param_slot[e], tb = ap.termBase[sz(e)];
         switch (ir.kind[e]) {
             case CSIM_R:
                 src << "    const double " << tname(tb + T_R_G) << " = (" << pname(s) << " == 0.0) ? 0.0 : 1.0 / " << pname(s) << ";\n";
@@ -530,7 +396,7 @@ int emitKernel(std::ostringstream& src, const csim_ir& ir, const AssemblyPlan& a
         }
     }
     if (!opt.dcMode) src << "    const double " << tname(ap.termGmin) << " = " << lit(K.tran_gmin) << ";\n";
-    else termAV[static_cast<std::size_t>(ap.termGmin)] = AV::dyn("gminv");      // ConvController's gmin, per iteration
+    else termAV[sz(ap.termGmin)] = Sym::dyn("gminv");      // ConvController's gmin, per iteration
     src << ldsInit.str();
 
     // ---- state
@@ -589,36 +455,36 @@ int emitKernel(std::ostringstream& src, const csim_ir& ir, const AssemblyPlan& a
     const std::string i2 = "        ";
     if (!opt.stepInLds)
         for (int t = 0; t < ap.nTerms; ++t)
-            if (stepSlot[static_cast<std::size_t>(t)] >= 0) src << i2 << "double " << sname(t) << ";\n";
+            if (stepSlot[sz(t)] >= 0) src << i2 << "double " << sname(t) << ";\n";
     for (int e = 0; e < ir.n_elems; ++e) {
-        const int s = ir.param_slot[e], tb = ap.termBase[static_cast<std::size_t>(e)];
+        const int s = ir.param_slot[e], tb = ap.termBase[sz(e)];
         const int32_t* q = ir.eq + 4 * e;
         switch (ir.kind[e]) {
             case CSIM_V: case CSIM_I:
                 if (opt.dcMode) {
                     // SourceSpec::evalDC (reference include/sim.hpp:152-158): (dc + (SIN ? v0 : 0)) * scale
                     if (ir.wave[e] == CSIM_WAVE_SIN)
-                        src << i2 << sname(tb) << " = (" << pRef[static_cast<std::size_t>(s)] << " + " << pRef[static_cast<std::size_t>(s + 1)] << ") * scale;\n";
+                        src << i2 << sname(tb) << " = (" << pRef[sz(s)] << " + " << pRef[sz(s + 1)] << ") * scale;\n";
                     else
-                        src << i2 << sname(tb) << " = " << pRef[static_cast<std::size_t>(s)] << " * scale;\n";
+                        src << i2 << sname(tb) << " = " << pRef[sz(s)] << " * scale;\n";
                 } else {
-                    emitTranSourceValue(src, i2, ir, e, [&](int o) { return pRef[static_cast<std::size_t>(s + o)]; }, sname(tb));
+                    emitTranSourceValue(src, i2, ir, e, [&](int o) { return pRef[sz(s + o)]; }, sname(tb));
                 }
                 break;
             case CSIM_C:
                 if (opt.dcMode) break;
-                src << i2 << sname(tb + T_C_IH) << " = -" << tRef[static_cast<std::size_t>(tb + T_C_GC)] << " * " << vdiff(q[0], q[1]) << ";\n";
+                src << i2 << sname(tb + T_C_IH) << " = -" << tRef[sz(tb + T_C_GC)] << " * " << vdiff(q[0], q[1]) << ";\n";
                 break;
             case CSIM_L:
                 if (opt.dcMode) break;
-                src << i2 << sname(tb + T_L_VH) << " = -" << tRef[static_cast<std::size_t>(tb + T_L_REQ)] << " * X(" << ir.branch_eq[e] << ");\n";
+                src << i2 << sname(tb + T_L_VH) << " = -" << tRef[sz(tb + T_L_REQ)] << " * X(" << ir.branch_eq[e] << ");\n";
                 break;
             case CSIM_NMOS: case CSIM_PMOS:
                 if (opt.dcMode) break;
-                src << i2 << sname(tb + T_M_IHGS) << " = -" << tRef[static_cast<std::size_t>(tb + T_M_GCH)] << " * " << vdiff(q[1], q[2]) << ";\n"
-                    << i2 << sname(tb + T_M_IHGD) << " = -" << tRef[static_cast<std::size_t>(tb + T_M_GCH)] << " * " << vdiff(q[1], q[0]) << ";\n"
-                    << i2 << sname(tb + T_M_IHSB) << " = -" << tRef[static_cast<std::size_t>(tb + T_M_GCF)] << " * " << vdiff(q[2], q[3]) << ";\n"
-                    << i2 << sname(tb + T_M_IHDB) << " = -" << tRef[static_cast<std::size_t>(tb + T_M_GCF)] << " * " << vdiff(q[0], q[3]) << ";\n";
+                src << i2 << sname(tb + T_M_IHGS) << " = -" << tRef[sz(tb + T_M_GCH)] << " * " << vdiff(q[1], q[2]) << ";\n"
+                    << i2 << sname(tb + T_M_IHGD) << " = -" << tRef[sz(tb + T_M_GCH)] << " * " << vdiff(q[1], q[0]) << ";\n"
+                    << i2 << sname(tb + T_M_IHSB) << " = -" << tRef[sz(tb + T_M_GCF)] << " * " << vdiff(q[2], q[3]) << ";\n"
+                    << i2 << sname(tb + T_M_IHDB) << " = -" << tRef[sz(tb + T_M_GCF)] << " * " << vdiff(q[0], q[3]) << ";\n";
                 break;
             default: break;
         }
@@ -635,24 +501,24 @@ int emitKernel(std::ostringstream& src, const csim_ir& ir, const AssemblyPlan& a
             << i2 << "for (int iter = 0; iter < " << K.tran_max_iters << "; ++iter) {\n"
             << i2 << "    if (!__any(active)) break;\n";
     // ---- per-iteration terms: MOS channel (device_common.hpp mos_eval)
-    std::vector<char> xLoaded(static_cast<std::size_t>(N), 0);
+    std::vector<char> xLoaded(sz(N), 0);
     for (int e = 0; e < ir.n_elems; ++e) {
         if (ir.kind[e] != CSIM_NMOS && ir.kind[e] != CSIM_PMOS) continue;
-        const int s = ir.param_slot[e], tb = ap.termBase[static_cast<std::size_t>(e)];
+        const int s = ir.param_slot[e], tb = ap.termBase[sz(e)];
         const int32_t* q = ir.eq + 4 * e;
         const bool isP = ir.kind[e] == CSIM_PMOS;
         const std::string m = "m" + std::to_string(e) + "_";
         for (int tq = 0; tq < 3; ++tq) {
-            if (q[tq] >= 0 && !xLoaded[static_cast<std::size_t>(q[tq])]) {
+            if (q[tq] >= 0 && !xLoaded[sz(q[tq])]) {
                 g.out << g.ind << "const double " << xloc(q[tq]) << " = " << xname(q[tq]) << ";\n";
-                xLoaded[static_cast<std::size_t>(q[tq])] = 1;
+                xLoaded[sz(q[tq])] = 1;
             }
         }
         const std::string Vd = xloc(q[0]), Vg = xloc(q[1]), Vs = xloc(q[2]);
         const std::string pVth = "m" + std::to_string(e) + "_vth", pK = "m" + std::to_string(e) + "_k",
                           pLam = "m" + std::to_string(e) + "_lam";
-        g.out << g.ind << "const double " << pVth << " = " << pRef[static_cast<std::size_t>(s)] << ", " << pK << " = "
-              << pRef[static_cast<std::size_t>(s + 1)] << ", " << pLam << " = " << pRef[static_cast<std::size_t>(s + 2)] << ";\n";
+        g.out << g.ind << "const double " << pVth << " = " << pRef[sz(s)] << ", " << pK << " = "
+              << pRef[sz(s + 1)] << ", " << pLam << " = " << pRef[sz(s + 2)] << ";\n";
         g.out << g.ind << "// MOS element " << e << (isP ? " (PMOS)" : " (NMOS)") << "\n";
         g.out << g.ind << "const double " << m << "vgs = " << (isP ? "-" : "") << "(" << Vg << " - " << Vs << ");\n"
               << g.ind << "const double " << m << "vds = " << (isP ? "-" : "") << "(" << Vd << " - " << Vs << ");\n"
@@ -678,62 +544,19 @@ int emitKernel(std::ostringstream& src, const csim_ir& ir, const AssemblyPlan& a
     // accumulate into the bool named pvName.
     const int ldsBase = ldsNext;
     int ldsMax = ldsNext;
-    auto emitSolve = [&](const PivotSchedule& sc, const std::string& pvName) -> std::vector<AV> {
+    auto emitSolve = [&](const PivotSchedule& sc, const std::string& pvName) -> std::vector<Sym> {
         ldsNext = ldsBase;                 // parked slots are reused by every alternative
-        // ---- assemble [G | I] symbolically (gather lists of plan.cpp, reference order).
-        // Entries are only RECORDED here; the code of an entry is emitted when the
-        // elimination first reads it (shortens live ranges: ~137 entries would
-        // otherwise all be live at once).
-        std::vector<std::vector<AV>> M(static_cast<std::size_t>(N), std::vector<AV>(static_cast<std::size_t>(N + 1)));
+        // ---- assemble [G | I] symbolically (gather lists of plan.cpp, reference order), lazily
         g.out << g.ind << "// assembly (lazy) + elimination\n";
-        g.pending.assign(static_cast<std::size_t>(N), std::vector<std::vector<AV>>(static_cast<std::size_t>(N + 1)));
-        const GatherPlan& gp = opt.dcMode ? ap.dc : ap.tran;
-        for (int n = 0; n < gp.nnzG(); ++n) {
-            std::vector<AV> terms;
-            for (int c = gp.gPtr[static_cast<std::size_t>(n)]; c < gp.gPtr[static_cast<std::size_t>(n + 1)]; ++c) {
-                const int con = gp.gCon[static_cast<std::size_t>(c)];
-                AV t = termAV[static_cast<std::size_t>(con >> 1)];
-                terms.push_back((con & 1) ? g.negate(t) : t);
-            }
-            const int pos = gp.gPos[static_cast<std::size_t>(n)];
-            g.pending[static_cast<std::size_t>(pos / LD)][static_cast<std::size_t>(pos % LD)] = terms;
-            // structural marker so that zero tests see the entry before it is materialised
-            M[static_cast<std::size_t>(pos / LD)][static_cast<std::size_t>(pos % LD)] = AV::dyn("?");
-        }
-        for (int n = 0; n < gp.nnzI(); ++n) {
-            std::vector<AV> terms;
-            for (int c = gp.iPtr[static_cast<std::size_t>(n)]; c < gp.iPtr[static_cast<std::size_t>(n + 1)]; ++c) {
-                const int con = gp.iCon[static_cast<std::size_t>(c)];
-                AV t = termAV[static_cast<std::size_t>(con >> 1)];
-                terms.push_back((con & 1) ? g.negate(t) : t);
-            }
-            const int r = gp.iRow[static_cast<std::size_t>(n)];
-            g.pending[static_cast<std::size_t>(r)][static_cast<std::size_t>(N)] = terms;
-            M[static_cast<std::size_t>(r)][static_cast<std::size_t>(N)] = AV::dyn("?");
-        }
-        // resolve every all-constant entry now (they cost no code and decide the zero pattern)
-        for (int r = 0; r < N; ++r)
-            for (int c = 0; c <= N; ++c) {
-                auto& pend = g.pending[static_cast<std::size_t>(r)][static_cast<std::size_t>(c)];
-                if (pend.empty()) continue;
-                bool allConst = true;
-                for (const AV& t : pend) allConst = allConst && t.kind != AV::DYN;
-                if (allConst) { M[static_cast<std::size_t>(r)][static_cast<std::size_t>(c)] = g.orderedSum(pend); pend.clear(); }
-            }
-        // materialise on first use
-        auto at = [&](int r, int c) -> AV& {
-            auto& pend = g.pending[static_cast<std::size_t>(r)][static_cast<std::size_t>(c)];
-            AV& slot = M[static_cast<std::size_t>(r)][static_cast<std::size_t>(c)];
-            if (!pend.empty()) { slot = g.orderedSum(pend); pend.clear(); }
-            return slot;
-        };
+        LazyMatrix A(g, N, N + 1);
+        A.assemble(opt.dcMode ? ap.dc : ap.tran, LD, termAV, true, true);
 
         // ---- elimination with the scheduled pivots (solver.hpp:46-77), RHS carried along
-        std::vector<AV> rinv(static_cast<std::size_t>(N));      // 1 / U(k,k)
+        std::vector<Sym> rinv(sz(N));      // 1 / U(k,k)
         int parked = 0;
         for (int k = 0; k < N; ++k) {
-            const int p = sc.pivotPos[static_cast<std::size_t>(k)];
-            const AV ap_ = at(p, k);
+            const int p = sc.pivotPos[sz(k)];
+            const Sym ap_ = A.at(p, k);
             g.out << g.ind << "// column " << k << ": pivot row position " << p << "\n";
             // A scheduling barrier every few columns.  hipcc schedules each basic block for ILP and inflates
             // the live set of this 3000-instruction body; with barriers the allocator ends at 86 spilled
@@ -741,117 +564,86 @@ int emitKernel(std::ostringstream& src, const csim_ir& ir, const AssemblyPlan& a
             // 1/2/3/4/5/6/8/10 with the branch-free checks: 8.41, 8.46, 8.54, 8.53, 8.47, 8.49, 8.48, 8.43e8
             // at B = 4096; a real block boundary (scalar branch on an opaque flag) measured equal within noise.
             if (gopt.barrierEvery > 0 && (k % gopt.barrierEvery) == 0) g.out << g.ind << "__builtin_amdgcn_sched_barrier(0);\n";
-            // the reference picks the FIRST row attaining the column maximum (solver.hpp:48-56)
-            // and fails below 1e-15 (:58-61)
             if (ap_.isZero()) {
                 g.out << g.ind << pvName << " = true;   // scheduled pivot is a structural zero\n";
             } else {
-                const std::string absP = ap_.kind == AV::CONST ? lit(std::fabs(ap_.c)) : "fabs(" + ap_.v + ")";
-                std::vector<std::string> conds;        // all must hold
-                bool contradiction = false;
-                if (ap_.kind == AV::DYN) { conds.push_back("(" + absP + " >= " + lit(K.lu_eps) + ")"); ++g.st.nCmp; }
-                else if (std::fabs(ap_.c) < K.lu_eps) contradiction = true;
-                for (int i = k; i < N; ++i) {
-                    if (i == p) continue;
-                    const AV& ai = at(i, k);
-                    if (ai.isZero()) continue;
-                    const bool before = i < p;
-                    if (ai.kind == AV::CONST && ap_.kind == AV::CONST) {
-                        const bool ok = before ? (std::fabs(ap_.c) > std::fabs(ai.c)) : (std::fabs(ap_.c) >= std::fabs(ai.c));
-                        if (!ok) contradiction = true;   // schedule contradicts constant entries
-                        continue;
-                    }
-                    const std::string absI = ai.kind == AV::CONST ? lit(std::fabs(ai.c)) : "fabs(" + ai.v + ")";
-                    conds.push_back("(" + absP + (before ? " > " : " >= ") + absI + ")");
-                    ++g.st.nCmp;
-                }
-                if (contradiction) g.out << g.ind << pvName << " = true;\n";
-                else if (ap_.kind == AV::DYN) {
+                const PivotRule pr = analysePivot(A, k, p, K.lu_eps);
+                stats.nCmp += static_cast<int>(pr.conds.size());
+                if (pr.contradiction) g.out << g.ind << pvName << " = true;\n";
+                else if (ap_.kind == Sym::DYN) {
                     // one running maximum per side (rows before / after the scheduled one), then at most two
                     // tests per column, accumulated WITHOUT branches ("|=": 8.2e8 vs 6.9e8 at B = 4096 for
                     // short-circuit "||" chains) with 1e-15 folded into the later-rows maximum (+1.9 %).
                     // fmax ignores a NaN operand exactly like the reference's "> maxVal" scan.
-                    std::string mb, ma;
-                    for (int i = k; i < N; ++i) {
-                        if (i == p) continue;
-                        const AV& ai = at(i, k);
-                        if (ai.isZero()) continue;
-                        const std::string absI = ai.kind == AV::CONST ? lit(std::fabs(ai.c)) : "fabs(" + ai.v + ")";
-                        std::string& m = (i < p) ? mb : ma;
-                        m = m.empty() ? absI : "fmax(" + m + ", " + absI + ")";
-                    }
-                    std::string e = ma.empty() ? "(" + absP + " >= " + lit(K.lu_eps) + ")"
-                                               : "(" + absP + " >= fmax(" + ma + ", " + lit(K.lu_eps) + "))";
-                    if (!mb.empty()) e += " & (" + absP + " > " + mb + ")";
+                    std::string e = pr.maxAfter.empty() ? "(" + pr.absP + " >= " + lit(K.lu_eps) + ")"
+                                                        : "(" + pr.absP + " >= fmax(" + pr.maxAfter + ", " + lit(K.lu_eps) + "))";
+                    if (!pr.maxBefore.empty()) e += " & (" + pr.absP + " > " + pr.maxBefore + ")";
                     g.out << g.ind << pvName << " |= !(" << e << ");\n";
                 } else {
                     // constant pivot (a +-1 incidence entry) against run-time candidates: short-circuit form.
                     // Its block boundaries are load-bearing for hipcc's register allocation of this body
                     // (branch-free "|=" here: 46 -> 243 spilled registers, 8.5e8 -> 4.8e8 at B = 4096).
-                    for (const std::string& c : conds) g.out << g.ind << pvName << " = " << pvName << " || !" << c << ";\n";
+                    for (const std::string& c : pr.conds) g.out << g.ind << pvName << " = " << pvName << " || !" << c << ";\n";
                 }
             }
-            if (p != k) {
-                std::swap(M[static_cast<std::size_t>(p)], M[static_cast<std::size_t>(k)]);
-                std::swap(g.pending[static_cast<std::size_t>(p)], g.pending[static_cast<std::size_t>(k)]);
-            }
-            const AV piv = at(k, k);
-            AV r;                       // what the row is scaled with: 1 / pivot, or (faithful) the pivot itself as divisor
+            if (p != k) A.swapRows(p, k);
+            const Sym piv = A.at(k, k);
+            Sym r;                       // what the row is scaled with: 1 / pivot, or (faithful) the pivot itself as divisor
             if (opt.faithful) r = piv;
-            else if (piv.kind == AV::CONST) r = AV::konst(1.0 / piv.c);
-            else if (piv.kind == AV::DYN) { r = g.emit("rcp_nr(" + g.ref(piv) + ")"); ++g.st.nRecip; }
-            rinv[static_cast<std::size_t>(k)] = r;
+            else if (piv.kind == Sym::CONST) r = Sym::konst(1.0 / piv.c);
+            else if (piv.kind == Sym::DYN) { r = g.emit("rcp_nr(" + g.ref(piv) + ")"); ++stats.nRecip; }
+            rinv[sz(k)] = r;
             for (int i = k + 1; i < N; ++i) {
-                const AV aik = at(i, k);
+                const Sym aik = A.at(i, k);
                 if (aik.isZero()) continue;
-                ++g.st.nLower;
-                const AV f = opt.faithful ? g.div(aik, r) : g.mul(aik, r);     // multiplier (solver.hpp:71)
+                ++stats.nLower;
+                const Sym f = opt.faithful ? g.div(aik, r) : g.mul(aik, r);     // multiplier (solver.hpp:71)
                 for (int j = k + 1; j <= N; ++j) {
-                    if (M[static_cast<std::size_t>(k)][static_cast<std::size_t>(j)].isZero()) continue;
-                    const AV u = at(k, j);
+                    if (A.cell(k, j).isZero()) continue;
+                    const Sym u = A.at(k, j);
                     if (u.isZero()) continue;
-                    const AV a = at(i, j);
-                    M[static_cast<std::size_t>(i)][static_cast<std::size_t>(j)] = g.fnma(a, f, u);   // :74
+                    const Sym a = A.at(i, j);
+                    A.cell(i, j) = g.fnma(a, f, u);   // :74
                 }
-                M[static_cast<std::size_t>(i)][static_cast<std::size_t>(k)] = AV::zero();
+                A.cell(i, k) = Sym();
             }
             // row k is final: it is next read in the back substitution.  The rich variant parks
             // its run-time entries (and the pivot reciprocal) in LDS instead of leaving it to the
             // register allocator to spill them to scratch.
             if (opt.parkBudget != 0) {
                 for (int j = k + 1; j <= N; ++j) {
-                    if (M[static_cast<std::size_t>(k)][static_cast<std::size_t>(j)].isZero()) continue;
-                    const AV v = at(k, j);
-                    if (v.kind != AV::DYN) continue;
+                    if (A.cell(k, j).isZero()) continue;
+                    const Sym v = A.at(k, j);
+                    if (v.kind != Sym::DYN) continue;
                     if (opt.parkBudget > 0 && parked >= opt.parkBudget) break;
                     ++parked;
                     const std::string q = qslot();
                     g.out << g.ind << q << " = " << g.ref(v) << ";\n";
-                    M[static_cast<std::size_t>(k)][static_cast<std::size_t>(j)] = AV::dyn(q);
+                    A.cell(k, j) = Sym::dyn(q);
                 }
-                if (r.kind == AV::DYN && (opt.parkBudget < 0 || parked < opt.parkBudget)) {
+                if (r.kind == Sym::DYN && (opt.parkBudget < 0 || parked < opt.parkBudget)) {
                     ++parked;
                     const std::string q = qslot();
                     g.out << g.ind << q << " = " << g.ref(r) << ";\n";
-                    rinv[static_cast<std::size_t>(k)] = AV::dyn(q);
+                    rinv[sz(k)] = Sym::dyn(q);
                 }
             }
         }
 
         // ---- back substitution (solver.hpp:116-128): row i descending, j ascending
         g.out << g.ind << "// back substitution\n";
-        std::vector<AV> xr(static_cast<std::size_t>(N));
+        std::vector<Sym> xr(sz(N));
         for (int i = N - 1; i >= 0; --i) {
-            AV sum = at(i, N);
+            Sym sum = A.at(i, N);
             for (int j = i + 1; j < N; ++j) {
-                if (M[static_cast<std::size_t>(i)][static_cast<std::size_t>(j)].isZero()) continue;
-                const AV u = at(i, j);
+                if (A.cell(i, j).isZero()) continue;
+                const Sym u = A.at(i, j);
                 if (u.isZero()) continue;
-                if (u.kind == AV::DYN) ++g.st.nDynU;
-                sum = g.fnma(sum, u, xr[static_cast<std::size_t>(j)]);
+                if (u.kind == Sym::DYN) ++stats.nDynU;
+                sum = g.fnma(sum, u, xr[sz(j)]);
             }
-            xr[static_cast<std::size_t>(i)] = opt.faithful ? g.div(sum, rinv[static_cast<std::size_t>(i)])      // :126
-                                                           : g.mul(sum, rinv[static_cast<std::size_t>(i)]);
+            xr[sz(i)] = opt.faithful ? g.div(sum, rinv[sz(i)])      // :126
+                                                           : g.mul(sum, rinv[sz(i)]);
         }
 
 
@@ -869,11 +661,11 @@ int emitKernel(std::ostringstream& src, const csim_ir& ir, const AssemblyPlan& a
         if (alt == 0) g.out << g.ind << "{\n";
         else g.out << g.ind << "if (__any(active && pv)) {   // alternative schedule " << alt << "\n";
         g.out << g.ind << "bool " << pvName << " = false;\n";
-        const std::vector<AV> sol = emitSolve(alternatives[alt], pvName);
-        if (alt == 0) firstAlt = g.st;             // operation counts of ONE solve on the most frequent schedule
+        const std::vector<Sym> sol = emitSolve(alternatives[alt], pvName);
+        if (alt == 0) firstAlt = stats;             // operation counts of ONE solve on the most frequent schedule
         for (int i = 0; i < N; ++i) {
-            if (alt == 0) g.out << g.ind << "xr" << i << " = " << g.ref(sol[static_cast<std::size_t>(i)]) << ";\n";
-            else g.out << g.ind << "xr" << i << " = pv ? " << g.ref(sol[static_cast<std::size_t>(i)]) << " : xr" << i << ";\n";
+            if (alt == 0) g.out << g.ind << "xr" << i << " = " << g.ref(sol[sz(i)]) << ";\n";
+            else g.out << g.ind << "xr" << i << " = pv ? " << g.ref(sol[sz(i)]) << " : xr" << i << ";\n";
         }
         if (alt == 0) g.out << g.ind << "pv = " << pvName << ";\n";
         else g.out << g.ind << "pv = pv && " << pvName << ";\n";

@@ -1,6 +1,7 @@
 // codegen_group.cpp -- HIP emitter of the sixteen- and four-lanes-per-instance scheduled transient kernels
 // (plan and rationale: group_plan.hpp).  The emitted kernel has the parameters and the hand-over
 // protocol of the lane-per-instance kernel (codegen.cpp): fallback[], done[], violFlag.
+#include "codegen_sym.hpp"
 #include "group_plan.hpp"
 
 #include <cmath>
@@ -10,23 +11,6 @@
 namespace csim {
 
 namespace {
-
-std::string lit(double x)
-{
-    char buf[64];
-    std::snprintf(buf, sizeof buf, "%a", x);
-    return std::string("(") + buf + ")";
-}
-
-std::string intArray(const std::string& name, const std::vector<int32_t>& v)
-{
-    std::ostringstream o;
-    o << "static __device__ const int " << name << "[" << (v.empty() ? 1 : v.size()) << "] = {";
-    if (v.empty()) o << "0";
-    for (std::size_t i = 0; i < v.size(); ++i) o << (i ? "," : "") << ((i % 32 == 31) ? "\n    " : "") << v[i];
-    o << "};\n";
-    return o.str();
-}
 
 // device code that does not depend on the circuit: element terms restated from the reference
 // (the general kernels' versions live in device_common.hpp; a generated library is self-contained)

@@ -32,174 +32,15 @@
 //   csim_tran_linear_kernel   one lane per instance, iterate and x_raw in LDS, tape streamed from global
 //       memory -- circuits whose tape does not fit the register file (N = 601 ladder of the tests).
 #include "codegen.hpp"
+#include "codegen_sym.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <functional>
 #include <sstream>
 
 namespace csim {
-
-namespace {
-
-std::string lit(double x)
-{
-    char buf[64];
-    std::snprintf(buf, sizeof buf, "%a", x);
-    return std::string("(") + buf + ")";
-}
-
-// abstract value: structural zero, exact constant, or an expression evaluated at run time
-struct LV {
-    enum Kind { ZERO, CONST, DYN } kind = ZERO;
-    double c = 0.0;
-    std::string e;           // DYN: expression (a variable name or a load)
-    bool neg = false;
-    static LV konst(double x) { LV a; if (x == 0.0) return a; a.kind = CONST; a.c = x; return a; }
-    static LV dyn(const std::string& s, bool n = false) { LV a; a.kind = DYN; a.e = s; a.neg = n; return a; }
-    bool zero() const { return kind == ZERO; }
-};
-
-struct LGen {
-    std::ostringstream out;
-    std::string ind, prefix;
-    int tmp = 0;
-    std::string ref(const LV& a) const
-    {
-        if (a.kind == LV::CONST) return lit(a.c);
-        if (a.kind == LV::DYN) return a.neg ? "(-" + a.e + ")" : a.e;
-        return "0.0";
-    }
-    LV emit(const std::string& expr)
-    {
-        const std::string n = prefix + std::to_string(tmp++);
-        out << ind << "const double " << n << " = " << expr << ";\n";
-        return LV::dyn(n);
-    }
-    LV negate(LV a) { if (a.kind == LV::CONST) a.c = -a.c; else if (a.kind == LV::DYN) a.neg = !a.neg; return a; }
-    LV mul(const LV& a, const LV& b)
-    {
-        if (a.zero() || b.zero()) return LV();
-        if (a.kind == LV::CONST && b.kind == LV::CONST) return LV::konst(a.c * b.c);
-        if (a.kind == LV::CONST || b.kind == LV::CONST) {
-            const LV& k = a.kind == LV::CONST ? a : b;
-            const LV& d = a.kind == LV::CONST ? b : a;
-            if (k.c == 1.0) return d;
-            if (k.c == -1.0) return negate(d);
-            return emit(lit(k.c) + " * " + ref(d));
-        }
-        LV r = emit(a.e + " * " + b.e);
-        r.neg = a.neg != b.neg;
-        return r;
-    }
-    LV div(const LV& a, const LV& b)                     // a / b, a true division (solver.hpp:71)
-    {
-        if (a.zero()) return LV();
-        if (a.kind == LV::CONST && b.kind == LV::CONST) return LV::konst(a.c / b.c);
-        if (b.kind == LV::CONST && b.c == 1.0) return a;
-        if (b.kind == LV::CONST && b.c == -1.0) return negate(a);
-        LV r = emit((a.kind == LV::CONST ? lit(a.c) : a.e) + " / " + (b.kind == LV::CONST ? lit(b.c) : b.e));
-        r.neg = (a.kind == LV::DYN && a.neg) != (b.kind == LV::DYN && b.neg);
-        return r;
-    }
-    LV fnma(const LV& a, const LV& f, const LV& u)      // a - f*u
-    {
-        if (f.zero() || u.zero()) return a;
-        if (a.zero()) return negate(mul(f, u));
-        if (f.kind == LV::CONST && u.kind == LV::CONST) {
-            const double p = f.c * u.c;
-            if (a.kind == LV::CONST) return LV::konst(a.c - p);
-            return emit(ref(a) + " - " + lit(p));
-        }
-        const bool f1 = f.kind == LV::CONST && std::fabs(f.c) == 1.0, u1 = u.kind == LV::CONST && std::fabs(u.c) == 1.0;
-        if (f1 || u1) {
-            LV w = f1 ? u : f;
-            if ((f1 ? f.c : u.c) < 0) w = negate(w);
-            return emit(ref(a) + " - " + ref(w));
-        }
-        return emit(ref(a) + " - " + ref(f) + " * " + ref(u));
-    }
-    LV orderedSum(const std::vector<LV>& terms)           // the reference's accumulation order
-    {
-        bool allConst = true;
-        for (const LV& t : terms) allConst = allConst && t.kind != LV::DYN;
-        if (allConst) {
-            double acc = 0.0;
-            for (const LV& t : terms) acc = acc + (t.kind == LV::CONST ? t.c : 0.0);
-            return LV::konst(acc);
-        }
-        std::vector<LV> nz;
-        for (const LV& t : terms) if (!t.zero()) nz.push_back(t);
-        if (nz.size() == 1) return nz[0];
-        std::string e;
-        for (std::size_t i = 0; i < nz.size(); ++i) {
-            const LV& t = nz[i];
-            if (i == 0) { e = ref(t); continue; }
-            if (t.kind == LV::DYN) e = "(" + e + (t.neg ? " - " : " + ") + t.e + ")";
-            else e = "(" + e + " + " + lit(t.c) + ")";
-        }
-        return emit(e);
-    }
-};
-
-} // namespace
-
-// TRAN source value of element e into `target` (shared with codegen.cpp): SourceSpec::evalTran with
-// TranWaveform::eval (reference include/sim.hpp:75-143,160-162).  P(o) = expression of parameter slot o.
-void emitTranSourceValue(std::ostream& src, const std::string& i2, const csim_ir& ir, int e,
-                         const std::function<std::string(int)>& P, const std::string& target)
-{
-    const csim_consts& K = ir.k;
-    if (ir.wave[e] == CSIM_WAVE_SIN) {
-        src << i2 << "if (tNow < " << P(4) << ") " << target << " = " << P(0) << " + " << P(1) << ";\n"
-            << i2 << "else " << target << " = " << P(0) << " + (" << P(1) << " + " << P(2)
-            << " * sin((2.0 * " << lit(K.pi) << " * " << P(3) << ") * (tNow - " << P(4) << ") + " << P(5) << "));\n";
-    } else if (ir.wave[e] == CSIM_WAVE_PULSE) {
-        src << i2 << "{\n"
-            << i2 << "    const double v1 = " << P(1) << ", v2 = " << P(2) << ", td = " << P(3) << ", tr = " << P(4)
-            << ", tf = " << P(5) << ", ton = " << P(6) << ", per = " << P(7) << ";\n"
-            << i2 << "    double w;\n"
-            << i2 << "    if (per <= 0.0) {\n"
-            << i2 << "        const double tau = tNow - td;\n"
-            << i2 << "        if (tau <= 0.0) w = v1;\n"
-            << i2 << "        else if (tau < tr) w = v1 + clamp01_cg(tau / tr) * (v2 - v1);\n"
-            << i2 << "        else if (tau < tr + ton) w = v2;\n"
-            << i2 << "        else w = v2 + clamp01_cg((tau - (tr + ton)) / tf) * (v1 - v2);\n"
-            << i2 << "    } else if (tNow < td) {\n"
-            << i2 << "        w = v1;\n"
-            << i2 << "    } else {\n"
-            << i2 << "        double tau = fmod(tNow - td, per);\n"
-            << i2 << "        if (tau < 0.0) tau += per;\n"
-            << i2 << "        if (tau < tr) w = v1 + (v2 - v1) * clamp01_cg(tau / tr);\n"
-            << i2 << "        else if (tau < tr + ton) w = v2;\n"
-            << i2 << "        else if (tau < tr + ton + tf) w = v2 + (v1 - v2) * clamp01_cg((tau - (tr + ton)) / tf);\n"
-            << i2 << "        else w = v1;\n"
-            << i2 << "    }\n"
-            << i2 << "    " << target << " = " << P(0) << " + w;\n"
-            << i2 << "}\n";
-    } else if (ir.wave[e] == CSIM_WAVE_PWL) {
-        const int n = ir.wave_n[e];
-        auto PT = [&](int i) { return P(1 + i); };
-        auto PV = [&](int i) { return P(1 + n + i); };
-        src << i2 << "{\n" << i2 << "    double w;\n";
-        if (n <= 0) {
-            src << i2 << "    w = 0.0;\n";
-        } else {
-            src << i2 << "    if (tNow <= " << PT(0) << ") w = " << PV(0) << ";\n"
-                << i2 << "    else if (tNow >= " << PT(n - 1) << ") w = " << PV(n - 1) << ";\n";
-            for (int i = 0; i + 1 < n; ++i)
-                src << i2 << "    else if (tNow > " << PT(i) << " && tNow <= " << PT(i + 1) << ") { const double ta = " << PT(i)
-                    << ", tb = " << PT(i + 1) << ", va = " << PV(i) << ", vb = " << PV(i + 1)
-                    << "; w = va + (vb - va) * ((tNow - ta) / (tb - ta)); }\n";
-            src << i2 << "    else w = " << PV(n - 1) << ";\n";
-        }
-        src << i2 << "    " << target << " = " << P(0) << " + w;\n" << i2 << "}\n";
-    } else {
-        src << i2 << target << " = " << P(0) << " + 0.0;\n";
-    }
-}
 
 namespace {
 
@@ -223,13 +64,13 @@ std::string linearPrelude()
 // `pk`) is stored, "@F<h>|<expr>@" where the factor block itself reads a launch constant back.  A back-end
 // numbers the reads (tape positions) and resolveFactorText() stores every handle to all positions that read it.
 std::string rdHandle(int h) { return "@L" + std::to_string(h) + "@"; }
-int handleOf(const LV& v)          // handle of a parked run-time value, -1 for anything else
+int handleOf(const Sym& v)          // handle of a parked run-time value, -1 for anything else
 {
-    if (v.kind != LV::DYN || v.e.size() < 4 || v.e.compare(0, 2, "@L") != 0) return -1;
+    if (v.kind != Sym::DYN || v.e.size() < 4 || v.e.compare(0, 2, "@L") != 0) return -1;
     return std::atoi(v.e.c_str() + 2);
 }
 
-struct FwdOp { int i, k; LV f; };              // b_i -= f * b_k, row positions at that point of the elimination
+struct FwdOp { int i, k; Sym f; };              // b_i -= f * b_k, row positions at that point of the elimination
 
 // Symbolic factorisation of a linear circuit's transient matrix with the recorded pivots, shared by both
 // linear kernels.  `text` is device code for ONE lane = one instance (it expects params, SB, bb, vo0, dt,
@@ -240,8 +81,8 @@ struct LinearFactor {
     std::string text;
     std::vector<FwdOp> fwd;
     std::vector<int> swapWith;                  // row swap of column k (position), in order
-    std::vector<std::vector<LV>> U;             // finished rows: U[k][j], j > k
-    std::vector<LV> piv, rinv;                  // U(k,k) and its correctly rounded reciprocal
+    std::vector<std::vector<Sym>> U;            // finished rows: U[k][j], j > k
+    std::vector<Sym> piv, rinv;                 // U(k,k) and its correctly rounded reciprocal
     std::vector<int> coefHandle;                // per element: handle of C/dt (capacitor) or L/dt (inductor), else -1
 };
 
@@ -250,50 +91,48 @@ void buildLinearFactor(const csim_ir& ir, const AssemblyPlan& ap, const PivotSch
 {
     const int N = ir.n_unknowns;
     const csim_consts& K = ir.k;
-    const int LD = ap.LD;
-    const GatherPlan& gpl = dcMode ? ap.dc : ap.tran;
     int& nHandles = F.nHandles;
     auto rd = rdHandle;
     auto st = [](int h) { return "@S" + std::to_string(h) + "@"; };
-    F.coefHandle.assign(static_cast<std::size_t>(ir.n_elems), -1);
+    F.coefHandle.assign(sz(ir.n_elems), -1);
     // "@F<h>|<expr>@": the factor block's read of a launch constant -- from the tape where the step reads it too
     // (its first slot), else <expr>.  Recomputing it from params there made hipcc keep the parameter's ADDRESS
     // from the first read alive across the whole factor block: 631 spilled addresses, a 4.9 KB scratch frame.
     auto rdF = [](int h, const std::string& expr) { return "@F" + std::to_string(h) + "|" + expr + "@"; };
     // ---- terms.  Launch constants are written to the store once (factor block) and re-read where needed.
-    std::vector<LV> termF(static_cast<std::size_t>(ap.nTerms));
+    std::vector<Sym> termF(sz(ap.nTerms));
     std::ostringstream consts;                            // code that fills the launch constants
     int nConstStmts = 0;                                  // a scheduling barrier every 16: see the factor block
-    termF[static_cast<std::size_t>(ap.termOne)] = LV::konst(1.0);
-    termF[static_cast<std::size_t>(ap.termGmin)] = dcMode ? LV() : LV::konst(K.tran_gmin);      // the direct DC solve stamps no gmin
+    termF[sz(ap.termOne)] = Sym::konst(1.0);
+    termF[sz(ap.termGmin)] = dcMode ? Sym() : Sym::konst(K.tran_gmin);      // the direct DC solve stamps no gmin
     auto PX = [](int slot) { return "params[" + std::to_string(slot) + "LL * SB + bb]"; };
     // the same parameter as read by the factor block: through an always-zero offset the compiler cannot fold, so that
     // it does not keep all C/dt of the tape-filling block alive (in scratch) for the factor block's matrix entries
     auto PF = [](int slot) { return "params[" + std::to_string(slot) + "LL * SB + bb + vo0]"; };
     for (int e = 0; e < ir.n_elems; ++e) {
-        const int s = ir.param_slot[e], tb = ap.termBase[static_cast<std::size_t>(e)];
+        const int s = ir.param_slot[e], tb = ap.termBase[sz(e)];
         switch (ir.kind[e]) {
             case CSIM_R:
                 // used by the factorisation only (once per launch): evaluated where a G entry needs it
-                termF[static_cast<std::size_t>(tb + T_R_G)] = LV::dyn("lin_ginv(" + PF(s) + ")");
+                termF[sz(tb + T_R_G)] = Sym::dyn("lin_ginv(" + PF(s) + ")");
                 break;
             case CSIM_C: {
                 if (dcMode) break;                                          // open at DC
                 const int h = nHandles++;
-                F.coefHandle[static_cast<std::size_t>(e)] = h;
+                F.coefHandle[sz(e)] = h;
                 consts << "    { const double pk = lin_gc(" << PX(s) << ", dt); " << st(h) << " }\n";
                 if ((++nConstStmts % 16) == 0) consts << "    __builtin_amdgcn_sched_barrier(0);\n";
-                termF[static_cast<std::size_t>(tb + T_C_GC)] = LV::dyn(rdF(h, "lin_gc(" + PF(s) + ", dt)"));
+                termF[sz(tb + T_C_GC)] = Sym::dyn(rdF(h, "lin_gc(" + PF(s) + ", dt)"));
                 break;
             }
             case CSIM_L: {
                 if (dcMode) break;                                          // a 0 V source at DC: the plan's exact +-1 incidence only
                 const int h = nHandles++;
-                F.coefHandle[static_cast<std::size_t>(e)] = h;
+                F.coefHandle[sz(e)] = h;
                 consts << "    { const double L = " << PX(s) << "; viol = viol || !(L > 0.0); const double pk = L / dt; " << st(h) << " }\n";
                 if ((++nConstStmts % 16) == 0) consts << "    __builtin_amdgcn_sched_barrier(0);\n";
-                termF[static_cast<std::size_t>(tb + T_L_REQ)] = LV::dyn(rdF(h, "(" + PF(s) + " / dt)"));
-                termF[static_cast<std::size_t>(tb + T_L_ONE)] = LV::konst(1.0);
+                termF[sz(tb + T_L_REQ)] = Sym::dyn(rdF(h, "(" + PF(s) + " / dt)"));
+                termF[sz(tb + T_L_ONE)] = Sym::konst(1.0);
                 break;
             }
             default: break;
@@ -301,110 +140,71 @@ void buildLinearFactor(const csim_ir& ir, const AssemblyPlan& ap, const PivotSch
     }
 
     // ---- factor block: assembly of G (lazy) + elimination with the recorded pivots (solver.hpp:46-77)
-    LGen gf;
-    gf.ind = "    ";
-    gf.prefix = "vf";
-    std::vector<std::vector<LV>> M(static_cast<std::size_t>(N), std::vector<LV>(static_cast<std::size_t>(N)));
-    std::vector<std::vector<std::vector<LV>>> pend(static_cast<std::size_t>(N), std::vector<std::vector<LV>>(static_cast<std::size_t>(N)));
-    for (int n = 0; n < gpl.nnzG(); ++n) {
-        std::vector<LV> terms;
-        for (int c = gpl.gPtr[static_cast<std::size_t>(n)]; c < gpl.gPtr[static_cast<std::size_t>(n + 1)]; ++c) {
-            const int con = gpl.gCon[static_cast<std::size_t>(c)];
-            LV t = termF[static_cast<std::size_t>(con >> 1)];
-            terms.push_back((con & 1) ? gf.negate(t) : t);
-        }
-        const int pos = gpl.gPos[static_cast<std::size_t>(n)];
-        bool allConst = true;
-        for (const LV& t : terms) allConst = allConst && t.kind != LV::DYN;
-        if (allConst) M[static_cast<std::size_t>(pos / LD)][static_cast<std::size_t>(pos % LD)] = gf.orderedSum(terms);
-        else { pend[static_cast<std::size_t>(pos / LD)][static_cast<std::size_t>(pos % LD)] = terms; M[static_cast<std::size_t>(pos / LD)][static_cast<std::size_t>(pos % LD)] = LV::dyn("?"); }
-    }
-    auto at = [&](int r, int c) -> LV& {
-        auto& p = pend[static_cast<std::size_t>(r)][static_cast<std::size_t>(c)];
-        LV& slot = M[static_cast<std::size_t>(r)][static_cast<std::size_t>(c)];
-        if (!p.empty()) { slot = gf.orderedSum(p); p.clear(); }
-        return slot;
-    };
-    auto park = [&](const LV& v) -> LV {                   // run-time value -> the tape; constants stay constants
-        if (v.kind != LV::DYN) return v;
+    SymGen gf("    ", "vf");
+    LazyMatrix A(gf, N, N);
+    A.assemble(dcMode ? ap.dc : ap.tran, ap.LD, termF, true, false);
+    auto park = [&](const Sym& v) -> Sym {                 // run-time value -> the tape; constants stay constants
+        if (v.kind != Sym::DYN) return v;
         const int h = nHandles++;
         gf.out << gf.ind << "{ const double pk = " << gf.ref(v) << "; " << st(h) << " }\n";
-        return LV::dyn(rd(h));
+        return Sym::dyn(rd(h));
     };
     std::vector<FwdOp>& fwd = F.fwd;                       // b_i -= f * b_k, in elimination order
     std::vector<int>& swapWith = F.swapWith;
-    swapWith.assign(static_cast<std::size_t>(N), 0);
-    std::vector<LV>& rinv = F.rinv;
-    rinv.assign(static_cast<std::size_t>(N), LV());
-    F.piv.assign(static_cast<std::size_t>(N), LV());
+    swapWith.assign(sz(N), 0);
+    std::vector<Sym>& rinv = F.rinv;
+    rinv.assign(sz(N), Sym());
+    F.piv.assign(sz(N), Sym());
     for (int k = 0; k < N; ++k) {
-        const int p = sc.pivotPos[static_cast<std::size_t>(k)];
-        swapWith[static_cast<std::size_t>(k)] = p;
-        const LV pv = at(p, k);
+        const int p = sc.pivotPos[sz(k)];
+        swapWith[sz(k)] = p;
+        const Sym pv = A.at(p, k);
         gf.out << gf.ind << "// column " << k << ": pivot row position " << p << "\n";
         // scheduling barriers: without them hipcc hoists hundreds of loads to the top of these long
         // straight-line blocks and spills what it hoisted (16 KB of scratch per lane, measured)
         if ((k % 2) == 0) gf.out << gf.ind << "__builtin_amdgcn_sched_barrier(0);\n";
-        if (pv.zero()) {
+        if (pv.isZero()) {
             gf.out << gf.ind << "pvF = 1;   // scheduled pivot is a structural zero\n";
         } else {
-            // first row attaining the column maximum (solver.hpp:48-56), >= 1e-15 (:58-61)
-            const std::string absP = pv.kind == LV::CONST ? lit(std::fabs(pv.c)) : "fabs(" + pv.e + ")";
-            std::string mb, ma;
-            bool contradiction = pv.kind == LV::CONST && std::fabs(pv.c) < K.lu_eps;
-            for (int i = k; i < N; ++i) {
-                if (i == p) continue;
-                const LV& ai = at(i, k);
-                if (ai.zero()) continue;
-                if (ai.kind == LV::CONST && pv.kind == LV::CONST) {
-                    const bool ok = i < p ? std::fabs(pv.c) > std::fabs(ai.c) : std::fabs(pv.c) >= std::fabs(ai.c);
-                    if (!ok) contradiction = true;
-                    continue;
-                }
-                const std::string absI = ai.kind == LV::CONST ? lit(std::fabs(ai.c)) : "fabs(" + ai.e + ")";
-                std::string& m = (i < p) ? mb : ma;
-                m = m.empty() ? absI : "fmax(" + m + ", " + absI + ")";
-            }
-            if (contradiction) gf.out << gf.ind << "pvF = 1;\n";
+            const PivotRule pr = analysePivot(A, k, p, K.lu_eps);
+            if (pr.contradiction) gf.out << gf.ind << "pvF = 1;\n";
             else {
                 std::string e;
-                if (pv.kind == LV::DYN) e = ma.empty() ? "(" + absP + " >= " + lit(K.lu_eps) + ")" : "(" + absP + " >= fmax(" + ma + ", " + lit(K.lu_eps) + "))";
-                else if (!ma.empty()) e = "(" + absP + " >= " + ma + ")";
-                if (!mb.empty()) e += std::string(e.empty() ? "" : " & ") + "(" + absP + " > " + mb + ")";
+                if (pv.kind == Sym::DYN) e = pr.maxAfter.empty() ? "(" + pr.absP + " >= " + lit(K.lu_eps) + ")" : "(" + pr.absP + " >= fmax(" + pr.maxAfter + ", " + lit(K.lu_eps) + "))";
+                else if (!pr.maxAfter.empty()) e = "(" + pr.absP + " >= " + pr.maxAfter + ")";
+                if (!pr.maxBefore.empty()) e += std::string(e.empty() ? "" : " & ") + "(" + pr.absP + " > " + pr.maxBefore + ")";
                 // The flag is an int that an empty asm "uses" after every test: left as a bool that only the end of
                 // the block reads, the compiler sinks all 257 tests there and keeps their operands alive until then
                 // (528 spilled doubles, most of a 4.2 KB scratch frame).
                 if (!e.empty()) gf.out << gf.ind << "pvF |= (" << e << ") ? 0 : 1; asm volatile(\"\" : \"+v\"(pvF));\n";
             }
         }
-        if (p != k) { std::swap(M[static_cast<std::size_t>(p)], M[static_cast<std::size_t>(k)]); std::swap(pend[static_cast<std::size_t>(p)], pend[static_cast<std::size_t>(k)]); }
-        const LV piv = at(k, k);
-        LV r;                                                             // correctly rounded 1 / pivot (for :126)
-        if (piv.kind == LV::CONST) r = LV::konst(1.0 / piv.c);
-        else if (piv.kind == LV::DYN) r = gf.emit("1.0 / " + gf.ref(piv));
+        if (p != k) A.swapRows(p, k);
+        const Sym piv = A.at(k, k);
+        Sym r;                                                            // correctly rounded 1 / pivot (for :126)
+        if (piv.kind == Sym::CONST) r = Sym::konst(1.0 / piv.c);
+        else if (piv.kind == Sym::DYN) r = gf.emit("1.0 / " + gf.ref(piv));
         for (int i = k + 1; i < N; ++i) {
-            const LV aik = at(i, k);
-            if (aik.zero()) continue;
-            const LV f = gf.div(aik, piv);                                // multiplier, a true division (solver.hpp:71)
+            const Sym aik = A.at(i, k);
+            if (aik.isZero()) continue;
+            const Sym f = gf.div(aik, piv);                               // multiplier, a true division (solver.hpp:71)
             for (int j = k + 1; j < N; ++j) {
-                if (M[static_cast<std::size_t>(k)][static_cast<std::size_t>(j)].zero()) continue;
-                const LV u = at(k, j);
-                if (u.zero()) continue;
-                const LV a = at(i, j);
-                M[static_cast<std::size_t>(i)][static_cast<std::size_t>(j)] = gf.fnma(a, f, u);   // :74
+                if (A.cell(k, j).isZero()) continue;
+                const Sym u = A.at(k, j);
+                if (u.isZero()) continue;
+                const Sym a = A.at(i, j);
+                A.cell(i, j) = gf.fnma(a, f, u);                          // :74
             }
-            M[static_cast<std::size_t>(i)][static_cast<std::size_t>(k)] = LV();
+            A.cell(i, k) = Sym();
             fwd.push_back({i, k, park(f)});
         }
         // row k is final: park its run-time entries and the reciprocal
-        for (int j = k + 1; j < N; ++j) {
-            if (M[static_cast<std::size_t>(k)][static_cast<std::size_t>(j)].zero()) continue;
-            M[static_cast<std::size_t>(k)][static_cast<std::size_t>(j)] = park(at(k, j));
-        }
-        rinv[static_cast<std::size_t>(k)] = park(r);
-        F.piv[static_cast<std::size_t>(k)] = park(piv);
+        for (int j = k + 1; j < N; ++j)
+            if (!A.cell(k, j).isZero()) A.cell(k, j) = park(A.at(k, j));
+        rinv[sz(k)] = park(r);
+        F.piv[sz(k)] = park(piv);
     }
-    F.U = M;
+    F.U = A.M;
     F.text = consts.str() + "    // factorisation, once per launch: G does not depend on the iterate or on time\n    int pvF = 0;\n" + gf.out.str();
 }
 
@@ -420,7 +220,7 @@ std::string resolveFactorText(std::string factorText, const std::vector<std::vec
         const std::size_t b = factorText.find('@', a + 2);
         const int h = std::atoi(factorText.substr(a + 2, b - a - 2).c_str());
         outText += factorText.substr(i, a - i);
-        for (int n : uses[static_cast<std::size_t>(h)]) outText += "TW(" + std::to_string(n) + ") = pk; ";
+        for (int n : uses[sz(h)]) outText += "TW(" + std::to_string(n) + ") = pk; ";
         i = b + 1;
     }
     factorText = outText;
@@ -432,7 +232,7 @@ std::string resolveFactorText(std::string factorText, const std::vector<std::vec
         const std::size_t bar = factorText.find('|', a + 2), b = factorText.find('@', bar + 1);
         const int h = std::atoi(factorText.substr(a + 2, bar - a - 2).c_str());
         outText += factorText.substr(i, a - i);
-        if (!uses[static_cast<std::size_t>(h)].empty()) outText += "TF(" + std::to_string(uses[static_cast<std::size_t>(h)][0]) + ")";
+        if (!uses[sz(h)].empty()) outText += "TF(" + std::to_string(uses[sz(h)][0]) + ")";
         else outText += factorText.substr(bar + 1, b - bar - 1);
         i = b + 1;
     }
@@ -443,17 +243,82 @@ std::string resolveFactorText(std::string factorText, const std::vector<std::vec
 // e = sum - piv * q0 (exact, one FMA), q = q0 + e * r -- the last three steps of the compiler's own f64 division
 // (which refines v_rcp_f64 first); with r correctly rounded the quotient is the correctly rounded one.
 // (tools/dev/ubench/div_markstein.hip compares it with the `/` operator.)
-LV emitQuotient(LGen& g, const LV& sum, const LV& piv, const LV& rinv)
+Sym emitQuotient(SymGen& g, const Sym& sum, const Sym& piv, const Sym& rinv)
 {
-    if (sum.zero()) return LV();
-    if (piv.kind == LV::CONST) {
+    if (sum.isZero()) return Sym();
+    if (piv.kind == Sym::CONST) {
         if (piv.c == 1.0) return sum;
         if (piv.c == -1.0) return g.negate(sum);
         return g.emit(g.ref(sum) + " / " + lit(piv.c));
     }
-    const std::string n = g.prefix + std::to_string(g.tmp++);
-    g.out << g.ind << "const double " << n << " = lin_quot(" << g.ref(sum) << ", " << g.ref(piv) << ", " << g.ref(rinv) << ");\n";
-    return LV::dyn(n);
+    return g.emit("lin_quot(" + g.ref(sum) + ", " + g.ref(piv) + ", " + g.ref(rinv) + ")");
+}
+
+// The substitution with the parked factors, shared by the transient kernel (once per step; x_raw to XRL) and the DC
+// kernel (once; x to xout): right-hand side from the I-gather list (term values termS), the forward elimination
+// replayed on it, back substitution.  Tape reads are numbered in the order of the solve's reads, and the factor
+// block stores every handle to all the positions that read it.
+struct LinearSolve {
+    std::string factor, solve;
+    int nTape = 0;
+};
+
+LinearSolve emitLinearSolve(const AssemblyPlan& ap, const LinearFactor& F, const std::vector<Sym>& termS, bool dc)
+{
+    const int N = static_cast<int>(F.piv.size());
+    SymGen gs(dc ? "    " : "            ", dc ? "vd" : "vs");
+    LazyMatrix b(gs, N, 1);
+    b.assemble(dc ? ap.dc : ap.tran, ap.LD, termS, false, true);
+    std::size_t op = 0;
+    for (int k = 0; k < N; ++k) {
+        const int p = F.swapWith[sz(k)];
+        if (p != k) b.swapRows(p, k);
+        if ((k % 4) == 0) gs.out << gs.ind << "__builtin_amdgcn_sched_barrier(0);\n";
+        for (; op < F.fwd.size() && F.fwd[op].k == k; ++op) {
+            const Sym bk = b.at(k, 0);
+            if (bk.isZero()) continue;
+            const Sym bi = b.at(F.fwd[op].i, 0);
+            b.cell(F.fwd[op].i, 0) = gs.fnma(bi, F.fwd[op].f, bk);
+        }
+    }
+    gs.out << gs.ind << "// back substitution (solver.hpp:116-128)" << (dc ? "" : "; x_raw goes to LDS") << "\n";
+    std::vector<Sym> xr(sz(N));
+    for (int i = N - 1; i >= 0; --i) {
+        if ((i % 4) == 0) gs.out << gs.ind << "__builtin_amdgcn_sched_barrier(0);\n";
+        Sym sum = b.at(i, 0);
+        for (int j = i + 1; j < N; ++j) {
+            const Sym& u = F.U[sz(i)][sz(j)];
+            if (u.isZero()) continue;
+            sum = gs.fnma(sum, u, xr[sz(j)]);
+        }
+        const Sym& pv = F.piv[sz(i)];
+        Sym x;
+        if (dc && sum.isZero()) {
+            // a structurally zero sum still goes through the division: +0 / U(i,i) is -0 for a negative pivot, and the
+            // operating point is an OUTPUT (the t = 0 row of the reference's CSV prints the sign)
+            x = gs.emit(pv.kind == Sym::CONST ? lit(0.0 / pv.c) : "0.0 / " + gs.ref(pv));
+        } else {
+            x = emitQuotient(gs, sum, pv, F.rinv[sz(i)]);
+            if (x.kind == Sym::DYN && (x.e.compare(0, gs.prefix.size(), gs.prefix) != 0 || x.neg)) x = gs.emit(gs.ref(x));    // a named value, read once below
+        }
+        if (dc) gs.out << gs.ind << "if (ok) xout[" << i << "LL * SB + b] = " << gs.ref(x) << ";\n";
+        else gs.out << gs.ind << "XRL(" << i << ") = " << gs.ref(x) << ";\n";
+        xr[sz(i)] = x;
+    }
+
+    LinearSolve ls;
+    std::vector<std::vector<int>> uses(sz(F.nHandles));
+    const std::string text = gs.out.str();
+    std::size_t i = 0;
+    while (i < text.size()) {
+        const std::size_t a = text.find("@L", i);
+        if (a == std::string::npos) { ls.solve += text.substr(i); break; }
+        uses[sz(std::atoi(text.c_str() + a + 2))].push_back(ls.nTape);
+        ls.solve += text.substr(i, a - i) + "TP(" + std::to_string(ls.nTape++) + ")";
+        i = text.find('@', a + 2) + 1;
+    }
+    ls.factor = resolveFactorText(F.text, uses);
+    return ls;
 }
 
 } // namespace
@@ -469,36 +334,31 @@ std::string emitLinearKernel(const csim_ir& ir, const AssemblyPlan& ap, const Pi
     int LPW = 64;
     while (LPW >= 8 && 2LL * N * 8 * LPW > 160 * 1024) LPW /= 2;
     if (LPW < 8) return std::string();
-    const GatherPlan& gpl = ap.tran;
     LinearFactor F;
     buildLinearFactor(ir, ap, sc, F);
-    const int nHandles = F.nHandles;
-    const std::vector<FwdOp>& fwd = F.fwd;
-    const std::vector<int>& swapWith = F.swapWith;
-    const std::vector<std::vector<LV>>& M = F.U;
     auto rd = rdHandle;
     // per-step terms: sources evaluated at tNow, history currents from the previous state (still in XL when the
     // substitution runs, at the start of the step)
-    std::vector<LV> termS(static_cast<std::size_t>(ap.nTerms));
+    std::vector<Sym> termS(sz(ap.nTerms));
     std::ostringstream stepCode;
-    termS[static_cast<std::size_t>(ap.termOne)] = LV::konst(1.0);
-    termS[static_cast<std::size_t>(ap.termGmin)] = LV::konst(K.tran_gmin);
+    termS[sz(ap.termOne)] = Sym::konst(1.0);
+    termS[sz(ap.termGmin)] = Sym::konst(K.tran_gmin);
     for (int e = 0; e < ir.n_elems; ++e) {
-        const int s = ir.param_slot[e], tb = ap.termBase[static_cast<std::size_t>(e)];
+        const int s = ir.param_slot[e], tb = ap.termBase[sz(e)];
         const int32_t* q = ir.eq + 4 * e;
         auto X = [&](int eq) { return eq >= 0 ? "XL(" + std::to_string(eq) + ")" : std::string("0.0"); };
-        const int h = F.coefHandle[static_cast<std::size_t>(e)];
+        const int h = F.coefHandle[sz(e)];
         switch (ir.kind[e]) {
             case CSIM_C: {
                 // history current -Gc * vPrev (tanalisis.cpp:77)
                 const std::string v = (q[0] >= 0 && q[1] >= 0) ? "(" + X(q[0]) + " - " + X(q[1]) + ")"
                                       : (q[0] >= 0 ? X(q[0]) : (q[1] >= 0 ? "(-" + X(q[1]) + ")" : std::string("0.0")));
-                termS[static_cast<std::size_t>(tb + T_C_IH)] = LV::dyn("(-" + rd(h) + " * " + v + ")");
+                termS[sz(tb + T_C_IH)] = Sym::dyn("(-" + rd(h) + " * " + v + ")");
                 break;
             }
             case CSIM_L: {
                 const int kb = ir.branch_eq[e];
-                termS[static_cast<std::size_t>(tb + T_L_VH)] = LV::dyn("(-" + rd(h) + " * " + X((kb >= 0 && kb < N) ? kb : -1) + ")");
+                termS[sz(tb + T_L_VH)] = Sym::dyn("(-" + rd(h) + " * " + X((kb >= 0 && kb < N) ? kb : -1) + ")");
                 break;
             }
             case CSIM_V: case CSIM_I: {
@@ -507,7 +367,7 @@ std::string emitLinearKernel(const csim_ir& ir, const AssemblyPlan& ap, const Pi
                 // parameters are re-read per step through an offset the compiler cannot fold (see codegen.cpp)
                 emitTranSourceValue(stepCode, "        ", ir, e,
                                     [&](int o) { return "params[" + std::to_string(s + o) + "LL * SB + bb + vo]"; }, name);
-                termS[static_cast<std::size_t>(tb + T_SRC_VAL)] = LV::dyn(name);
+                termS[sz(tb + T_SRC_VAL)] = Sym::dyn(name);
                 break;
             }
             default: break;
@@ -515,74 +375,9 @@ std::string emitLinearKernel(const csim_ir& ir, const AssemblyPlan& ap, const Pi
     }
 
     // ---- per-step block: right-hand side, forward elimination replayed, back substitution
-    LGen gs;
-    gs.ind = "            ";
-    gs.prefix = "vs";
-    std::vector<LV> rhs(static_cast<std::size_t>(N));
-    std::vector<std::vector<LV>> rpend(static_cast<std::size_t>(N));
-    for (int n = 0; n < gpl.nnzI(); ++n) {
-        std::vector<LV> terms;
-        for (int c = gpl.iPtr[static_cast<std::size_t>(n)]; c < gpl.iPtr[static_cast<std::size_t>(n + 1)]; ++c) {
-            const int con = gpl.iCon[static_cast<std::size_t>(c)];
-            LV t = termS[static_cast<std::size_t>(con >> 1)];
-            terms.push_back((con & 1) ? gs.negate(t) : t);
-        }
-        rpend[static_cast<std::size_t>(gpl.iRow[static_cast<std::size_t>(n)])] = terms;
-        rhs[static_cast<std::size_t>(gpl.iRow[static_cast<std::size_t>(n)])] = LV::dyn("?");
-    }
-    auto bAt = [&](int r) -> LV& {
-        if (!rpend[static_cast<std::size_t>(r)].empty()) { rhs[static_cast<std::size_t>(r)] = gs.orderedSum(rpend[static_cast<std::size_t>(r)]); rpend[static_cast<std::size_t>(r)].clear(); }
-        return rhs[static_cast<std::size_t>(r)];
-    };
-    {
-        std::size_t op = 0;
-        for (int k = 0; k < N; ++k) {
-            const int p = swapWith[static_cast<std::size_t>(k)];
-            if (p != k) { std::swap(rhs[static_cast<std::size_t>(p)], rhs[static_cast<std::size_t>(k)]); std::swap(rpend[static_cast<std::size_t>(p)], rpend[static_cast<std::size_t>(k)]); }
-            if ((k % 4) == 0) gs.out << gs.ind << "__builtin_amdgcn_sched_barrier(0);\n";
-            for (; op < fwd.size() && fwd[op].k == k; ++op) {
-                const LV bk = bAt(k);
-                if (bk.zero()) continue;
-                const LV bi = bAt(fwd[op].i);
-                rhs[static_cast<std::size_t>(fwd[op].i)] = gs.fnma(bi, fwd[op].f, bk);
-            }
-        }
-    }
-    gs.out << gs.ind << "// back substitution (solver.hpp:116-128); x_raw goes to LDS\n";
-    std::vector<LV> xr(static_cast<std::size_t>(N));
-    for (int i = N - 1; i >= 0; --i) {
-        if ((i % 4) == 0) gs.out << gs.ind << "__builtin_amdgcn_sched_barrier(0);\n";
-        LV sum = bAt(i);
-        for (int j = i + 1; j < N; ++j) {
-            const LV& u = M[static_cast<std::size_t>(i)][static_cast<std::size_t>(j)];
-            if (u.zero()) continue;
-            sum = gs.fnma(sum, u, xr[static_cast<std::size_t>(j)]);
-        }
-        LV x = emitQuotient(gs, sum, F.piv[static_cast<std::size_t>(i)], F.rinv[static_cast<std::size_t>(i)]);
-        if (x.kind == LV::DYN && (x.e.compare(0, 2, "vs") != 0 || x.neg)) x = gs.emit(gs.ref(x));    // a named value, read once below
-        gs.out << gs.ind << "XRL(" << i << ") = " << gs.ref(x) << ";\n";
-        xr[static_cast<std::size_t>(i)] = x;
-    }
-
-    // ---- number the tape in the order of the per-step block's reads
-    std::string stepText = gs.out.str();
-    std::vector<std::vector<int>> uses(static_cast<std::size_t>(nHandles));
-    int nTape = 0;
-    {
-        std::string outText;
-        std::size_t i = 0;
-        while (i < stepText.size()) {
-            const std::size_t a = stepText.find("@L", i);
-            if (a == std::string::npos) { outText += stepText.substr(i); break; }
-            const std::size_t b = stepText.find('@', a + 2);
-            const int h = std::atoi(stepText.substr(a + 2, b - a - 2).c_str());
-            outText += stepText.substr(i, a - i) + "TP(" + std::to_string(nTape) + ")";
-            uses[static_cast<std::size_t>(h)].push_back(nTape++);
-            i = b + 1;
-        }
-        stepText = outText;
-    }
-    const std::string factorText = resolveFactorText(F.text, uses);
+    const LinearSolve ls = emitLinearSolve(ap, F, termS, false);
+    std::string stepText = ls.solve;
+    int nTape = ls.nTape;
     // The step reads the tape strictly in order, one miss of ~700 cycles each if it waits for every entry
     // where it is used (measured: 454 us per step on the N = 257 ladder, 1539 sequential misses).  So the
     // entries are loaded into registers two chunks of 32 ahead of their use: loads of chunk c+2 are issued
@@ -600,25 +395,25 @@ std::string emitLinearKernel(const csim_ir& ir, const AssemblyPlan& ap, const Pi
             }
         }
         const int nChunks = (nTape + chunk - 1) / chunk;
-        std::vector<int> firstLine(static_cast<std::size_t>(nChunks), -1);
+        std::vector<int> firstLine(sz(nChunks), -1);
         for (std::size_t l = 0; l < lines.size(); ++l) {
             std::size_t at = 0;
             while ((at = lines[l].find("TP(", at)) != std::string::npos) {
                 const int n = std::atoi(lines[l].c_str() + at + 3);
-                if (firstLine[static_cast<std::size_t>(n / chunk)] < 0) firstLine[static_cast<std::size_t>(n / chunk)] = static_cast<int>(l);
+                if (firstLine[sz(n / chunk)] < 0) firstLine[sz(n / chunk)] = static_cast<int>(l);
                 at += 3;
             }
         }
         auto loadsOf = [&](int c) {
             std::string t;
             for (int n = c * chunk; n < std::min(nTape, (c + 1) * chunk); ++n)
-                t += gs.ind + "const double tq" + std::to_string(n) + " = TP(" + std::to_string(n) + ");\n";
+                t += "            const double tq" + std::to_string(n) + " = TP(" + std::to_string(n) + ");\n";
             return t;
         };
         std::string outText = loadsOf(0) + (nChunks > 1 ? loadsOf(1) : std::string());
         for (std::size_t l = 0; l < lines.size(); ++l) {
             for (int c = 0; c + 2 < nChunks; ++c)
-                if (firstLine[static_cast<std::size_t>(c)] == static_cast<int>(l)) outText += loadsOf(c + 2);
+                if (firstLine[sz(c)] == static_cast<int>(l)) outText += loadsOf(c + 2);
             std::string ln = lines[l];
             std::size_t at = 0;
             while ((at = ln.find("TP(", at)) != std::string::npos) {
@@ -667,7 +462,7 @@ std::string emitLinearKernel(const csim_ir& ir, const AssemblyPlan& ap, const Pi
       << "    {\n        const double* xin = xio + bb;\n#pragma unroll 1\n"
       << "        for (int i = 0; i < " << N << "; ++i, xin += SB) XL(i) = *xin;\n    }\n"
       << "    // launch constants (tanalisis.cpp:65-67,296) and the factors -> the tape\n"
-      << factorText
+      << ls.factor
       << "    viol = viol || pvF != 0;\n"
       << "    unsigned st = inb ? status[bb] : 0u;\n"
       << "    bool dead = !inb || (st & ST_TRAN_NONFINITE) != 0u;\n"
@@ -760,97 +555,22 @@ std::string emitLinearDcKernel(const csim_ir& ir, const AssemblyPlan& ap, const 
 {
     const int N = ir.n_unknowns;
     if (ir.has_nonlinear || N <= 0) return std::string();
-    const GatherPlan& gpl = ap.dc;
     LinearFactor F;
     buildLinearFactor(ir, ap, sc, F, true);
     // right-hand side: source values at DC, SourceSpec::evalDC(1.0) = (dc + (SIN ? v0 : 0)) * 1.0 (include/sim.hpp:152-158)
-    std::vector<LV> termS(static_cast<std::size_t>(ap.nTerms));
-    termS[static_cast<std::size_t>(ap.termOne)] = LV::konst(1.0);
+    std::vector<Sym> termS(sz(ap.nTerms));
+    termS[sz(ap.termOne)] = Sym::konst(1.0);
     std::ostringstream srcCode;
     for (int e = 0; e < ir.n_elems; ++e) {
         if (ir.kind[e] != CSIM_V && ir.kind[e] != CSIM_I) continue;
-        const int s = ir.param_slot[e], tb = ap.termBase[static_cast<std::size_t>(e)];
+        const int s = ir.param_slot[e], tb = ap.termBase[sz(e)];
         const std::string name = "sv" + std::to_string(e);
         auto PX = [&](int o) { return "params[" + std::to_string(s + o) + "LL * SB + bb]"; };
         srcCode << "    const double " << name << " = " << (ir.wave[e] == CSIM_WAVE_SIN ? "(" + PX(0) + " + " + PX(1) + ") * 1.0" : PX(0) + " * 1.0") << ";\n";
-        termS[static_cast<std::size_t>(tb + T_SRC_VAL)] = LV::dyn(name);
+        termS[sz(tb + T_SRC_VAL)] = Sym::dyn(name);
     }
-    LGen gs;
-    gs.ind = "    ";
-    gs.prefix = "vd";
-    std::vector<LV> rhs(static_cast<std::size_t>(N));
-    std::vector<std::vector<LV>> rpend(static_cast<std::size_t>(N));
-    for (int n = 0; n < gpl.nnzI(); ++n) {
-        std::vector<LV> terms;
-        for (int c = gpl.iPtr[static_cast<std::size_t>(n)]; c < gpl.iPtr[static_cast<std::size_t>(n + 1)]; ++c) {
-            const int con = gpl.iCon[static_cast<std::size_t>(c)];
-            LV t = termS[static_cast<std::size_t>(con >> 1)];
-            terms.push_back((con & 1) ? gs.negate(t) : t);
-        }
-        rpend[static_cast<std::size_t>(gpl.iRow[static_cast<std::size_t>(n)])] = terms;
-        rhs[static_cast<std::size_t>(gpl.iRow[static_cast<std::size_t>(n)])] = LV::dyn("?");
-    }
-    auto bAt = [&](int r) -> LV& {
-        if (!rpend[static_cast<std::size_t>(r)].empty()) { rhs[static_cast<std::size_t>(r)] = gs.orderedSum(rpend[static_cast<std::size_t>(r)]); rpend[static_cast<std::size_t>(r)].clear(); }
-        if (rhs[static_cast<std::size_t>(r)].kind == LV::DYN && rhs[static_cast<std::size_t>(r)].e == "?") rhs[static_cast<std::size_t>(r)] = LV();
-        return rhs[static_cast<std::size_t>(r)];
-    };
-    {
-        std::size_t op = 0;
-        for (int k = 0; k < N; ++k) {
-            const int p = F.swapWith[static_cast<std::size_t>(k)];
-            if (p != k) { std::swap(rhs[static_cast<std::size_t>(p)], rhs[static_cast<std::size_t>(k)]); std::swap(rpend[static_cast<std::size_t>(p)], rpend[static_cast<std::size_t>(k)]); }
-            if ((k % 4) == 0) gs.out << gs.ind << "__builtin_amdgcn_sched_barrier(0);\n";
-            for (; op < F.fwd.size() && F.fwd[op].k == k; ++op) {
-                const LV bk = bAt(k);
-                if (bk.zero()) continue;
-                const LV bi = bAt(F.fwd[op].i);
-                rhs[static_cast<std::size_t>(F.fwd[op].i)] = gs.fnma(bi, F.fwd[op].f, bk);
-            }
-        }
-    }
-    gs.out << gs.ind << "// back substitution (solver.hpp:116-128)\n";
-    std::vector<LV> xr(static_cast<std::size_t>(N));
-    for (int i = N - 1; i >= 0; --i) {
-        if ((i % 4) == 0) gs.out << gs.ind << "__builtin_amdgcn_sched_barrier(0);\n";
-        LV sum = bAt(i);
-        for (int j = i + 1; j < N; ++j) {
-            const LV& u = F.U[static_cast<std::size_t>(i)][static_cast<std::size_t>(j)];
-            if (u.zero()) continue;
-            sum = gs.fnma(sum, u, xr[static_cast<std::size_t>(j)]);
-        }
-        LV x;
-        if (sum.zero()) {
-            // a structurally zero sum still goes through the division: +0 / U(i,i) is -0 for a negative pivot, and the
-            // operating point is an OUTPUT (the t = 0 row of the reference's CSV prints the sign)
-            const LV& pv = F.piv[static_cast<std::size_t>(i)];
-            x = gs.emit(pv.kind == LV::CONST ? lit(0.0 / pv.c) : "0.0 / " + gs.ref(pv));
-        } else {
-            x = emitQuotient(gs, sum, F.piv[static_cast<std::size_t>(i)], F.rinv[static_cast<std::size_t>(i)]);
-            if (x.kind == LV::DYN && (x.e.compare(0, 2, "vd") != 0 || x.neg)) x = gs.emit(gs.ref(x));
-        }
-        gs.out << gs.ind << "if (ok) xout[" << i << "LL * SB + b] = " << gs.ref(x) << ";\n";
-        xr[static_cast<std::size_t>(i)] = x;
-    }
-    // tape positions in the order of the solve's reads
-    std::string solveText = gs.out.str();
-    std::vector<std::vector<int>> uses(static_cast<std::size_t>(F.nHandles));
-    int nTape = 0;
-    {
-        std::string outText;
-        std::size_t i = 0;
-        while (i < solveText.size()) {
-            const std::size_t a = solveText.find("@L", i);
-            if (a == std::string::npos) { outText += solveText.substr(i); break; }
-            const std::size_t b = solveText.find('@', a + 2);
-            const int h = std::atoi(solveText.substr(a + 2, b - a - 2).c_str());
-            outText += solveText.substr(i, a - i) + "TP(" + std::to_string(nTape) + ")";
-            uses[static_cast<std::size_t>(h)].push_back(nTape++);
-            i = b + 1;
-        }
-        solveText = outText;
-    }
-    if (nTape == 0) nTape = 1;
+    const LinearSolve ls = emitLinearSolve(ap, F, termS, true);
+    const int nTape = std::max(ls.nTape, 1);
     std::ostringstream o;
     o << "// ---- linear circuit: DC operating point, one direct solve (codegen_linear.cpp emitLinearDcKernel)\n"
       << linearPrelude()
@@ -875,11 +595,11 @@ std::string emitLinearDcKernel(const csim_ir& ir, const AssemblyPlan& ap, const 
       << "#define TP(n) tapeR[(long long)(n) * SBW]\n"
       << "    bool viol = false;\n"
       << "    (void)dt;\n"
-      << resolveFactorText(F.text, uses)
+      << ls.factor
       << "    viol = viol || pvF != 0;\n"
       << "    const bool ok = inb && !viol;\n"
       << srcCode.str()
-      << solveText
+      << ls.solve
       << "    if (inb) {\n"
       << "        if (viol) { fallback[b] = 1; violFlag[0] = 1; }     // the general kernel solves this instance\n"
       << "        else { iters[b] = 1; status[b] = 0u; }\n"
@@ -923,7 +643,6 @@ std::string emitLinearGroupKernel(const csim_ir& ir, const AssemblyPlan& ap, con
     const GatherPlan& gpl = ap.tran;
     LinearFactor F;
     buildLinearFactor(ir, ap, sc, F);
-    auto sz = [](int v) { return static_cast<std::size_t>(v); };
 
     // ---- where rows end up: final pivot positions (the right-hand side is assembled there directly)
     std::vector<int> cur(sz(N));
@@ -972,7 +691,7 @@ std::string emitLinearGroupKernel(const csim_ir& ir, const AssemblyPlan& ap, con
     // ---- the tape: every parked value goes to the lane that consumes it, in that lane's order of use
     std::vector<int> cnt(sz(G), 0);
     std::vector<std::vector<int>> uses(sz(F.nHandles));
-    auto take = [&](const LV& v, int lane) -> std::string {
+    auto take = [&](const Sym& v, int lane) -> std::string {
         const int h = handleOf(v);
         const int r = cnt[sz(lane)]++;
         uses[sz(h)].push_back(r * G + lane);
@@ -985,7 +704,7 @@ std::string emitLinearGroupKernel(const csim_ir& ir, const AssemblyPlan& ap, con
     for (std::size_t n = 0; n < hist.size(); ++n) {
         const int lane = static_cast<int>(n) % G, r = static_cast<int>(n) / G;
         if (cnt[sz(lane)] != r || hist[n].coefH < 0) return std::string();     // cannot happen: rounds are handed out in order
-        (void)take(LV::dyn(rdHandle(hist[n].coefH)), lane);
+        (void)take(Sym::dyn(rdHandle(hist[n].coefH)), lane);
         hA[n] = hist[n].a; hB[n] = hist[n].b; hOut[n] = hist[n].out;
     }
     for (int g = 0; g < G; ++g) cnt[sz(g)] = std::max(cnt[sz(g)], histRounds);     // ordinals < histRounds belong to the rounds
@@ -1006,10 +725,10 @@ std::string emitLinearGroupKernel(const csim_ir& ir, const AssemblyPlan& ap, con
         std::string srcName;
         for (std::size_t op = 0; op < F.fwd.size(); ++op) {
             const int k = F.fwd[op].k, P = fpos[sz(opOrig[op])];
-            const LV& f = F.fwd[op].f;
-            if (bzero[sz(k)] || f.zero()) continue;                    // b_k is a structural zero: b_P - f * 0 == b_P
+            const Sym& f = F.fwd[op].f;
+            if (bzero[sz(k)] || f.isZero()) continue;                    // b_k is a structural zero: b_P - f * 0 == b_P
             std::string t;
-            if (f.kind == LV::DYN && cnt[sz(k % G)] < cnt[sz(P % G)]) {
+            if (f.kind == Sym::DYN && cnt[sz(k % G)] < cnt[sz(P % G)]) {
                 // The multiplier may sit in the TARGET row's lane (b_k is broadcast, shared by the column's operations) or
                 // in the SOURCE row's lane (the product is formed there and broadcast): whichever lane holds fewer
                 // operands so far -- a row that receives from many columns (the ladder's border row: 256 of them) would
@@ -1030,10 +749,10 @@ std::string emitLinearGroupKernel(const csim_ir& ir, const AssemblyPlan& ap, con
                 lastSrc = k;
                 ++nChainInstr;
             }
-            if (f.kind == LV::CONST && std::fabs(f.c) == 1.0) t = (f.c < 0 ? "(-" + srcName + ")" : srcName);
+            if (f.kind == Sym::CONST && std::fabs(f.c) == 1.0) t = (f.c < 0 ? "(-" + srcName + ")" : srcName);
             else {
                 t = "ft" + std::to_string(tmp++);
-                ch << in << "const double " << t << " = " << (f.kind == LV::CONST ? lit(f.c) : take(f, P % G)) << " * " << srcName << ";\n";
+                ch << in << "const double " << t << " = " << (f.kind == Sym::CONST ? lit(f.c) : take(f, P % G)) << " * " << srcName << ";\n";
                 ++nChainInstr;
             }
             ch << in << W(P) << " = fma(-" << t << ", " << MK(P) << ", " << W(P) << ");\n";
@@ -1053,9 +772,9 @@ std::string emitLinearGroupKernel(const csim_ir& ir, const AssemblyPlan& ap, con
             int lastJ = -1;
             std::string xb;
             for (int j = i + 1; j < N; ++j) {
-                const LV& u = F.U[sz(i)][sz(j)];
-                if (u.zero() || xzero[sz(j)]) continue;
-                if (u.kind == LV::DYN && cnt[sz(j % G)] < cnt[sz(i % G)]) {       // operand in the lane of x_j: see the forward pass
+                const Sym& u = F.U[sz(i)][sz(j)];
+                if (u.isZero() || xzero[sz(j)]) continue;
+                if (u.kind == Sym::DYN && cnt[sz(j % G)] < cnt[sz(i % G)]) {       // operand in the lane of x_j: see the forward pass
                     const std::string pt = "up" + std::to_string(tmp++), t = "ut" + std::to_string(tmp++);
                     ch << in << "const double " << pt << " = " << take(u, j % G) << " * " << xq[sz(j)] << ";\n"
                        << in << "const double " << t << " = grp_bc<" << j % G << ">(" << pt << ");\n"
@@ -1071,10 +790,10 @@ std::string emitLinearGroupKernel(const csim_ir& ir, const AssemblyPlan& ap, con
                     ++nChainInstr;
                 }
                 std::string t;
-                if (u.kind == LV::CONST && std::fabs(u.c) == 1.0) t = (u.c < 0 ? "(-" + xb + ")" : xb);
+                if (u.kind == Sym::CONST && std::fabs(u.c) == 1.0) t = (u.c < 0 ? "(-" + xb + ")" : xb);
                 else {
                     t = "ut" + std::to_string(tmp++);
-                    ch << in << "const double " << t << " = " << (u.kind == LV::CONST ? lit(u.c) : take(u, i % G)) << " * " << xb << ";\n";
+                    ch << in << "const double " << t << " = " << (u.kind == Sym::CONST ? lit(u.c) : take(u, i % G)) << " * " << xb << ";\n";
                     ++nChainInstr;
                 }
                 ch << in << W(i) << " = fma(-" << t << ", " << MK(i) << ", " << W(i) << ");\n";
@@ -1107,22 +826,14 @@ std::string emitLinearGroupKernel(const csim_ir& ir, const AssemblyPlan& ap, con
     for (int p = 0; p < NP; ++p) {
         const int ip = (Tmax + 2 * (p / G)) * G + p % G, ir_ = ip + G;
         if (p >= N) { constFill.push_back({ip, 1.0}); constFill.push_back({ir_, 1.0}); continue; }
-        const LV& pv = F.piv[sz(p)];
-        if (pv.kind == LV::CONST) { constFill.push_back({ip, pv.c}); constFill.push_back({ir_, 1.0 / pv.c}); continue; }
+        const Sym& pv = F.piv[sz(p)];
+        if (pv.kind == Sym::CONST) { constFill.push_back({ip, pv.c}); constFill.push_back({ir_, 1.0 / pv.c}); continue; }
         if (handleOf(pv) < 0 || handleOf(F.rinv[sz(p)]) < 0) return std::string();      // cannot happen: a run-time pivot is parked
         uses[sz(handleOf(pv))].push_back(ip);
         uses[sz(handleOf(F.rinv[sz(p)]))].push_back(ir_);
     }
 
     // ---- tables
-    auto intArray = [](const std::string& name, const std::vector<int32_t>& v) {
-        std::ostringstream t;
-        t << "static __device__ const int " << name << "[" << (v.empty() ? 1 : v.size()) << "] = {";
-        if (v.empty()) t << "0";
-        for (std::size_t i = 0; i < v.size(); ++i) t << (i ? "," : "") << ((i % 32 == 31) ? "\n    " : "") << v[i];
-        t << "};\n";
-        return t.str();
-    };
     std::vector<int32_t> srcTab(srcElems.begin(), srcElems.end());
     const int srcRounds = (static_cast<int>(srcTab.size()) + G - 1) / G;
     srcTab.resize(sz(std::max(1, srcRounds) * G), -1);

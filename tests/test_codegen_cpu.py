@@ -184,3 +184,22 @@ def test_generated_source_changes_only_with_a_new_generator_revision(codegen):
             "the generator's output changed but kGeneratorRevision (codegen.hpp) did not: bump it"
         pytest.fail("generator output and revision changed: record them with tools/update_generated_golden.py")
     assert upd.revision() == golden["generator_revision"], "revision bumped without a change of the emitted code: re-record"
+
+
+def test_every_kernel_family_changes_only_with_a_new_generator_revision(codegen):
+    """As above, for the rest of the generator's output: the golden record's family_md5 holds the md5 for further
+    generator option sets and for circuits that reach every other kernel family -- the gate-only-node and PULSE / PWL
+    circuits, and linear circuits with a DC schedule (sixteen-lane and lane-per-instance linear kernels, linear DC)."""
+    import importlib.util
+    import json
+    from conftest import ROOT
+    spec = importlib.util.spec_from_file_location("upd", os.path.join(ROOT, "tools", "update_generated_golden.py"))
+    upd = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(upd)
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "generated_source.json")))
+    now = upd.family_digests()
+    if now != golden["family_md5"]:
+        assert upd.revision() != golden["generator_revision"], \
+            "the generator's output changed but kGeneratorRevision (codegen.hpp) did not: bump it"
+        pytest.fail("generator output and revision changed: record them with tools/update_generated_golden.py")
+    assert upd.revision() == golden["generator_revision"], "revision bumped without a change of the emitted code: re-record"

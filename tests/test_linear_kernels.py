@@ -8,7 +8,7 @@ import shutil
 import numpy as np
 import pytest
 
-from conftest import rel_err
+from conftest import netlist_path, rel_err
 from test_gpu_parity import NOFB, TOL, _orc, _run_tran
 
 pytestmark = pytest.mark.gpu
@@ -36,12 +36,7 @@ CIRCUITS = {
     # the configs[3] ladder at a quarter of its length: tridiagonal + the source's border row (pivoted first)
     "ladder64": lambda: __import__("circuitsimulator_amd.workloads", fromlist=["x"]).rc_ladder_netlist(64),
     # inductors (branch rows, exact +-1 incidence), a current source, PULSE and PWL waveforms, a floating-ish mesh
-    "rlc_mesh": lambda: (
-        "V1 a 0 PULSE(0 1 2e-9 1e-9 1e-9 5e-9 20e-9)\n"
-        "I1 0 c PWL(0 0 5e-9 1e-3 30e-9 -1e-3)\n"
-        "R1 a b 50\nL1 b c 2e-9\nC1 c 0 1e-12\nR2 c d 75\nL2 d e 5e-9\nC2 e 0 2e-12\nR3 e 0 1e3\n"
-        "R4 b e 220\nC3 b d 0.5e-12\nV2 f 0 SIN 0.5 0.25 2e8 0\nR5 f d 330\n"
-        ".TRAN 1e-10 8e-9\n"),
+    "rlc_mesh": lambda: open(netlist_path("rlc_mesh.sp")).read(),
 }
 
 
