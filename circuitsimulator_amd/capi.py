@@ -55,6 +55,13 @@ PROTOTYPES = {
     "csim_netlist_dc_sweep_params": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "csim_netlist_csv_header": (C.c_int, [_vp, _cp, _i32]),
     "csim_netlist_mc_kinds": (C.c_int, [_vp, _vp]),
+    "csim_netlist_ac": (C.c_int, [_vp, _pi32, _pi32, _pi32, _pdbl, _pdbl]),
+    "csim_netlist_ac_source": (C.c_int, [_vp, _i32, _pdbl, _pdbl]),
+    "csim_ac_num_freqs": (_i64, [_i32, _i32, _dbl, _dbl]),
+    "csim_ac_freqs": (C.c_int, [_i32, _i32, _dbl, _dbl, _vp]),
+    "csim_ac_batch_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "csim_ac_batch": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp]),
+    "csim_ac_system_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
     "csim_engine_create": (C.c_int, [_vp, _i32, C.POINTER(_vp)]),
     "csim_engine_destroy": (None, [_vp]),
     "csim_engine_tran_kernel": (_cp, [_vp]),

@@ -68,6 +68,22 @@ BatchDcResult BatchEngine::dc(const std::vector<double>& params, int B)
     return r;
 }
 
+BatchAcResult BatchEngine::ac(const std::vector<double>& params, int B, const std::vector<double>& freqs,
+                              const std::vector<int32_t>& probeEq)
+{
+    BatchAcResult r;
+    r.freqs = freqs;
+    r.nProbe = probeEq.empty() ? numUnknowns() : static_cast<int>(probeEq.size());
+    const int F = static_cast<int>(freqs.size());
+    r.v.assign(static_cast<std::size_t>(B) * F * r.nProbe, std::complex<double>());
+    r.status.assign(static_cast<std::size_t>(B), 0);
+    if (csim_ac_batch(eng_, params.empty() ? nullptr : params.data(), B, freqs.data(), F,
+                      probeEq.empty() ? nullptr : probeEq.data(), r.nProbe, reinterpret_cast<double*>(r.v.data()),
+                      r.status.data()) != CSIM_OK)
+        fail("csim_ac_batch");
+    return r;
+}
+
 BatchTranResult BatchEngine::tran(const std::vector<double>& params, int B, double tstep, double tstop,
                                   double tstart, const std::vector<int32_t>& probeEq, int outStride)
 {

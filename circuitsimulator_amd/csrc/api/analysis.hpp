@@ -12,6 +12,8 @@
 #include <string>
 #include <vector>
 
+#include <complex>
+
 #include "circuit.hpp"
 #include "csim.h"
 #include "sim.hpp"
@@ -30,6 +32,13 @@ struct BatchTranResult {
     std::vector<double> xFinal;       // [B][N]
     std::vector<int64_t> iters;
     std::vector<uint32_t> status;
+};
+
+struct BatchAcResult {
+    std::vector<double> freqs;                    // [F] Hz
+    int nProbe = 0;
+    std::vector<std::complex<double>> v;          // [B][F][n_probe]
+    std::vector<uint32_t> status;                 // DC and AC bits (CSIM_ST_LU_TINY_PIVOT: a singular frequency)
 };
 
 // One engine per (circuit, GPU).  Throws std::runtime_error when no HIP
@@ -54,6 +63,10 @@ public:
     BatchDcResult dc(const std::vector<double>& params, int B);
     BatchTranResult tran(const std::vector<double>& params, int B, double tstep, double tstop, double tstart,
                          const std::vector<int32_t>& probeEq, int outStride);
+    // AC small-signal sweep (csim_ac_batch, include/csim.h): DC operating point, then (G + jwC) v = J at every
+    // frequency of freqs (Hz); probeEq empty = every unknown.
+    BatchAcResult ac(const std::vector<double>& params, int B, const std::vector<double>& freqs,
+                     const std::vector<int32_t>& probeEq = {});
 
     // the transient of instance `instance` of params ([B][P], empty = nominal) as the reference's CSV
     // (src/tanalisis.cpp:189-231); probeEq empty: the netlist's .PLOTNV/.PRINT probes when `sim` names any, else

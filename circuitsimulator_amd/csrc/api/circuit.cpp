@@ -242,6 +242,11 @@ CircuitIR flatten(const Circuit& ckt)
         out.wave.push_back(r.wave);
         out.waveN.push_back(r.waveN);
         out.paramSlot.push_back(static_cast<int32_t>(out.nominal.size()));
+        const SourceSpec* src = nullptr;
+        if (const auto* v = dynamic_cast<const VoltageSource*>(e.get())) src = &v->getSpec();
+        else if (const auto* i = dynamic_cast<const CurrentSource*>(e.get())) src = &i->getSpec();
+        out.acMag.push_back(src ? src->acMag : 0.0);
+        out.acPhaseDeg.push_back(src ? src->acPhaseDeg : 0.0);
         if (r.branchEq >= 0 && r.branchEq < nNode + nBranch)
             out.eqNames[static_cast<std::size_t>(r.branchEq)] = e->getName();
         const bool mos = (r.kind == CSIM_NMOS || r.kind == CSIM_PMOS);

@@ -80,6 +80,10 @@ struct CircuitIR {
     //   mcAux[p] : for kind 2 the product COX*(W/L) pieces: see mcMu/mcCox/mcWL
     std::vector<int32_t> mcKind;
     std::vector<double> mcMu, mcCox, mcW, mcL;
+    // AC small-signal excitation per element (`AC mag [phase]` on a V/I source line; 0 elsewhere).
+    // Not part of the parameter vector: AC analysis does not perturb it, and P stays that of the
+    // netlist without AC tokens.
+    std::vector<double> acMag, acPhaseDeg;
     // names for output headers: node name per node equation, element name per
     // branch equation
     std::vector<std::string> eqNames;

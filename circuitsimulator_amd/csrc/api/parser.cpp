@@ -229,10 +229,41 @@ bool parsePulseOrPwl(const std::vector<std::string>& t, std::size_t next, int li
     }
     return true;
 }
+// `AC mag [phase_deg]`: the small-signal excitation of a source (SourceSpec::acMag / acPhaseDeg,
+// include/sim.hpp:146-149, stamped by VoltageSource/CurrentSource::stampAC, src/element.cpp:68-81,125-151).
+// The reference's parser has no syntax for it either; accepted as a superset after the DC value or in its
+// place, before an optional SIN / PULSE / PWL waveform.  `next` moves past the tokens consumed; false (with a
+// message) when the numbers do not parse.
+bool isWaveKeyword(const std::string& token)
+{
+    return toLower(token) == "sin" || toLower(token) == "dc" || startsWithKeyword(token, "pulse") ||
+           startsWithKeyword(token, "pwl") || startsWithKeyword(token, "sin");
+}
+
+bool parseAcSpec(const std::vector<std::string>& t, std::size_t& next, int lineNo, const std::string& raw, SourceSpec& spec)
+{
+    if (next >= t.size() || toLower(t[next]) != "ac") return true;
+    if (next + 1 >= t.size()) {
+        std::cerr << "Line " << lineNo << ": AC needs a magnitude: " << raw << "\n";
+        return false;
+    }
+    try {
+        spec.acMag = parseSpiceNumber(t[next + 1]);
+        next += 2;
+        if (next < t.size() && !isWaveKeyword(t[next])) {
+            spec.acPhaseDeg = parseSpiceNumber(t[next]);
+            next += 1;
+        }
+    } catch (const std::exception& e) {
+        std::cerr << "Line " << lineNo << ": cannot parse AC parameters: " << e.what() << " in '" << raw << "'\n";
+        return false;
+    }
+    return true;
+}
 } // namespace
 
-// Vname np nm <value> [SIN ...] | Vname np nm DC <value> [SIN ...] |
-// Vname np nm SIN v0 va freq [td [phi]]
+// Vname np nm <value> [AC mag [phase]] [SIN ...] | Vname np nm DC <value> [AC ...] [SIN ...] |
+// Vname np nm [AC mag [phase]] SIN v0 va freq [td [phi]]
 void NetlistParser::voltageSource(const Statement& st)
 {
     const auto& t = st.tokens;
@@ -247,7 +278,7 @@ void NetlistParser::voltageSource(const Statement& st)
         if (t.size() >= 5 && toLower(t[3]) == "dc") {
             spec.dcValue = parseSpiceNumber(t[4]);
             next = 5;
-        } else if (toLower(t[3]) == "sin" || startsWithKeyword(t[3], "pulse") || startsWithKeyword(t[3], "pwl")) {
+        } else if (toLower(t[3]) == "ac" || toLower(t[3]) == "sin" || startsWithKeyword(t[3], "pulse") || startsWithKeyword(t[3], "pwl")) {
             spec.dcValue = 0.0;
             next = 3;
         } else {
@@ -259,6 +290,7 @@ void NetlistParser::voltageSource(const Statement& st)
                   << " in '" << st.raw << "'\n";
         return;
     }
+    if (!parseAcSpec(t, next, st.lineNo, st.raw, spec)) return;
 
     if (parsePulseOrPwl(t, next, st.lineNo, st.raw, spec)) {
         // superset of the reference dialect, see above
@@ -286,7 +318,8 @@ void NetlistParser::voltageSource(const Statement& st)
     ckt.addVoltageSource(t[0], t[1], t[2], spec);
 }
 
-// Iname np nm [DC] value        (+ optional PULSE / PWL waveform: superset, see above)
+// Iname np nm [DC] value [AC mag [phase]]   (+ optional PULSE / PWL waveform: superset, see above)
+// Iname np nm AC mag [phase]                 (no DC value: 0)
 void NetlistParser::currentSource(const Statement& st)
 {
     const auto& t = st.tokens;
@@ -300,8 +333,13 @@ void NetlistParser::currentSource(const Statement& st)
         if (startsWithKeyword(t[3], "pulse") || startsWithKeyword(t[3], "pwl")) {
             parsePulseOrPwl(t, 3, st.lineNo, st.raw, spec);
         } else {
-            spec.dcValue = parseSpiceNumber(dcForm ? t[4] : t[3]);
-            parsePulseOrPwl(t, dcForm ? 5 : 4, st.lineNo, st.raw, spec);
+            std::size_t next = 3;
+            if (toLower(t[3]) != "ac") {
+                spec.dcValue = parseSpiceNumber(dcForm ? t[4] : t[3]);
+                next = dcForm ? 5 : 4;
+            }
+            if (!parseAcSpec(t, next, st.lineNo, st.raw, spec)) return;
+            parsePulseOrPwl(t, next, st.lineNo, st.raw, spec);
         }
     } catch (const std::exception& e) {
         std::cerr << "Line " << st.lineNo << ": cannot parse I value: " << e.what()

@@ -277,6 +277,25 @@ int csim_engine_create(const csim_netlist* nl, int32_t device, csim_engine** out
     if (!rc) rc = upload(eng, c.mcCox, &eng->dCox);
     if (!rc) rc = upload(eng, c.mcW, &eng->dW);
     if (!rc) rc = upload(eng, c.mcL, &eng->dL);
+    if (!rc) {
+        // AC excitation mag * (cos, sin)(deg * pi / 180), as VoltageSource/CurrentSource::stampAC (element.cpp:68-81,125-151)
+        const double pi = ir->k.pi;
+        std::vector<double> re(c.acMag.size()), im(c.acMag.size());
+        for (std::size_t e = 0; e < c.acMag.size(); ++e) {
+            const double phi = c.acPhaseDeg[e] * pi / 180.0;
+            re[e] = c.acMag[e] * std::cos(phi);
+            im[e] = c.acMag[e] * std::sin(phi);
+            eng->acAnySource = eng->acAnySource || c.acMag[e] != 0.0;
+        }
+        rc = upload(eng, re, &eng->dAcRe);
+        if (!rc) rc = upload(eng, im, &eng->dAcIm);
+        const AcConfig& a = nl->sim.ac;
+        eng->acEnabled = a.enabled ? 1 : 0;
+        eng->acSweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
+        eng->acPoints = a.nPoints;
+        eng->acFstart = a.fstart;
+        eng->acFstop = a.fstop;
+    }
     if (!rc) rc = fillGenPlan(eng, eng->plan.dc, eng->gpDc);
     if (!rc) rc = fillGenPlan(eng, eng->plan.tran, eng->gpTran);
     if (rc) { csim_engine_destroy(eng); return rc; }
@@ -301,6 +320,9 @@ void csim_engine_destroy(csim_engine* eng)
     if (eng->hViolFlag) (void)hipHostFree(eng->hViolFlag);
     if (eng->dKnownAlts) (void)hipFree(eng->dKnownAlts);
     if (eng->dBigScratch) (void)hipFree(eng->dBigScratch);
+    if (eng->dAcOmega) (void)hipFree(eng->dAcOmega);
+    if (eng->dAcProbe) (void)hipFree(eng->dAcProbe);
+    if (eng->dAcSys) (void)hipFree(eng->dAcSys);
     if (eng->schedLib) dlclose(eng->schedLib);
     delete eng;
 }
@@ -363,6 +385,12 @@ int csim_engine_set_option(csim_engine* eng, const char* key, const char* value)
     else if (k == "near_test_rollback") c.nearTestRollback = iv != 0;
     else if (k == "hybrid_sync") c.hybridSync = iv != 0;
     else if (k == "dc_fast") c.dcFast = iv != 0;
+    else if (k == "ac_kernel") {
+        if (v == "auto") c.acKernel = csim::AC_KERNEL_AUTO;
+        else if (v == "wave") c.acKernel = csim::AC_KERNEL_WAVE;
+        else if (v == "packed") c.acKernel = csim::AC_KERNEL_PACKED;
+        else { setError("ac_kernel must be auto, wave or packed"); return CSIM_ERR_ARG; }
+    }
     else { setError("csim_engine_set_option: unknown option '" + k + "'"); return CSIM_ERR_ARG; }
     return CSIM_OK;
 }
@@ -754,6 +782,151 @@ int csim_dc_batch(csim_engine* eng, const double* params, int32_t B, double* x_o
     if (x_out)    HIPCHK(hipMemcpy(x_out, dXt.p, sizeof(double) * (size_t)N * B, hipMemcpyDeviceToHost));
     if (nr_iters) HIPCHK(hipMemcpy(nr_iters, dIt.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost));
     if (status)   HIPCHK(hipMemcpy(status, dSt.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    return CSIM_OK;
+}
+
+// ---- AC small-signal analysis ----------------------------------------------
+
+// the system of every instance lives in device scratch between assembly and sweep; instances are processed in
+// chunks that keep it below 256 MiB
+static int acChunk(const csim_engine* eng, int B)
+{
+    const size_t per = sizeof(double) * csim::acSystemDoubles(eng->plan.N);
+    const size_t cap = std::max<size_t>(256, ((size_t)256 << 20) / per);
+    return (int)std::min<size_t>((size_t)B, cap);
+}
+
+static int acCheck(const csim_engine* eng)
+{
+    if (eng->plan.N > 63) { setError("AC analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
+    if (!eng->acAnySource) { setError("AC analysis: no source carries an AC magnitude (V/I ... AC mag [phase])"); return CSIM_ERR_CONFIG; }
+    return CSIM_OK;
+}
+
+int csim_ac_system_dev(csim_engine* eng, const double* d_params, int32_t B, const double* d_xop, double* d_sys, void* stream)
+{
+    if (!eng || B < 0 || (B > 0 && (!d_params || !d_xop || !d_sys))) { setError("csim_ac_system_dev: bad argument"); return CSIM_ERR_ARG; }
+    if (eng->plan.N > 63) { setError("AC analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
+    if (B == 0) return CSIM_OK;
+    HIPCHK(hipSetDevice(eng->device));
+    HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, 0, B, d_xop, d_sys,
+                                  static_cast<hipStream_t>(stream)));
+    return CSIM_OK;
+}
+
+int csim_ac_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const double* d_xop, const double* freqs,
+                      int32_t F, const int32_t* probe_eq, int32_t n_probe, double* d_out, uint32_t* d_status, void* stream)
+{
+    if (!eng || B < 0 || F < 0 || (B > 0 && F > 0 && (!d_params || !d_xop || !freqs || !d_out || !d_status))) {
+        setError("csim_ac_batch_dev: bad argument");
+        return CSIM_ERR_ARG;
+    }
+    if (const int rc = acCheck(eng)) return rc;
+    const int N = eng->plan.N;
+    const int nProbe = probe_eq ? n_probe : N;
+    if (probe_eq) {
+        if (n_probe <= 0) { setError("csim_ac_batch_dev: n_probe must be positive"); return CSIM_ERR_ARG; }
+        for (int i = 0; i < n_probe; ++i)
+            if (probe_eq[i] < 0 || probe_eq[i] >= N) { setError("probe equation index out of range"); return CSIM_ERR_ARG; }
+    }
+    int which = eng->cfg.acKernel;
+    if (which == csim::AC_KERNEL_AUTO) which = N <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
+    if (which == csim::AC_KERNEL_PACKED && N > 32) { setError("ac_kernel=packed covers N <= 32"); return CSIM_ERR_UNSUPPORTED; }
+    if (B == 0 || F == 0) return CSIM_OK;
+    HIPCHK(hipSetDevice(eng->device));
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+
+    // angular frequencies and the probe list: uploaded when they change (a synchronous copy), cached otherwise
+    std::vector<double> omega((size_t)F);
+    for (int f = 0; f < F; ++f) omega[(size_t)f] = 2.0 * eng->cir.ir.k.pi * freqs[f];
+    if (omega != eng->acOmegaCache) {
+        if (eng->acOmegaCap < F) {
+            if (eng->dAcOmega) HIPCHK(hipFree(eng->dAcOmega));
+            eng->dAcOmega = nullptr;
+            eng->acOmegaCap = 0;
+            HIPCHK(hipMalloc(reinterpret_cast<void**>(&eng->dAcOmega), sizeof(double) * (size_t)F));
+            eng->acOmegaCap = F;
+        }
+        eng->acOmegaCache.clear();
+        HIPCHK(hipMemcpy(eng->dAcOmega, omega.data(), sizeof(double) * (size_t)F, hipMemcpyHostToDevice));
+        eng->acOmegaCache = omega;
+    }
+    const int32_t* dProbe = nullptr;
+    if (probe_eq) {
+        std::vector<int32_t> want(probe_eq, probe_eq + n_probe);
+        if (want != eng->acProbeCache) {
+            if (eng->dAcProbe) HIPCHK(hipFree(eng->dAcProbe));
+            eng->dAcProbe = nullptr;
+            eng->acProbeCache.clear();
+            HIPCHK(hipMalloc(reinterpret_cast<void**>(&eng->dAcProbe), sizeof(int32_t) * want.size()));
+            HIPCHK(hipMemcpy(eng->dAcProbe, want.data(), sizeof(int32_t) * want.size(), hipMemcpyHostToDevice));
+            eng->acProbeCache = want;
+        }
+        dProbe = eng->dAcProbe;
+    }
+    const int chunk = acChunk(eng, B);
+    if (eng->acSysCap < chunk) {
+        if (eng->dAcSys) HIPCHK(hipFree(eng->dAcSys));
+        eng->dAcSys = nullptr;
+        eng->acSysCap = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&eng->dAcSys), sizeof(double) * csim::acSystemDoubles(N) * (size_t)chunk));
+        eng->acSysCap = chunk;
+    }
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int Bc = std::min(chunk, B - b0);
+        HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, b0, Bc, d_xop, eng->dAcSys, hs));
+        HIPCHK(csim::launchAcSweep(which, N, eng->dAcSys, eng->dAcOmega, F, dProbe, nProbe, B, b0, Bc, eng->cir.ir.k.lu_eps,
+                                   d_out, d_status, hs));
+    }
+    return CSIM_OK;
+}
+
+int csim_ac_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F,
+                  const int32_t* probe_eq, int32_t n_probe, double* out, uint32_t* status)
+{
+    if (!eng || B < 0) { setError("csim_ac_batch: bad argument"); return CSIM_ERR_ARG; }
+    if (const int rc = acCheck(eng)) return rc;
+    std::vector<double> card;
+    if (!freqs) {
+        if (!eng->acEnabled) { setError("csim_ac_batch: no frequencies given and the netlist has no .AC card"); return CSIM_ERR_CONFIG; }
+        const int64_t n = csim_ac_num_freqs(eng->acSweep, eng->acPoints, eng->acFstart, eng->acFstop);
+        if (n < 0) return static_cast<int>(n);
+        card.resize((size_t)n);
+        if (const int rc = csim_ac_freqs(eng->acSweep, eng->acPoints, eng->acFstart, eng->acFstop, card.data())) return rc;
+        freqs = card.data();
+        F = static_cast<int32_t>(n);
+    }
+    if (F < 0 || (B > 0 && F > 0 && !out)) { setError("csim_ac_batch: bad argument"); return CSIM_ERR_ARG; }
+    if (B == 0) return CSIM_OK;
+    HIPCHK(hipSetDevice(eng->device));
+    const int N = eng->plan.N;
+    const int nProbe = probe_eq ? n_probe : N;
+    DevBuf dParams, dX, dIt, dSt, dOut;
+    int rc = stageParams(eng, params, B, dParams);
+    if (rc) return rc;
+    const size_t outDoubles = (size_t)2 * F * (size_t)std::max(nProbe, 0) * B;
+    HIPCHK(dX.alloc(sizeof(double) * (size_t)N * B));
+    HIPCHK(dIt.alloc(sizeof(int32_t) * (size_t)B));
+    HIPCHK(dSt.alloc(sizeof(uint32_t) * (size_t)B));
+    HIPCHK(dOut.alloc(sizeof(double) * outDoubles));
+    rc = csim_dc_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), dIt.as<int32_t>(), dSt.as<uint32_t>(), nullptr);
+    if (rc) return rc;
+    rc = csim_ac_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), freqs, F, probe_eq, n_probe, dOut.as<double>(),
+                           dSt.as<uint32_t>(), nullptr);
+    if (rc) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    if (status) HIPCHK(hipMemcpy(status, dSt.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    if (outDoubles == 0) return CSIM_OK;
+    std::vector<double> h(outDoubles);                       // [F][n_probe][B] -> [B][F][n_probe]
+    HIPCHK(hipMemcpy(h.data(), dOut.p, sizeof(double) * outDoubles, hipMemcpyDeviceToHost));
+    for (int f = 0; f < F; ++f)
+        for (int p = 0; p < nProbe; ++p)
+            for (int b = 0; b < B; ++b) {
+                const size_t src = (((size_t)f * nProbe + p) * B + b) * 2;
+                const size_t dst = (((size_t)b * F + f) * nProbe + p) * 2;
+                out[dst] = h[src];
+                out[dst + 1] = h[src + 1];
+            }
     return CSIM_OK;
 }
 

@@ -29,6 +29,7 @@ struct EngineConfig {
     std::string jitGenOpts;      // jit_gen_opts: generator options of this engine's JIT, "key=value,key=value" (codegen.hpp)
     bool nearTestRollback = false;   // near_test_rollback: test aid -- every verified near-threshold decision counts as a
                                  // mismatch, so the roll-back path runs (results must not change)
+    int acKernel = 0;            // ac_kernel: test aid -- 0 auto (register-resident for N <= 32, else wave), 1 wave, 2 packed
     bool dcFast = false;         // dc_fast        / CSIM_DC_FAST: 1 = DC operating points start on the fast generated kernel
                                  // (contraction, reciprocal pivots, guarded decisions) instead of the faithful one
 };
@@ -101,6 +102,20 @@ struct csim_engine {
 
     // Gauss-Seidel DC: off-diagonal structure of the DC system per row (uploaded on first use)
     const int32_t *dGsRowPtr = nullptr, *dGsRowCol = nullptr;
+
+    // AC analysis: the netlist's .AC card, the excitation per element (re, im; element order), and the sweep's
+    // device tables (uploaded on first use, cached by content) and per-chunk system scratch
+    int acEnabled = 0, acSweep = 0, acPoints = 0;
+    double acFstart = 0.0, acFstop = 0.0;
+    bool acAnySource = false;
+    const double *dAcRe = nullptr, *dAcIm = nullptr;
+    double* dAcOmega = nullptr;
+    int acOmegaCap = 0;
+    std::vector<double> acOmegaCache;
+    int32_t* dAcProbe = nullptr;
+    std::vector<int32_t> acProbeCache;
+    double* dAcSys = nullptr;
+    int acSysCap = 0;                      // instances
 
     std::vector<int> netlistProbes;        // .PLOTNV / .PRINT node-voltage probes of the netlist (default CSV columns)
 

@@ -78,6 +78,16 @@ hipError_t launchMcParams(int P, int B, long long bFirst, uint64_t seed, double 
                           const double* dCox, const double* dW, const double* dL,
                           double* dParams, hipStream_t stream);
 
+// AC small-signal analysis (kernels_ac.hip).  System of one instance (acSystemDoubles(N) doubles): G and C
+// column-major [N][N], J re [N], J im [N].  Instances b0 .. b0+Bc-1 of a batch of B; dSys holds Bc systems.
+enum { AC_KERNEL_AUTO = 0, AC_KERNEL_WAVE = 1, AC_KERNEL_PACKED = 2 };
+size_t acSystemDoubles(int N);
+hipError_t launchAcAssemble(const GenPlan& pl, const double* dAcRe, const double* dAcIm, const double* dParams, int B,
+                            int b0, int Bc, const double* dXop, double* dSys, hipStream_t stream);
+// dOut [F][nProbe][B] complex (re, im), dStatus [B] OR-ed; dProbe null = every unknown (nProbe = N)
+hipError_t launchAcSweep(int which, int N, const double* dSys, const double* dOmega, int F, const int32_t* dProbe,
+                         int nProbe, int B, int b0, int Bc, double eps, double* dOut, uint32_t* dStatus, hipStream_t stream);
+
 // layout helpers (transpose.hip): [rows][cols] <-> [cols][rows] of doubles
 hipError_t launchTranspose(const double* dIn, double* dOut, int rows, int cols, hipStream_t stream);
 

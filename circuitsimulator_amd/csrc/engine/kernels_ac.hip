@@ -1,0 +1,393 @@
+// kernels_ac.hip -- small-signal AC analysis: (G(x_op) + jwC) v = J for B instances x F frequencies.
+//
+// AC is the small-signal limit of the engine's own backward-Euler transient (include/csim.h "AC analysis").
+// Three kernels:
+//
+//   ac_assemble_kernel   one wavefront per instance, ONCE per instance: the transient plan's gather
+//                        (device_common.hpp assemble(), linear in the term vector) run with two term vectors.
+//                        G pass: 1/R, incidence ones, tran_gmin, the MOSFET gd/gg/gs at x_op, companion terms
+//                        zero.  C pass: only C, L, Cj0/2, Cj0 in the companion slots (C/dt, L/dt, ... with dt = 1).
+//                        The RHS columns of the two passes carry the AC excitation (re, im) in the source
+//                        slots.  Same sparsity, signs and accumulation order as the transient.  Output per
+//                        instance: G and C column-major [N][N], then J re [N], J im [N].
+//   ac_sweep_wave_kernel one wavefront per instance, N <= 63: for every frequency the augmented complex
+//                        matrix in LDS (re / im planes, odd leading dimension), pivot by max-reduction and
+//                        ballot, rows swapped in LDS, elimination spread over the trailing sub-matrix.
+//   ac_sweep_packed_kernel  N <= 32: 32 lanes per instance, two instances per wavefront.  Lane r owns one row;
+//                        column j is register j (re and im: 2 (NP + 1) doubles, NP = N rounded up to 8).
+//                        Rows are exchanged logically: every lane carries the row position it holds; the pivot
+//                        row (a run-time lane) reaches the others by a bpermute per register.
+//
+// Both sweep kernels apply ac_lu.hpp's primitives to every entry in the same order: their outputs are
+// bit-identical (tests/test_ac_gpu.py forces each through the engine option ac_kernel).
+#include <hip/hip_runtime.h>
+
+#include "ac_lu.hpp"
+#include "device_common.hpp"
+#include "kernels.hpp"
+
+namespace csim {
+
+#pragma clang fp contract(off)
+
+namespace {
+
+// G pass (companion terms zero) or C pass (only the companion slots, as C, L, Cj0/2, Cj0) of the
+// transient's term vector; the source slots carry src[e] (re or im part of the AC excitation)
+template <bool CPASS>
+__device__ void ac_terms(const GenPlan& pl, const double* Pv, const double* x, const double* src, double* T, int lane)
+{
+    for (int e = lane; e < pl.nElem; e += 64) {
+        const int kind = pl.kind[e], s = pl.slot[e], tb = pl.termBase[e];
+        if (kind == CSIM_R) {
+            const double R = Pv[s];
+            T[tb + T_R_G] = CPASS ? 0.0 : ((R == 0.0) ? 0.0 : 1.0 / R);     // element.cpp:20-24
+        } else if (kind == CSIM_C) {
+            const double C = Pv[s];
+            T[tb + T_C_GC] = (CPASS && C > 0.0) ? C : 0.0;                  // tanalisis.cpp:65-67
+            T[tb + T_C_IH] = 0.0;
+        } else if (kind == CSIM_L) {
+            const double L = Pv[s];
+            const bool on = L > 0.0;                                         // tanalisis.cpp:296
+            T[tb + T_L_REQ] = (CPASS && on) ? L : 0.0;
+            T[tb + T_L_VH] = 0.0;
+            T[tb + T_L_ONE] = (!CPASS && on) ? 1.0 : 0.0;
+        } else if (kind == CSIM_V || kind == CSIM_I) {
+            T[tb + T_SRC_VAL] = src[e];
+        } else if (kind == CSIM_NMOS || kind == CSIM_PMOS) {
+            for (int t = 0; t <= T_M_IHDB; ++t) T[tb + t] = 0.0;
+            if (CPASS) {
+                const double Cj0 = Pv[s + 3];
+                const double Ch = 0.5 * Cj0;                                 // tanalisis.cpp:337-341
+                T[tb + T_M_GCH] = Ch > 0.0 ? Ch : 0.0;
+                T[tb + T_M_GCF] = Cj0 > 0.0 ? Cj0 : 0.0;
+            } else {
+                const int32_t* q = pl.eq + 4 * e;
+                const MosLin m = mos_eval(kind == CSIM_PMOS, Pv[s + 0], Pv[s + 1], Pv[s + 2], pl.k.mos_off_gds,
+                                          volt_of(x, q[0]), volt_of(x, q[1]), volt_of(x, q[2]));
+                T[tb + T_M_GD] = m.gd;
+                T[tb + T_M_GG] = m.gg;
+                T[tb + T_M_GS] = m.gs;
+            }
+        }
+    }
+    if (lane == 0) {
+        T[pl.termOne] = CPASS ? 0.0 : 1.0;
+        T[pl.termGmin] = CPASS ? 0.0 : pl.k.tran_gmin;                      // tanalisis.cpp:356
+    }
+    wave_sync();
+}
+
+// dense matrix of the LDS system -> column-major [N][N] + its RHS column
+__device__ void ac_store(const double* Gm, int N, int LD, double* mat, double* rhs, int lane)
+{
+    for (int idx = lane; idx < N * N; idx += 64) {
+        const int j = idx / N, i = idx - j * N;
+        mat[idx] = Gm[i * LD + j];
+    }
+    for (int i = lane; i < N; i += 64) rhs[i] = Gm[i * LD + N];
+    wave_sync();
+}
+
+__global__ void __launch_bounds__(64) ac_assemble_kernel(GenPlan pl, const double* __restrict__ acRe,
+                                                         const double* __restrict__ acIm, const double* __restrict__ params,
+                                                         int B, int b0, const double* __restrict__ xop, double* __restrict__ sys)
+{
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x;
+    const int c = blockIdx.x, b = b0 + c;
+    const int N = pl.N, LD = pl.LD;
+    double* T = lds;
+    double* Pv = T + pl.nTerms;
+    double* x = Pv + pl.P;
+    double* Gm = x + N;
+    for (int p = lane; p < pl.P; p += 64) Pv[p] = params[(size_t)p * B + b];
+    for (int i = lane; i < N; i += 64) x[i] = xop[(size_t)i * B + b];
+    wave_sync();
+    double* out = sys + (size_t)c * (2 * N * N + 2 * N);
+    ac_terms<false>(pl, Pv, x, acRe, T, lane);
+    assemble(pl, T, Gm, lane);
+    ac_store(Gm, N, LD, out, out + 2 * N * N, lane);
+    ac_terms<true>(pl, Pv, x, acIm, T, lane);
+    assemble(pl, T, Gm, lane);
+    ac_store(Gm, N, LD, out + N * N, out + 2 * N * N + N, lane);
+}
+
+// output offset of (frequency f, probe p, instance b), complex pairs: 64-bit
+__device__ __forceinline__ size_t ac_out_at(int f, int p, int nProbe, int B, int b)
+{
+    return (((size_t)f * (size_t)nProbe + (size_t)p) * (size_t)B + (size_t)b) * 2;
+}
+
+// ---- wave per system (N <= 63)
+__global__ void __launch_bounds__(64) ac_sweep_wave_kernel(int N, const double* __restrict__ sys, const double* __restrict__ omega,
+                                                           int F, const int32_t* __restrict__ probe, int nProbe, int B, int b0,
+                                                           double eps, double* __restrict__ out, uint32_t* __restrict__ status)
+{
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x;
+    const int c = blockIdx.x, b = b0 + c;
+    const int LD = (N + 1) | 1;                 // plan.hpp ldFor(): odd, >= N + 1
+    double* Ar = lds;
+    double* Ai = Ar + N * LD;
+    double* Lr = Ai + N * LD;        // multipliers of the current column, then products of the back substitution
+    double* Li = Lr + 64;
+    double* Xr = Li + 64;
+    double* Xi = Xr + 64;
+    const double* Gt = sys + (size_t)c * (2 * N * N + 2 * N);
+    const double* Ct = Gt + N * N;
+    const double* Jr = Ct + N * N;
+    const double* Ji = Jr + N;
+    const double eps2 = eps * eps;
+    unsigned flags = 0u;
+
+    for (int f = 0; f < F; ++f) {
+        const double w = omega[f];
+        for (int idx = lane; idx < N * N; idx += 64) {
+            const int j = idx / N, i = idx - j * N;
+            Ar[i * LD + j] = Gt[idx];
+            Ai[i * LD + j] = w * Ct[idx];
+        }
+        for (int i = lane; i < N; i += 64) { Ar[i * LD + N] = Jr[i]; Ai[i * LD + N] = Ji[i]; }
+        wave_sync();
+
+        bool failed = false;
+        for (int k = 0; k < N; ++k) {
+            const bool cand = lane >= k && lane < N;
+            const double v = cand ? cpx_abs2({Ar[lane * LD + k], Ai[lane * LD + k]}) : -1.0;
+            const double dv = read_lane(v, k);
+            int piv = k;
+            double maxv = dv;
+            if (dv == dv) {                  // a NaN diagonal keeps the pivot
+                maxv = wave_max(v);          // v_max_f64 drops NaN candidates, as "v > maxv" never takes them
+                piv = __ffsll((long long)__ballot(cand && v == maxv)) - 1;
+            }
+            if (maxv < eps2) { failed = true; break; }
+            if (piv != k) {
+                for (int j = k + lane; j <= N; j += 64) {
+                    double t = Ar[k * LD + j]; Ar[k * LD + j] = Ar[piv * LD + j]; Ar[piv * LD + j] = t;
+                    t = Ai[k * LD + j]; Ai[k * LD + j] = Ai[piv * LD + j]; Ai[piv * LD + j] = t;
+                }
+                wave_sync();
+            }
+            const cpx p = {Ar[k * LD + k], Ai[k * LD + k]};
+            if (lane > k && lane < N) {
+                const cpx l = cpx_div({Ar[lane * LD + k], Ai[lane * LD + k]}, p);
+                Lr[lane] = l.re;
+                Li[lane] = l.im;
+            }
+            wave_sync();
+            const int cols = N - k, total = (N - k - 1) * cols;
+            for (int e = lane; e < total; e += 64) {
+                const int di = e / cols;
+                const int i = k + 1 + di, j = k + 1 + (e - di * cols);
+                const cpx l = {Lr[i], Li[i]};
+                if (cpx_is_zero(l)) continue;
+                const cpx r = cpx_elim({Ar[i * LD + j], Ai[i * LD + j]}, l, {Ar[k * LD + j], Ai[k * LD + j]});
+                Ar[i * LD + j] = r.re;
+                Ai[i * LD + j] = r.im;
+            }
+            wave_sync();
+        }
+
+        if (failed) {
+            flags |= CSIM_ST_LU_TINY_PIVOT;
+            if (lane < N) { Xr[lane] = 0.0; Xi[lane] = 0.0; }
+        } else {
+            for (int i = N - 1; i >= 0; --i) {
+                if (lane > i && lane < N) {              // products U(i,j) x(j), then their ordered sum
+                    const cpx pr = cpx_mul({Ar[i * LD + lane], Ai[i * LD + lane]}, {Xr[lane], Xi[lane]});
+                    Lr[lane] = pr.re;
+                    Li[lane] = pr.im;
+                }
+                wave_sync();
+                cpx s = {Ar[i * LD + N], Ai[i * LD + N]};
+                for (int j = i + 1; j < N; ++j) s = cpx_sub(s, {Lr[j], Li[j]});
+                const cpx xv = cpx_div(s, {Ar[i * LD + i], Ai[i * LD + i]});
+                wave_sync();
+                if (lane == 0) { Xr[i] = xv.re; Xi[i] = xv.im; }
+                wave_sync();
+            }
+        }
+        wave_sync();
+        for (int p = lane; p < nProbe; p += 64) {
+            const int eq = probe ? probe[p] : p;
+            const size_t at = ac_out_at(f, p, nProbe, B, b);
+            out[at] = Xr[eq];
+            out[at + 1] = Xi[eq];
+        }
+        wave_sync();
+    }
+    if (lane == 0 && flags) status[b] |= flags;
+}
+
+// ---- register-resident, 32 lanes per system (N <= NP <= 32)
+constexpr int ACP_LANES = 32;
+
+__device__ __forceinline__ unsigned half_ballot(bool pred, int h)
+{
+    return (unsigned)((__ballot(pred) >> (h * ACP_LANES)) & 0xFFFFFFFFull);
+}
+__device__ __forceinline__ double half_max(double v)
+{
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, ACP_LANES));
+    return v;
+}
+__device__ __forceinline__ int half_min(int v)
+{
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m, ACP_LANES));
+    return v;
+}
+
+// column K of the elimination: pivot search over the positions K..N-1, logical exchange of positions K and
+// the pivot's, pivot row to every lane, rows below apply their multiplier
+template <int NP, int K>
+__device__ __forceinline__ void acp_column(double (&ar)[NP + 1], double (&ai)[NP + 1], int N, int& pos, bool& failed,
+                                           double eps2, int h)
+{
+    if constexpr (K < NP) {
+        if (K < N) {
+            const bool cand = pos >= K && pos < N;
+            const double v = cand ? cpx_abs2({ar[K], ai[K]}) : -1.0;
+            const int dl = __ffs((int)half_ballot(pos == K, h)) - 1;
+            const double dv = __shfl(v, dl, ACP_LANES);
+            const double m = half_max(v);
+            const int first = half_min((cand && v == m) ? pos : 1 << 20);
+            const bool nanDiag = dv != dv;                   // a NaN diagonal keeps the pivot
+            const int pivPos = nanDiag ? K : first;
+            const double maxv = nanDiag ? dv : m;
+            if (maxv < eps2) failed = true;
+            const int pl = __ffs((int)half_ballot(pos == pivPos, h)) - 1;
+            if (pos == pivPos) pos = K;
+            else if (pos == K) pos = pivPos;
+            const cpx p = {__shfl(ar[K], pl, ACP_LANES), __shfl(ai[K], pl, ACP_LANES)};
+            cpx l = {0.0, 0.0};
+            if (pos > K && pos < N) l = cpx_div({ar[K], ai[K]}, p);
+            const bool upd = !cpx_is_zero(l);
+#pragma unroll
+            for (int j = K + 1; j <= NP; ++j) {
+                const cpx u = {__shfl(ar[j], pl, ACP_LANES), __shfl(ai[j], pl, ACP_LANES)};
+                if (upd) {
+                    const cpx r = cpx_elim({ar[j], ai[j]}, l, u);
+                    ar[j] = r.re;
+                    ai[j] = r.im;
+                }
+            }
+        }
+        acp_column<NP, K + 1>(ar, ai, N, pos, failed, eps2, h);
+    }
+}
+
+// row I of the back substitution: every lane sums on its own row, the lane holding position I stores x(I)
+template <int NP, int I>
+__device__ __forceinline__ void acp_back(const double (&ar)[NP + 1], const double (&ai)[NP + 1], int N, int pos,
+                                         double* Xr, double* Xi)
+{
+    if constexpr (I >= 0) {
+        if (I < N) {
+            cpx s = {ar[NP], ai[NP]};
+#pragma unroll
+            for (int j = I + 1; j < NP; ++j)
+                if (j < N) s = cpx_sub(s, cpx_mul({ar[j], ai[j]}, {Xr[j], Xi[j]}));
+            const cpx xv = cpx_div(s, {ar[I], ai[I]});
+            if (pos == I) { Xr[I] = xv.re; Xi[I] = xv.im; }
+            __syncthreads();
+        }
+        acp_back<NP, I - 1>(ar, ai, N, pos, Xr, Xi);
+    }
+}
+
+template <int NP>
+__global__ void __launch_bounds__(64) ac_sweep_packed_kernel(int N, const double* __restrict__ sys, const double* __restrict__ omega,
+                                                             int F, const int32_t* __restrict__ probe, int nProbe, int B, int b0,
+                                                             int Bc, double eps, double* __restrict__ out,
+                                                             uint32_t* __restrict__ status)
+{
+    __shared__ double xs[2][2][ACP_LANES];                  // [instance][re, im][position]
+    const int lane = threadIdx.x;
+    const int h = lane / ACP_LANES, r = lane % ACP_LANES;
+    const int c = blockIdx.x * 2 + h;
+    const bool on = c < Bc;                                 // the second half of the last block may be empty
+    const int cc = on ? c : 0;
+    const int b = b0 + cc;
+    const double* Gt = sys + (size_t)cc * (2 * N * N + 2 * N);
+    const double* Ct = Gt + N * N;
+    const double* Jr = Ct + N * N;
+    const double* Ji = Jr + N;
+    double* Xr = xs[h][0];
+    double* Xi = xs[h][1];
+    const double eps2 = eps * eps;
+    unsigned flags = 0u;
+
+    for (int f = 0; f < F; ++f) {
+        const double w = omega[f];
+        double ar[NP + 1], ai[NP + 1];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            const bool in = r < N && j < N;
+            ar[j] = in ? Gt[j * N + r] : 0.0;
+            ai[j] = in ? w * Ct[j * N + r] : 0.0;
+        }
+        ar[NP] = r < N ? Jr[r] : 0.0;
+        ai[NP] = r < N ? Ji[r] : 0.0;
+        int pos = r;
+        bool failed = false;
+        acp_column<NP, 0>(ar, ai, N, pos, failed, eps2, h);
+        acp_back<NP, NP - 1>(ar, ai, N, pos, Xr, Xi);
+        if (failed) flags |= CSIM_ST_LU_TINY_PIVOT;
+        for (int p = r; p < nProbe; p += ACP_LANES) {
+            const int eq = probe ? probe[p] : p;
+            if (on) {
+                const size_t at = ac_out_at(f, p, nProbe, B, b);
+                out[at] = failed ? 0.0 : Xr[eq];
+                out[at + 1] = failed ? 0.0 : Xi[eq];
+            }
+        }
+        __syncthreads();
+    }
+    if (on && r == 0 && flags) status[b] |= flags;
+}
+
+} // namespace
+
+size_t acSystemDoubles(int N) { return (size_t)2 * N * N + (size_t)2 * N; }
+
+hipError_t launchAcAssemble(const GenPlan& pl, const double* dAcRe, const double* dAcIm, const double* dParams, int B,
+                            int b0, int Bc, const double* dXop, double* dSys, hipStream_t stream)
+{
+    if (Bc <= 0) return hipSuccess;
+    const size_t lds = sizeof(double) * ((size_t)pl.nTerms + pl.P + pl.N + (size_t)pl.N * pl.LD);
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute((const void*)ac_assemble_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(ac_assemble_kernel, dim3(Bc), dim3(64), lds, stream, pl, dAcRe, dAcIm, dParams, B, b0, dXop, dSys);
+    return hipGetLastError();
+}
+
+#define CSIM_ACP(NPV) hipLaunchKernelGGL(ac_sweep_packed_kernel<NPV>, dim3(grid), dim3(64), 0, stream, N, dSys, dOmega, F, dProbe, nProbe, B, b0, Bc, eps, dOut, dStatus)
+
+hipError_t launchAcSweep(int which, int N, const double* dSys, const double* dOmega, int F, const int32_t* dProbe,
+                         int nProbe, int B, int b0, int Bc, double eps, double* dOut, uint32_t* dStatus, hipStream_t stream)
+{
+    if (Bc <= 0 || F <= 0) return hipSuccess;
+    if (N < 1 || N > 63 || (which == AC_KERNEL_PACKED && N > 32)) return hipErrorInvalidValue;
+    if (which == AC_KERNEL_PACKED) {
+        const int grid = (Bc + 1) / 2;
+        if (N <= 8) CSIM_ACP(8);
+        else if (N <= 16) CSIM_ACP(16);
+        else if (N <= 24) CSIM_ACP(24);
+        else CSIM_ACP(32);
+    } else {
+        const size_t lds = sizeof(double) * (2 * (size_t)N * ldFor(N) + 4 * 64);
+        if (lds > 64 * 1024)
+            (void)hipFuncSetAttribute((const void*)ac_sweep_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(ac_sweep_wave_kernel, dim3(Bc), dim3(64), lds, stream, N, dSys, dOmega, F, dProbe, nProbe, B, b0,
+                           eps, dOut, dStatus);
+    }
+    return hipGetLastError();
+}
+#undef CSIM_ACP
+
+} // namespace csim

@@ -135,6 +135,58 @@ int csim_netlist_tran(const csim_netlist* nl, int32_t* enabled, double* tstep, d
     return CSIM_OK;
 }
 
+int csim_netlist_ac(const csim_netlist* nl, int32_t* enabled, int32_t* sweep, int32_t* n_points, double* fstart,
+                    double* fstop)
+{
+    if (!nl) return CSIM_ERR_ARG;
+    const AcConfig& a = nl->sim.ac;
+    if (enabled)  *enabled = a.enabled ? 1 : 0;
+    if (sweep)    *sweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
+    if (n_points) *n_points = a.nPoints;
+    if (fstart)   *fstart = a.fstart;
+    if (fstop)    *fstop = a.fstop;
+    return CSIM_OK;
+}
+
+int csim_netlist_ac_source(const csim_netlist* nl, int32_t elem, double* mag, double* phase_deg)
+{
+    if (!nl || elem < 0 || elem >= nl->cir.ir.n_elems) { csim::setError("csim_netlist_ac_source: bad element index"); return CSIM_ERR_ARG; }
+    if (mag) *mag = nl->cir.acMag[static_cast<std::size_t>(elem)];
+    if (phase_deg) *phase_deg = nl->cir.acPhaseDeg[static_cast<std::size_t>(elem)];
+    return CSIM_OK;
+}
+
+// SPICE frequency grid of an .AC card (DEC / OCT: n points per decade / octave from fstart, up to fstop;
+// LIN: n points from fstart to fstop inclusive)
+int64_t csim_ac_num_freqs(int32_t sweep, int32_t n_points, double fstart, double fstop)
+{
+    if (sweep < 0 || sweep > 2) { csim::setError("AC sweep must be 0 (DEC), 1 (OCT) or 2 (LIN)"); return CSIM_ERR_CONFIG; }
+    if (n_points <= 0 || !std::isfinite(fstart) || !std::isfinite(fstop) || fstop < fstart || (sweep != 2 && fstart <= 0.0)) {
+        csim::setError("invalid .AC numbers (need n > 0, fstop >= fstart, fstart > 0 for DEC/OCT)");
+        return CSIM_ERR_CONFIG;
+    }
+    if (sweep == 2) return n_points;
+    const double span = sweep == 0 ? std::log10(fstop / fstart) : std::log2(fstop / fstart);
+    const double last = std::floor(static_cast<double>(n_points) * span + 1e-9);
+    if (!(last >= 0.0) || last >= 2147483647.0) { csim::setError("invalid .AC numbers: too many points"); return CSIM_ERR_CONFIG; }
+    return static_cast<int64_t>(last) + 1;
+}
+
+int csim_ac_freqs(int32_t sweep, int32_t n_points, double fstart, double fstop, double* f)
+{
+    const int64_t n = csim_ac_num_freqs(sweep, n_points, fstart, fstop);
+    if (n < 0) return static_cast<int>(n);
+    if (!f) { csim::setError("csim_ac_freqs: null output"); return CSIM_ERR_ARG; }
+    if (sweep == 2) {
+        for (int64_t k = 0; k < n; ++k)
+            f[k] = n == 1 ? fstart : fstart + static_cast<double>(k) * (fstop - fstart) / static_cast<double>(n - 1);
+    } else {
+        const double base = sweep == 0 ? 10.0 : 2.0;
+        for (int64_t k = 0; k < n; ++k) f[k] = fstart * std::pow(base, static_cast<double>(k) / n_points);
+    }
+    return CSIM_OK;
+}
+
 int csim_netlist_num_probes(const csim_netlist* nl) { return nl ? static_cast<int>(nl->probeEq.size()) : 0; }
 
 int csim_netlist_probe_eq(const csim_netlist* nl, int32_t i)

@@ -15,6 +15,21 @@ import numpy as np
 from . import capi
 
 
+AC_SWEEPS = ("dec", "oct", "lin")
+
+
+def ac_freqs(sweep, n_points, fstart, fstop):
+    """SPICE frequency grid (csim_ac_freqs): sweep "dec" | "oct" | "lin" (or 0, 1, 2) -> numpy [F], Hz."""
+    sw = AC_SWEEPS.index(sweep.lower()) if isinstance(sweep, str) else int(sweep)
+    L = capi.lib()
+    n = L.csim_ac_num_freqs(sw, int(n_points), float(fstart), float(fstop))
+    if n < 0:
+        capi.check(int(n))
+    f = np.zeros(n, dtype=np.float64)
+    capi.check(L.csim_ac_freqs(sw, int(n_points), float(fstart), float(fstop), f.ctypes.data))
+    return f
+
+
 class Netlist:
     """A parsed, indexed and flattened netlist (host only)."""
 
@@ -39,6 +54,22 @@ class Netlist:
         capi.check(L.csim_netlist_nominal_params(self._h, self.nominal_params.ctypes.data))
         self.mc_kinds = np.zeros(self.n_params, dtype=np.int32)
         capi.check(L.csim_netlist_mc_kinds(self._h, self.mc_kinds.ctypes.data))
+        en, sw, npt, f0, f1 = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double(), C.c_double()
+        capi.check(L.csim_netlist_ac(self._h, C.byref(en), C.byref(sw), C.byref(npt), C.byref(f0), C.byref(f1)))
+        # the .AC card: None, or (sweep "dec" | "oct" | "lin", n_points, fstart, fstop)
+        self.ac = (AC_SWEEPS[sw.value], npt.value, f0.value, f1.value) if en.value else None
+
+    def ac_freqs(self):
+        """Frequency grid of the .AC card (numpy, Hz)."""
+        if self.ac is None:
+            raise capi.CsimError(capi.CSIM_ERR_CONFIG, "the netlist has no .AC card")
+        return ac_freqs(*self.ac)
+
+    def ac_source(self, elem):
+        """(mag, phase_deg) of element elem's `AC mag [phase]` (0, 0 without one)."""
+        m, p = C.c_double(), C.c_double()
+        capi.check(capi.lib().csim_netlist_ac_source(self._h, int(elem), C.byref(m), C.byref(p)))
+        return m.value, p.value
 
     @property
     def has_nonlinear(self):
@@ -230,7 +261,50 @@ class Engine:
             int(out_stride), wave.data_ptr() if wave is not None else None, x.data_ptr(), iters.data_ptr(),
             status.data_ptr(), step_iters.data_ptr() if step_iters is not None else None, self._stream()))
 
+    def _ac_args(self, freqs, probes):
+        f = self.netlist.ac_freqs() if freqs is None else np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        pe = None if probes is None else (C.c_int32 * len(probes))(*probes)
+        return f, pe, (self.N if probes is None else len(probes))
+
+    def ac(self, params, x_op, freqs=None, probes=None, status=None):
+        """AC sweep of the batch around the operating points x_op (device [N][B], from dc()).
+        freqs: Hz (None = the .AC card); probes: equation indices (None = every unknown).
+        -> (device complex128 [F][n_probe][B], status [B] int32, OR-ed into `status` when given)."""
+        torch = _torch()
+        B = params.shape[1]
+        f, pe, n_probe = self._ac_args(freqs, probes)
+        out = torch.zeros((len(f), n_probe, B, 2), dtype=torch.float64, device=self._dev())
+        st = status if status is not None else torch.zeros(B, dtype=torch.int32, device=self._dev())
+        capi.check(capi.lib().csim_ac_batch_dev(self._h, params.data_ptr(), B, x_op.data_ptr(), f.ctypes.data, len(f),
+                                                pe, n_probe, out.data_ptr(), st.data_ptr(), self._stream()))
+        return torch.view_as_complex(out), st
+
+    def ac_system(self, params, x_op):
+        """The linearised system per instance (csim_ac_system_dev): -> (G [B][N][N], C [B][N][N], J [B][N] complex),
+        device tensors."""
+        torch = _torch()
+        B, N = params.shape[1], self.N
+        sys = torch.empty((B, 2 * N * N + 2 * N), dtype=torch.float64, device=self._dev())
+        capi.check(capi.lib().csim_ac_system_dev(self._h, params.data_ptr(), B, x_op.data_ptr(), sys.data_ptr(),
+                                                 self._stream()))
+        G = sys[:, :N * N].reshape(B, N, N).transpose(1, 2)
+        Cm = sys[:, N * N:2 * N * N].reshape(B, N, N).transpose(1, 2)
+        J = torch.complex(sys[:, 2 * N * N:2 * N * N + N], sys[:, 2 * N * N + N:])
+        return G, Cm, J
+
     # -- host-pointer forms (numpy, instance-major as in SURVEY.md 8b) --------
+    def ac_host(self, params=None, B=1, freqs=None, probes=None):
+        """DC operating point + AC sweep: -> (numpy complex128 [B][F][n_probe], status [B])."""
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=np.float64)
+            B = params.shape[0]
+        f, pe, n_probe = self._ac_args(freqs, probes)
+        out = np.zeros((B, len(f), n_probe, 2))
+        st = np.zeros(B, dtype=np.uint32)
+        capi.check(capi.lib().csim_ac_batch(self._h, params.ctypes.data if params is not None else None, B,
+                                            f.ctypes.data, len(f), pe, n_probe, out.ctypes.data, st.ctypes.data))
+        return out[..., 0] + 1j * out[..., 1], st
+
     def dc_host(self, params=None, B=1):
         if params is not None:
             params = np.ascontiguousarray(params, dtype=np.float64)

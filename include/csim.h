@@ -78,7 +78,7 @@ extern "C" {
 #define CSIM_ERR_HIP          -4   /* a HIP runtime call failed                    */
 #define CSIM_ERR_UNSUPPORTED  -5   /* circuit outside what the kernels cover       */
 #define CSIM_ERR_EMPTY        -6   /* circuit has no unknowns                      */
-#define CSIM_ERR_CONFIG       -7   /* invalid .TRAN numbers (tstep/tstop <= 0)     */
+#define CSIM_ERR_CONFIG       -7   /* invalid .TRAN / .AC numbers, no AC source    */
 
 typedef struct csim_netlist csim_netlist;
 typedef struct csim_engine  csim_engine;
@@ -125,6 +125,12 @@ int  csim_netlist_dc_sweep_params(const csim_netlist* nl, int32_t i, int64_t n_p
 /* header line of the reference's transient CSV (src/tanalisis.cpp:191-206):
  * "time,V(<node>)...,I(<elem>)..."; returns the length needed (excl. NUL) */
 int  csim_netlist_csv_header(const csim_netlist* nl, char* buf, int32_t cap);
+/* .AC card (src/parser.cpp:526-549): sweep 0 DEC, 1 OCT, 2 LIN                   */
+int  csim_netlist_ac(const csim_netlist* nl, int32_t* enabled, int32_t* sweep, int32_t* n_points,
+                     double* fstart, double* fstop);
+/* AC excitation of element `elem` (`AC mag [phase_deg]` on a V/I line; 0, 0 for any other element).
+ * Kept beside the IR, not in the parameter vector: P and the slots are those of the netlist without AC. */
+int  csim_netlist_ac_source(const csim_netlist* nl, int32_t elem, double* mag, double* phase_deg);
 /* Monte-Carlo recipe per parameter slot: 0 fixed, 1 scaled by (1+sigma z),
  * 2 MOS K rebuilt from a MU draw: K = (MU(1+sigma z))*COX*(W/L)              */
 int  csim_netlist_mc_kinds(const csim_netlist* nl, int32_t* kinds);
@@ -176,6 +182,7 @@ int  csim_engine_set_kernel(csim_engine* eng, int32_t which);
  *   near_test_rollback (0)                  test aid: every verified near-threshold decision is treated as a
  *                                           mismatch, so the roll-back path runs (results must not change)
  *   hybrid_sync (CSIM_HYBRID_SYNC, 1)       see "Streams" above
+ *   ac_kernel (auto)                        test aid: AC sweep kernel, auto | wave | packed (see csim_ac_batch_dev)
  *   dc_fast (CSIM_DC_FAST, 0)               DC operating points start on the fast generated kernel (FMA
  *                                           contraction, reciprocal pivots; controller decisions within
  *                                           its rounding noise are replayed) instead of the faithful one
@@ -247,6 +254,48 @@ int  csim_tran_write_csv(csim_engine* eng, const double* params, int32_t B, int3
 /* number of rows csim_tran_batch writes per instance for these numbers       */
 int64_t csim_tran_num_rows(double tstep, double tstop, double tstart, int32_t out_stride);
 int64_t csim_tran_num_steps(double tstep, double tstop);
+
+/* ---- AC small-signal analysis (.AC; the reference parses the card and never runs it) ----
+ * The small-signal limit of this engine's own backward-Euler transient (csim_tran_batch), linearised at a DC
+ * operating point x_op:  (G + j w C) v = J,  w = 2 pi f (pi = csim_consts.pi).
+ *   G  the transient matrix with every companion term removed: resistors 1/R, V-source and inductor incidence
+ *      (+-1), the MOSFET Jacobian gd, gg, gs of mos_eval at x_op (src/element.cpp:181-274; cst unused),
+ *      tran_gmin on every node row (src/tanalisis.cpp:356).
+ *   C  capacitors C; MOSFET Cgs = Cgd = Cj0/2, Csb = Cdb = Cj0 (src/tanalisis.cpp:334-352); an inductor adds -L on
+ *      its branch diagonal (branch row Vp - Vm - j w L I = 0).  An element the transient leaves out is left out
+ *      here too, incidence included: C <= 0, L <= 0, Cj0 <= 0.
+ *   J  the AC excitations only, mag (cos phi, sin phi), phi = deg pi / 180, stamped as stampAC does
+ *      (src/element.cpp:68-81,125-151); DC values and waveforms do not enter.
+ * Assembled once per instance with the transient's gather order, then for every frequency a complex LU with
+ * partial pivoting in the shape of Solver::solveLinearSystemLU: pivot = the first row with the largest
+ * re^2 + im^2 (strict '>'); a maximum below lu_eps^2 gives the zero vector for that (instance, frequency) and
+ * sets CSIM_ST_LU_TINY_PIVOT in the instance's status; the rest of the sweep goes on.  Multiplier
+ * a conj(p) (1 / |p|^2), back substitution in ascending column order, no FMA contraction.  Circuits of up to
+ * 63 unknowns (CSIM_ERR_UNSUPPORTED beyond); no source with mag != 0: CSIM_ERR_CONFIG.
+ *
+ * Frequency grid (SPICE): DEC fstart 10^(k/n), OCT fstart 2^(k/n), k = 0 .. floor(n log_b(fstop/fstart) + 1e-9);
+ * LIN n points from fstart to fstop inclusive (n == 1: fstart).  n <= 0, fstart <= 0 (DEC/OCT) or fstop < fstart:
+ * CSIM_ERR_CONFIG.                                                                                              */
+int64_t csim_ac_num_freqs(int32_t sweep, int32_t n_points, double fstart, double fstop);   /* < 0: error */
+int  csim_ac_freqs(int32_t sweep, int32_t n_points, double fstart, double fstop, double* f);
+/* Enqueues the sweep; never waits (a new frequency or probe list is uploaded once, synchronously, then cached).
+ *   d_xop    [N][B] operating points (csim_dc_batch_dev)     freqs   host [F], Hz
+ *   probe_eq host, NULL = every unknown (n_probe ignored)    d_out   [F][n_probe][B] complex (re, im) pairs
+ *   d_status [B], OR-ed
+ * The engine option ac_kernel (test aid) forces the sweep kernel: "wave" (one wavefront per system, N <= 63) or
+ * "packed" (registers, 32 lanes per system, N <= 32); "auto" picks packed for N <= 32.  Both give bit-identical
+ * results.                                                                                                      */
+int  csim_ac_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int32_t B, const double* d_xop,
+                       const double* freqs, int32_t F, const int32_t* probe_eq, int32_t n_probe,
+                       double* d_out, uint32_t* d_status, void* stream);
+/* DC operating point, then the sweep.  params [B][P] or NULL (nominal); freqs NULL = the netlist's .AC card
+ * (F ignored); out [B][F][n_probe] complex; status [B]: DC and AC bits.                                      */
+int  csim_ac_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F,
+                   const int32_t* probe_eq, int32_t n_probe, double* out, uint32_t* status);
+/* The linearised system itself, per instance (enqueue only): d_sys [B][2N^2 + 2N] = G column-major [N][N],
+ * C column-major [N][N], J re [N], J im [N].                                                                    */
+int  csim_ac_system_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int32_t B, const double* d_xop,
+                        double* d_sys, void* stream);
 
 /* Batched dense solve A x = b with the engine's pivoted LU
  * (Solver::solveLinearSystemLU semantics: first-maximum partial pivoting,
