@@ -79,6 +79,7 @@ PROTOTYPES = {
     "csim_tran_num_rows": (_i64, [_dbl, _dbl, _dbl, _i32]),
     "csim_tran_num_steps": (_i64, [_dbl, _dbl]),
     "csim_lu_solve_batch": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "csim_ac_solve_batch": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "csim_lu_decompose_batch": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "csim_gs_solve_batch": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _i32, _dbl, _vp, _vp]),
     "csim_dc_gs_batch_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),

@@ -320,8 +320,11 @@ void csim_engine_destroy(csim_engine* eng)
     if (eng->hViolFlag) (void)hipHostFree(eng->hViolFlag);
     if (eng->dKnownAlts) (void)hipFree(eng->dKnownAlts);
     if (eng->dBigScratch) (void)hipFree(eng->dBigScratch);
-    if (eng->dAcOmega) (void)hipFree(eng->dAcOmega);
-    if (eng->dAcProbe) (void)hipFree(eng->dAcProbe);
+    for (auto* ring : {&eng->acOmegaSlots, &eng->acProbeSlots})
+        for (auto& s : *ring) {
+            if (s.done) (void)hipEventDestroy(s.done);
+            if (s.d) (void)hipFree(s.d);
+        }
     if (eng->dAcSys) (void)hipFree(eng->dAcSys);
     if (eng->schedLib) dlclose(eng->schedLib);
     delete eng;
@@ -803,6 +806,43 @@ static int acCheck(const csim_engine* eng)
     return CSIM_OK;
 }
 
+// A new frequency or probe list for the sweeps: into a slot no enqueued sweep still reads (never the current one,
+// which the previous call's kernels may be using), with a synchronous copy -- complete before the caller's next
+// launch, whatever its stream.  The ring grows only while more than its size of distinct lists are in flight;
+// at AC_MAX_SLOTS the oldest reader is waited for (that event alone, not the device).
+static constexpr size_t AC_MAX_SLOTS = 8;
+static int acUpload(std::vector<csim_engine::AcList>& ring, int& cur, const void* src, size_t bytes)
+{
+    int slot = -1;
+    for (size_t i = 0; i < ring.size() && slot < 0; ++i) {
+        if ((int)i == cur) continue;
+        const hipError_t q = hipEventQuery(ring[i].done);
+        if (q == hipSuccess) slot = (int)i;
+        else if (q != hipErrorNotReady) HIPCHK(q);
+    }
+    (void)hipGetLastError();                     // "not ready" is an answer here, not an error for the next launch check
+    if (slot < 0 && ring.size() < AC_MAX_SLOTS) {
+        ring.emplace_back();
+        slot = (int)ring.size() - 1;
+        HIPCHK(hipEventCreateWithFlags(&ring[(size_t)slot].done, hipEventDisableTiming));
+    }
+    if (slot < 0) {
+        slot = (cur + 1) % (int)ring.size();
+        HIPCHK(hipEventSynchronize(ring[(size_t)slot].done));
+    }
+    csim_engine::AcList& s = ring[(size_t)slot];
+    if (s.cap < bytes) {
+        if (s.d) HIPCHK(hipFree(s.d));
+        s.d = nullptr;
+        s.cap = 0;
+        HIPCHK(hipMalloc(&s.d, bytes));
+        s.cap = bytes;
+    }
+    HIPCHK(hipMemcpy(s.d, src, bytes, hipMemcpyHostToDevice));
+    cur = slot;
+    return CSIM_OK;
+}
+
 int csim_ac_system_dev(csim_engine* eng, const double* d_params, int32_t B, const double* d_xop, double* d_sys, void* stream)
 {
     if (!eng || B < 0 || (B > 0 && (!d_params || !d_xop || !d_sys))) { setError("csim_ac_system_dev: bad argument"); return CSIM_ERR_ARG; }
@@ -836,33 +876,24 @@ int csim_ac_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const
     HIPCHK(hipSetDevice(eng->device));
     hipStream_t hs = static_cast<hipStream_t>(stream);
 
-    // angular frequencies and the probe list: uploaded when they change (a synchronous copy), cached otherwise
+    // angular frequencies and the probe list: uploaded when they change, cached otherwise
     std::vector<double> omega((size_t)F);
     for (int f = 0; f < F; ++f) omega[(size_t)f] = 2.0 * eng->cir.ir.k.pi * freqs[f];
-    if (omega != eng->acOmegaCache) {
-        if (eng->acOmegaCap < F) {
-            if (eng->dAcOmega) HIPCHK(hipFree(eng->dAcOmega));
-            eng->dAcOmega = nullptr;
-            eng->acOmegaCap = 0;
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&eng->dAcOmega), sizeof(double) * (size_t)F));
-            eng->acOmegaCap = F;
-        }
+    if (eng->acOmegaCur < 0 || omega != eng->acOmegaCache) {
         eng->acOmegaCache.clear();
-        HIPCHK(hipMemcpy(eng->dAcOmega, omega.data(), sizeof(double) * (size_t)F, hipMemcpyHostToDevice));
+        if (const int rc = acUpload(eng->acOmegaSlots, eng->acOmegaCur, omega.data(), sizeof(double) * (size_t)F)) return rc;
         eng->acOmegaCache = omega;
     }
+    const double* dOmega = static_cast<const double*>(eng->acOmegaSlots[(size_t)eng->acOmegaCur].d);
     const int32_t* dProbe = nullptr;
     if (probe_eq) {
         std::vector<int32_t> want(probe_eq, probe_eq + n_probe);
-        if (want != eng->acProbeCache) {
-            if (eng->dAcProbe) HIPCHK(hipFree(eng->dAcProbe));
-            eng->dAcProbe = nullptr;
+        if (eng->acProbeCur < 0 || want != eng->acProbeCache) {
             eng->acProbeCache.clear();
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&eng->dAcProbe), sizeof(int32_t) * want.size()));
-            HIPCHK(hipMemcpy(eng->dAcProbe, want.data(), sizeof(int32_t) * want.size(), hipMemcpyHostToDevice));
+            if (const int rc = acUpload(eng->acProbeSlots, eng->acProbeCur, want.data(), sizeof(int32_t) * want.size())) return rc;
             eng->acProbeCache = want;
         }
-        dProbe = eng->dAcProbe;
+        dProbe = static_cast<const int32_t*>(eng->acProbeSlots[(size_t)eng->acProbeCur].d);
     }
     const int chunk = acChunk(eng, B);
     if (eng->acSysCap < chunk) {
@@ -875,9 +906,11 @@ int csim_ac_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int Bc = std::min(chunk, B - b0);
         HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, b0, Bc, d_xop, eng->dAcSys, hs));
-        HIPCHK(csim::launchAcSweep(which, N, eng->dAcSys, eng->dAcOmega, F, dProbe, nProbe, B, b0, Bc, eng->cir.ir.k.lu_eps,
+        HIPCHK(csim::launchAcSweep(which, N, eng->dAcSys, dOmega, F, dProbe, nProbe, B, b0, Bc, eng->cir.ir.k.lu_eps,
                                    d_out, d_status, hs));
     }
+    HIPCHK(hipEventRecord(eng->acOmegaSlots[(size_t)eng->acOmegaCur].done, hs));
+    if (dProbe) HIPCHK(hipEventRecord(eng->acProbeSlots[(size_t)eng->acProbeCur].done, hs));
     return CSIM_OK;
 }
 
@@ -1204,6 +1237,67 @@ int csim_lu_solve_batch(int32_t device, int32_t n, int32_t B, const double* A, c
         HIPCHK(csim::launchLuSolve(n, B, dA.as<double>(), dB.as<double>(), dX.as<double>(), dF.as<uint32_t>(), 1e-15, nullptr));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(x, dX.p, sizeof(double) * (size_t)n * B, hipMemcpyDeviceToHost));
+    if (flags) HIPCHK(hipMemcpy(flags, dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    return CSIM_OK;
+}
+
+// the complex counterpart: any (G + jwC) x = J through the AC sweep kernels, without an engine or a netlist
+int csim_ac_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* Cm, const double* J,
+                        const double* omega, int32_t F, int32_t kernel, double* x, uint32_t* flags)
+{
+    if (n < 0 || B < 0 || F < 0 || kernel < csim::AC_KERNEL_AUTO || kernel > csim::AC_KERNEL_PACKED ||
+        (n > 0 && B > 0 && F > 0 && (!G || !Cm || !J || !omega || !x))) {
+        setError("csim_ac_solve_batch: bad argument");
+        return CSIM_ERR_ARG;
+    }
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
+        setError("csim_ac_solve_batch: no usable HIP device (this library has no CPU path)");
+        return CSIM_ERR_NO_DEVICE;
+    }
+    if (n > 63) { setError("csim_ac_solve_batch covers n <= 63"); return CSIM_ERR_UNSUPPORTED; }
+    int which = kernel;
+    if (which == csim::AC_KERNEL_AUTO) which = n <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
+    if (which == csim::AC_KERNEL_PACKED && n > 32) { setError("csim_ac_solve_batch: the packed kernel covers n <= 32"); return CSIM_ERR_UNSUPPORTED; }
+    if (n == 0 || B == 0 || F == 0) return CSIM_OK;
+    HIPCHK(hipSetDevice(device));
+    // [B][n][n] row-major -> the layout launchAcSweep reads: G, C column-major, J re, J im
+    const size_t nn = (size_t)n * n, per = csim::acSystemDoubles(n);
+    std::vector<double> sys(per * (size_t)B);
+    for (int b = 0; b < B; ++b) {
+        double* s = sys.data() + per * (size_t)b;
+        for (int i = 0; i < n; ++i) {
+            for (int j = 0; j < n; ++j) {
+                s[(size_t)j * n + i] = G[nn * b + (size_t)i * n + j];
+                s[nn + (size_t)j * n + i] = Cm[nn * b + (size_t)i * n + j];
+            }
+            s[2 * nn + i] = J[((size_t)b * n + i) * 2];
+            s[2 * nn + n + i] = J[((size_t)b * n + i) * 2 + 1];
+        }
+    }
+    const size_t outDoubles = (size_t)2 * F * n * B;
+    DevBuf dSys, dOmega, dOut, dF;
+    HIPCHK(dSys.alloc(sizeof(double) * sys.size()));
+    HIPCHK(dOmega.alloc(sizeof(double) * (size_t)F));
+    HIPCHK(dOut.alloc(sizeof(double) * outDoubles));
+    HIPCHK(dF.alloc(sizeof(uint32_t) * (size_t)B));
+    HIPCHK(hipMemcpy(dSys.p, sys.data(), sizeof(double) * sys.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dOmega.p, omega, sizeof(double) * (size_t)F, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(dOut.p, 0, sizeof(double) * outDoubles));
+    HIPCHK(hipMemset(dF.p, 0, sizeof(uint32_t) * (size_t)B));
+    HIPCHK(csim::launchAcSweep(which, n, dSys.as<double>(), dOmega.as<double>(), F, nullptr, n, B, 0, B, 1e-15,
+                               dOut.as<double>(), dF.as<uint32_t>(), nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<double> h(outDoubles);                       // [F][n][B] -> [B][F][n]
+    HIPCHK(hipMemcpy(h.data(), dOut.p, sizeof(double) * outDoubles, hipMemcpyDeviceToHost));
+    for (int f = 0; f < F; ++f)
+        for (int p = 0; p < n; ++p)
+            for (int b = 0; b < B; ++b) {
+                const size_t src = (((size_t)f * n + p) * B + b) * 2;
+                const size_t dst = (((size_t)b * F + f) * n + p) * 2;
+                x[dst] = h[src];
+                x[dst + 1] = h[src + 1];
+            }
     if (flags) HIPCHK(hipMemcpy(flags, dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
     return CSIM_OK;
 }

@@ -104,15 +104,18 @@ struct csim_engine {
     const int32_t *dGsRowPtr = nullptr, *dGsRowCol = nullptr;
 
     // AC analysis: the netlist's .AC card, the excitation per element (re, im; element order), and the sweep's
-    // device tables (uploaded on first use, cached by content) and per-chunk system scratch
+    // device tables (uploaded when they change, cached by content) and per-chunk system scratch
     int acEnabled = 0, acSweep = 0, acPoints = 0;
     double acFstart = 0.0, acFstop = 0.0;
     bool acAnySource = false;
     const double *dAcRe = nullptr, *dAcIm = nullptr;
-    double* dAcOmega = nullptr;
-    int acOmegaCap = 0;
+    // A sweep that is still enqueued reads the list it was launched with, so a changed list never overwrites the
+    // current one: it goes to a slot whose last reader has finished (`done`, recorded on the caller's stream
+    // after every sweep that uses the slot), or to a new one.
+    struct AcList { void* d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; };
+    std::vector<AcList> acOmegaSlots, acProbeSlots;
+    int acOmegaCur = -1, acProbeCur = -1;  // slot holding acOmegaCache / acProbeCache
     std::vector<double> acOmegaCache;
-    int32_t* dAcProbe = nullptr;
     std::vector<int32_t> acProbeCache;
     double* dAcSys = nullptr;
     int acSysCap = 0;                      // instances

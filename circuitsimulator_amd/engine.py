@@ -503,6 +503,23 @@ def lu_solve_batch(A, b, device=0):
     return x, flags
 
 
+def ac_solve_batch(G, Cm, J, omega, kernel="auto", device=0):
+    """Batched complex solve (G + j w C) x = J through the AC sweep kernels (csim_ac_solve_batch).
+    G, Cm [B][n][n] real, J [B][n] complex, omega [F] rad/s; kernel auto | wave | packed.
+    -> (x complex128 [B][F][n], flags [B])"""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    Cm = np.ascontiguousarray(Cm, dtype=np.float64)
+    J = np.ascontiguousarray(J, dtype=np.complex128)
+    omega = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
+    B, n = J.shape
+    x = np.zeros((B, len(omega), n), dtype=np.complex128)
+    flags = np.zeros(B, dtype=np.uint32)
+    capi.check(capi.lib().csim_ac_solve_batch(device, n, B, G.ctypes.data, Cm.ctypes.data, J.ctypes.data,
+                                              omega.ctypes.data, len(omega), ("auto", "wave", "packed").index(kernel),
+                                              x.ctypes.data, flags.ctypes.data))
+    return x, flags
+
+
 def gs_solve_batch(A, b, x0=None, max_iters=1000, tol=1e-10, device=0):
     """Batched Solver::solveLinearSystemGaussSeidel on the GPU.  A [B][n][n], b/x0 [B][n] -> (x [B][n], sweeps [B])."""
     A = np.ascontiguousarray(A, dtype=np.float64)

@@ -278,7 +278,9 @@ int64_t csim_tran_num_steps(double tstep, double tstop);
  * CSIM_ERR_CONFIG.                                                                                              */
 int64_t csim_ac_num_freqs(int32_t sweep, int32_t n_points, double fstart, double fstop);   /* < 0: error */
 int  csim_ac_freqs(int32_t sweep, int32_t n_points, double fstart, double fstop, double* f);
-/* Enqueues the sweep; never waits (a new frequency or probe list is uploaded once, synchronously, then cached).
+/* Enqueues the sweep; never waits for it.  A new frequency or probe list is uploaded once (a synchronous copy into
+ * a buffer that no sweep still enqueued reads, so calls may follow each other on a stream without a
+ * synchronisation in between), then cached.
  *   d_xop    [N][B] operating points (csim_dc_batch_dev)     freqs   host [F], Hz
  *   probe_eq host, NULL = every unknown (n_probe ignored)    d_out   [F][n_probe][B] complex (re, im) pairs
  *   d_status [B], OR-ed
@@ -304,6 +306,15 @@ int  csim_ac_system_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int
  * n <= 63 runs LDS-resident, 64 <= n <= 1024 in place in global memory.       */
 int  csim_lu_solve_batch(int32_t device, int32_t n, int32_t B, const double* A,
                          const double* b, double* x, uint32_t* flags);
+/* The complex counterpart: B systems (G + j w C) x = J at F angular frequencies through the AC sweep kernels of
+ * "AC analysis" above (same pivot rule, multiplier, order; lu_eps = 1e-15), without an engine or a netlist.
+ * Host pointers.  G, C [B][n][n] row-major; J [B][n] complex (re, im) pairs; omega [F] rad/s, used as given;
+ * x [B][F][n] complex pairs (the zero vector where the factorisation fails); flags [B] optional (CSIM_ST_LU_*).
+ * kernel: 0 auto (packed for n <= 32), 1 wave (n <= 63), 2 packed (n <= 32); a size beyond the kernel:
+ * CSIM_ERR_UNSUPPORTED.  n, B or F == 0: nothing to do.                                                        */
+int  csim_ac_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* C,
+                         const double* J, const double* omega, int32_t F, int32_t kernel,
+                         double* x, uint32_t* flags);
 
 /* ---- Gauss-Seidel variant of the reference (never reached from its main(), kept as public API) ----
  * Batched Solver::solveLinearSystemGaussSeidel (include/solver.hpp:139-204): sweeps in row order with the

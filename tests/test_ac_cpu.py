@@ -125,10 +125,39 @@ def test_grid_errors(args):
 # ---- the complex LU core, compiled for the host
 HOST_DRIVER = r"""
 #include <cstdio>
+#include <string>
 #include <vector>
 #include "ac_lu.hpp"
-int main()
+// "sweep": binary records on stdin -- int32 n, F; G [n][n], C [n][n] row-major; J re [n], J im [n]; omega [F] --
+// solved at every omega as (G + j w C) x = J; one line of flags and %a values per frequency
+static int sweep()
 {
+    int32_t hd[2];
+    while (std::fread(hd, sizeof(int32_t), 2, stdin) == 2) {
+        const int n = hd[0], F = hd[1], ld = n + 1;
+        std::vector<double> G(n * n), C(n * n), J(2 * n), om(F), ar(n * ld), ai(n * ld), xr(n), xi(n);
+        if (std::fread(G.data(), sizeof(double), G.size(), stdin) != G.size()) return 1;
+        if (std::fread(C.data(), sizeof(double), C.size(), stdin) != C.size()) return 1;
+        if (std::fread(J.data(), sizeof(double), J.size(), stdin) != J.size()) return 1;
+        if (std::fread(om.data(), sizeof(double), om.size(), stdin) != om.size()) return 1;
+        for (int f = 0; f < F; ++f) {
+            for (int i = 0; i < n; ++i) {
+                for (int j = 0; j < n; ++j) { ar[i * ld + j] = G[i * n + j]; ai[i * ld + j] = om[f] * C[i * n + j]; }
+                ar[i * ld + n] = J[i];
+                ai[i * ld + n] = J[n + i];
+            }
+            const unsigned fl = csim::ac_lu_solve(n, ld, ar.data(), ai.data(), 1e-15, xr.data(), xi.data());
+            std::printf("%u", fl);
+            for (int i = 0; i < n; ++i) std::printf(" %a %a", xr[i], xi[i]);
+            std::printf("\n");
+        }
+    }
+    return 0;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc > 1 && std::string(argv[1]) == "sweep") return sweep();
     int n;
     while (std::scanf("%d", &n) == 1) {
         const int ld = n + 1;
@@ -170,6 +199,30 @@ def host_lu(tmp_path_factory):
             v = np.array([float.fromhex(t) for t in tok[1:]])
             res.append((int(tok[0]), v[0::2] + 1j * v[1::2]))
         return res
+
+    def sweep(systems, omega):
+        """systems: list of (G [n][n], C [n][n], J complex [n]) -> per system (flags [F], x complex [F][n]),
+        values exactly as printed (%a)"""
+        omega = np.ascontiguousarray(omega, dtype=np.float64)
+        blob = b"".join(np.array([len(J), len(omega)], dtype=np.int32).tobytes()
+                        + np.ascontiguousarray(G, dtype=np.float64).tobytes()
+                        + np.ascontiguousarray(Cm, dtype=np.float64).tobytes()
+                        + np.ascontiguousarray(J.real).tobytes() + np.ascontiguousarray(J.imag).tobytes()
+                        + omega.tobytes() for G, Cm, J in systems)
+        out = subprocess.run([str(exe), "sweep"], input=blob, capture_output=True, check=True).stdout.decode()
+        lines = out.splitlines()
+        assert len(lines) == len(systems) * len(omega)
+        res = []
+        for s, (_, _, J) in enumerate(systems):
+            fl, x = [], np.zeros((len(omega), len(J)), dtype=complex)
+            for f in range(len(omega)):
+                tok = lines[s * len(omega) + f].split()
+                v = np.array([float.fromhex(t) for t in tok[1:]])
+                fl.append(int(tok[0]))
+                x[f].real, x[f].imag = v[0::2], v[1::2]
+            res.append((fl, x))
+        return res
+    run.sweep = sweep
     return run
 
 
@@ -201,6 +254,70 @@ def test_host_lu_pivoting_rules(host_lu):
     A = np.array([[1e-3 + 1e-6 + 1j * w * 1e-9, 1], [1, 0]], dtype=complex)
     (fl, x), = host_lu([(A, np.array([0, 1], dtype=complex))])
     assert fl == 0 and x[0] == 1 and abs(x[1] + (1e-3 + 1e-6 + 1j * w * 1e-9)) < 1e-18
+
+
+def test_reference_equals_host_lu_on_kernel_inputs(host_lu):
+    """tests/ac_reference.py (the specification restated in numpy) against ac_lu_solve() on every input of the GPU
+    kernel tests (tests/ac_cases.py): flags equal, x equal bit for bit (NaN masks equal where NaNs are expected).
+
+    And a condition on the inputs: on every solve that is neither flagged nor fed a NaN, the reference's normwise
+    backward error, evaluated in numpy.longdouble, stays below 8 n 2^-53.  Random inputs sit near 0.3 n 2^-53;
+    the bound leaves the structured inputs about 25 times that.  An input that misses it is to be replaced, the
+    bound stays.  The structured kinds are also checked to do what they are named after."""
+    import ac_cases as cs
+    import ac_reference as ref
+    cov = cs.Coverage()
+    worst = (0.0, None)
+    n_solves = n_swaps = 0
+    for n in cs.SIZES:
+        cases = list(cs.all_cases(sizes=(n,)))
+        assert {c["kind"] for c in cases} >= set(cs.KINDS) - ({"tie_diag", "nan_below"} if n < 2 else set()) \
+            - ({"tie_rows"} if n < 3 else set())
+        host = host_lu.sweep([(c["G"][s], c["C"][s], c["J"][s]) for c in cases for s in range(cs.NSYS)], cs.OMEGA)
+        for ci, c in enumerate(cases):
+            kind = c["kind"]
+            flags, x, per_f, logs = cs.reference(c)
+            for s in range(cs.NSYS):
+                hfl, hx = host[ci * cs.NSYS + s]
+                where = (kind, n, s)
+                assert hfl == per_f[s], where
+                nan = np.isnan(x[s].view(np.float64))
+                assert np.array_equal(nan, np.isnan(hx.view(np.float64))), where
+                assert nan.any() == (kind in cs.HAS_NAN), where
+                assert np.array_equal(np.where(nan, 0, x[s].view(np.uint64)), np.where(nan, 0, hx.view(np.uint64))), where
+                cov.add(n, logs[s])
+                n_swaps += sum(g.swaps for g in logs[s])
+                # the kinds do what they say
+                if kind in cs.SINGULAR:
+                    assert per_f[s] == [4, 4, 4] and np.all(x[s] == 0), where
+                    at = {"sing_first": 0, "sing_mid": n // 2, "sing_last": n - 1}.get(kind)
+                    assert at is None or [g.failed_at for g in logs[s]] == [at] * 3, where
+                elif kind in ("sing_dc_only", "thr_both"):
+                    assert per_f[s] == [0, 4, 0] and int(flags[s]) == 4, where
+                    assert np.all(x[s, 1] == 0) and np.all(x[s, 0] != 0) and np.all(x[s, 2] != 0), where
+                else:
+                    assert per_f[s] == [0, 0, 0], where
+                if kind in ("tie_diag", "tie_rows"):
+                    assert logs[s][0].ties >= 1, where
+                if kind == "mna" and n >= 8:
+                    assert np.mean(c["G"][s] == 0) >= 0.6 and np.mean(c["C"][s] == 0) >= 0.6, where
+                    assert logs[s][0].skips > 0, where
+                if kind in cs.HAS_NAN:
+                    continue
+                for f, w in enumerate(cs.OMEGA):
+                    if per_f[s][f]:
+                        continue
+                    A = np.empty((n, n), dtype=complex)
+                    A.real, A.imag = c["G"][s], w * c["C"][s]
+                    be = ref.backward_error(A, x[s, f], c["J"][s]) / (n * 2.0 ** -53)
+                    n_solves += 1
+                    if be > worst[0]:
+                        worst = (be, where + (f,))
+                    assert be < 8.0, (be, where, f)
+    print("reference == ac_lu_solve() on %d unflagged NaN-free solves, %d row swaps; worst backward error "
+          "%.3f n 2^-53 at %s" % (n_solves, n_swaps, worst[0], worst[1]))
+    print("coverage:", cov)
+    cov.check()
 
 
 def test_packed_ac_kernel_registers(tmp_path):

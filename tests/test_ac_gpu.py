@@ -252,3 +252,257 @@ def test_singular_instance_flagged_others_unchanged():
     keep = [0, 2, 3]
     assert np.array_equal(out[keep], ref) and np.array_equal(st[keep], st_ref)
     assert int(st_ref.max()) & 0x4 == 0
+
+
+# ---- instance chunking, the frequency / probe caches, stream order, excitation, sizes, layout
+def _ac_chunk(N):
+    """instances per chunk of csim_ac_batch_dev: 256 MiB of system scratch (engine.cpp acChunk)"""
+    return max(256, (256 << 20) // (8 * (2 * N * N + 2 * N)))
+
+
+def _u64(t):
+    """device complex tensor or numpy complex array -> its bit pattern, shape + (2,)"""
+    a = np.ascontiguousarray(t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t), dtype=np.complex128)
+    return a.view(np.uint64).reshape(a.shape + (2,))
+
+
+def _spread_params(nl, B, seed):
+    """[P][B]: the nominal parameters, every one scaled by its own factor in 1 +- 5 % per instance"""
+    rng = np.random.default_rng(seed)
+    return nl.nominal_params[:, None] * (1.0 + 0.05 * rng.uniform(-1.0, 1.0, (nl.n_params, B)))
+
+
+def _ladder_text(N):
+    """RC ladder with N unknowns: N - 2 sections, nodes n0 .. n<N-2>, and the source's branch current"""
+    S = N - 2
+    lines = ["* RC ladder of %d sections" % S, "V1 n0 0 AC 1 0"]
+    for k in range(1, S + 1):
+        lines += ["R%d n%d n%d 10" % (k, k - 1, k), "C%d n%d 0 1p" % (k, k)]
+    return "\n".join(lines) + "\n"
+
+
+def _ladder_closed_form(S, f, upto):
+    """V(n<upto>) / V(n0) of the S-section ladder, the continued fraction of test_rc_ladder_wave_kernel"""
+    w = 2.0 * PI * f
+    R, Cv = 10.0, 1e-12
+    ysub = GMIN + 1j * w * Cv
+    ratios = [1.0 / (1.0 + R * ysub)]
+    for _ in range(S - 1):
+        ysub = GMIN + 1j * w * Cv + 1.0 / (R + 1.0 / ysub)
+        ratios.append(1.0 / (1.0 + R * ysub))
+    ratios = ratios[::-1]
+    return np.prod(ratios[:upto], axis=0)
+
+
+def _chunking(nl, eng, params, B, freqs, probes):
+    import torch
+    N = nl.n_unknowns
+    chunk = _ac_chunk(N)
+    assert chunk < B - 1 and B - chunk < chunk          # two chunks, the second one short
+    assert (B - chunk) % 2 == 1                         # and odd: the last packed wavefront is half empty
+    x, _, _ = eng.dc(params)
+    out, st = eng.ac(params, x, freqs=freqs, probes=probes)
+    torch.cuda.synchronize()
+    assert tuple(out.shape) == (len(freqs), len(probes), B)
+    full, fst = _u64(out), st.cpu().numpy()
+    assert not np.array_equal(full[:, :, 0], full[:, :, chunk]) and not np.array_equal(full[:, :, chunk], full[:, :, B - 1])
+    pick = [0, chunk - 1, chunk, chunk + 1, B - 1]
+    idx = torch.tensor(pick, device=params.device)
+    o5, s5 = eng.ac(params[:, idx].contiguous(), x[:, idx].contiguous(), freqs=freqs, probes=probes)
+    assert np.array_equal(_u64(o5), full[:, :, pick])
+    assert np.array_equal(s5.cpu().numpy(), fst[pick])
+    h = B // 2
+    halves = [eng.ac(params[:, a:b].contiguous(), x[:, a:b].contiguous(), freqs=freqs, probes=probes)
+              for a, b in ((0, h), (h, B))]
+    assert h < chunk and B - h < chunk                  # neither half is chunked
+    assert np.array_equal(np.concatenate([_u64(o) for o, _ in halves], axis=2), full)
+    assert np.array_equal(np.concatenate([s.cpu().numpy() for _, s in halves]), fst)
+
+
+def test_chunked_batch_packed_kernel():
+    """dbmixer (N = 31): 16 912 instances fill the system scratch; 89 more make a second, odd chunk at b0 > 0"""
+    from circuitsimulator_amd import Engine
+    nl = _with_ac("dbmixer.sp", "Vrf1+ 112 212 SIN")
+    assert nl.n_unknowns == 31 and _ac_chunk(31) == 16912
+    eng = Engine(nl, 0)
+    B = 16912 + 89
+    params = eng.mc_params(12345, 0.05, 0, B)
+    _chunking(nl, eng, params, B, [1e5, 1e9], [nl.n_unknowns - 1, 3])
+
+
+def test_chunked_batch_wave_kernel():
+    """the RC ladder (N = 42): 9 289 instances per chunk, 7 in the second"""
+    from circuitsimulator_amd import Engine
+    nl = _nl("ac_rc_ladder.sp")
+    assert nl.n_unknowns == 42 and _ac_chunk(42) == 9289
+    eng = Engine(nl, 0)
+    B = 9289 + 7
+    params = eng.upload_params(_spread_params(nl, B, 42))
+    _chunking(nl, eng, params, B, [1e6, 1e9], [nl.node_eq("n40"), nl.node_eq("n20")])
+
+
+def test_frequency_and_probe_caches():
+    """one engine, changing frequency lists (shorter, the first again, longer than ever) and probe lists: every
+    result equals a fresh engine's"""
+    from circuitsimulator_amd import Engine
+    nl = _with_ac("buffer.sp", "Vin 101 0 SIN")
+    B = 8
+    fa = np.array([1e3, 1e5, 1e7, 1e8, 1e9])
+    fb = np.array([2e4, 3e6, 4e8])
+    fl = np.array([1e3 * 7.0 ** k for k in range(9)])
+
+    def run(eng, f, probes):
+        params = eng.mc_params(777, 0.05, 0, B)
+        x, _, _ = eng.dc(params)
+        out, st = eng.ac(params, x, freqs=f, probes=probes)
+        return _u64(out), st.cpu().numpy()
+    eng = Engine(nl, 0)
+    for f, probes in ((fa, [3, 1]), (fb, [3, 1]), (fb, None), (fa, None), (fa, [1]), (fl, [1]), (fb, [3, 1]), (fl, None)):
+        got = run(eng, f, probes)
+        want = run(Engine(nl, 0), f, probes)
+        assert got[0].shape == (len(f), nl.n_unknowns if probes is None else len(probes), B, 2)
+        assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), (len(f), probes)
+
+
+def test_two_sweeps_back_to_back_on_a_stream():
+    """csim_ac_batch_dev enqueues and never waits: two sweeps on a non-blocking stream with nothing between them --
+    frequency lists of equal length and different values, different probe lists -- then one synchronise.  Both
+    results equal those of the same calls each followed by a synchronise.  (With the second list copied over the
+    buffer the first sweep was still reading, 1 155 072 of the first sweep's 1 163 264 values came out wrong.)"""
+    import torch
+    from circuitsimulator_amd import Engine
+    nl = _with_ac("dbmixer.sp", "Vrf1+ 112 212 SIN")
+    eng = Engine(nl, 0)
+    B = 4096
+    params = eng.mc_params(2024, 0.05, 0, B)
+    x, _, _ = eng.dc(params)
+    f1 = np.array([1e3 * math.pow(10.0, k / 10) for k in range(71)])
+    f2 = f1[::-1] * 3.0
+    p1, p2 = [30, 5], [7, 12, 0]
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        a1, st1 = eng.ac(params, x, freqs=f1, probes=p1)
+        a2, st2 = eng.ac(params, x, freqs=f2, probes=p2)
+        s.synchronize()
+        r1, rs1 = eng.ac(params, x, freqs=f1, probes=p1)
+        s.synchronize()
+        r2, rs2 = eng.ac(params, x, freqs=f2, probes=p2)
+        s.synchronize()
+    torch.cuda.synchronize()
+    bad1 = int(np.count_nonzero(_u64(a1) != _u64(r1)))
+    bad2 = int(np.count_nonzero(_u64(a2) != _u64(r2)))
+    print("back-to-back sweeps: %d of %d values of the first, %d of %d of the second differ from the synchronised runs"
+          % (bad1, _u64(r1).size, bad2, _u64(r2).size))
+    assert bad1 == 0 and bad2 == 0
+    assert np.array_equal(st1.cpu().numpy(), rs1.cpu().numpy()) and np.array_equal(st2.cpu().numpy(), rs2.cpu().numpy())
+
+
+def test_current_source_phase_and_two_sources():
+    """I1 a 0 AC 2 30 into R || C, V2 b 0 AC 0.5 -90 through R2 to the same node: superposition, with the sign
+    convention of include/csim.h (a current source takes its value out of its first node)"""
+    import torch
+    from circuitsimulator_amd import Engine
+    nl = _nl("ac_isrc_phase.sp")
+    eng = Engine(nl, 0)
+    f = nl.ac_freqs()
+    assert len(f) == 21
+    a, b = nl.node_eq("a"), nl.node_eq("b")
+    k = [i for i in range(nl.n_unknowns) if i not in (a, b)]
+    assert len(k) == 1
+    out, st = eng.ac_host(B=1)
+    assert int(st[0]) == 0
+    w = 2.0 * PI * f
+    I1 = 2.0 * complex(math.cos(30.0 * PI / 180.0), math.sin(30.0 * PI / 180.0))
+    V2 = 0.5 * complex(math.cos(-90.0 * PI / 180.0), math.sin(-90.0 * PI / 180.0))
+    G1, G2 = 1.0 / 1e3, 1.0 / 2e3
+    Va = (G2 * V2 - I1) / (G1 + G2 + GMIN + 1j * w * 1e-9)
+    Ib = -(G2 * (V2 - Va) + GMIN * V2)
+    assert _rel(out[0, :, a], Va, 1e-300) <= 1e-12
+    assert _rel(out[0, :, b], np.full(len(f), V2), 1e-300) <= 1e-12
+    assert _rel(out[0, :, k[0]], Ib, 1e-300) <= 1e-12
+    params = eng.upload_params(nl.nominal_table(1))
+    x, _, _ = eng.dc(params)
+    _, _, J = eng.ac_system(params, x)
+    torch.cuda.synchronize()
+    Jn = _numpy_J(nl)
+    assert Jn[a] == -I1 and Jn[k[0]] == V2 and Jn[b] == 0
+    assert np.array_equal(J.cpu().numpy()[0], Jn)
+
+
+@pytest.mark.parametrize("N", [17, 24, 25, 32, 33, 63])
+def test_ladder_sizes_through_a_netlist(N):
+    from circuitsimulator_amd import CsimError, Engine, capi
+    nl = _nl(text=_ladder_text(N))
+    assert nl.n_unknowns == N
+    S = N - 2
+    mid = S // 2
+    f = np.array([1e3 * math.pow(10.0, k / 5) for k in range(26)])           # the grid of ac_rc_ladder.sp's card
+    probes = [nl.node_eq("n%d" % S), nl.node_eq("n%d" % mid)]
+    res = {}
+    for kern in ("auto", "wave", "packed"):
+        eng = Engine(nl, 0)
+        eng.set_option("ac_kernel", kern)
+        if kern == "packed" and N > 32:
+            with pytest.raises(CsimError) as e:
+                eng.ac_host(B=1, freqs=f, probes=probes)
+            assert e.value.code == capi.CSIM_ERR_UNSUPPORTED
+            continue
+        out, st = eng.ac_host(B=1, freqs=f, probes=probes)
+        assert int(st[0]) == 0
+        assert _rel(out[0, :, 0], _ladder_closed_form(S, f, S), 1e-300) <= 1e-12, kern
+        assert _rel(out[0, :, 1], _ladder_closed_form(S, f, mid), 1e-300) <= 1e-12, kern
+        res[kern] = out
+    assert np.array_equal(_u64(res["auto"]), _u64(res["packed" if N <= 32 else "wave"]))
+    if N <= 32:
+        assert np.array_equal(_u64(res["wave"]), _u64(res["packed"]))
+
+
+def test_sixty_four_unknowns_and_no_ac_source_are_refused():
+    from circuitsimulator_amd import CsimError, Engine, capi
+    nl = _nl(text=_ladder_text(64))
+    assert nl.n_unknowns == 64
+    with pytest.raises(CsimError) as e:
+        Engine(nl, 0).ac_host(B=1, freqs=[1e6])
+    assert e.value.code == capi.CSIM_ERR_UNSUPPORTED
+    quiet = _nl(text=_ladder_text(10).replace("V1 n0 0 AC 1 0", "V1 n0 0 DC 1"))
+    with pytest.raises(CsimError) as e:
+        Engine(quiet, 0).ac_host(B=1, freqs=[1e6])
+    assert e.value.code == capi.CSIM_ERR_CONFIG
+
+
+def test_host_layout_and_status_is_ored():
+    """csim_ac_batch returns [B][F][n_probe]; the device form [F][n_probe][B] -- with B = 3, F = 4 and two probes a
+    swapped index shows.  d_status is OR-ed: bits set before the call stay."""
+    import torch
+    from circuitsimulator_amd import Engine
+    nl = _nl("ac_rlc_series.sp")
+    eng = Engine(nl, 0)
+    slotL = [s for kind, q, k, s in _records(nl) if kind == 2][0]
+    table = np.repeat(nl.nominal_params[None, :], 3, axis=0)
+    table[1, slotL - 1], table[2, slotL - 1] = 75.0, 120.0
+    f = [1e6, 3e6, 5e6, 9e6]
+    probes = [nl.node_eq("b"), nl.node_eq("a")]
+    host, hst = eng.ac_host(params=table, freqs=f, probes=probes)
+    assert host.shape == (3, 4, 2)
+    params = eng.upload_params(table.T)
+    x, _, _ = eng.dc(params)
+    dev, dst = eng.ac(params, x, freqs=f, probes=probes)
+    torch.cuda.synchronize()
+    dev = dev.cpu().numpy()
+    assert dev.shape == (4, 2, 3)
+    assert len({dev[i, j, b] for i in range(4) for j in range(2) for b in range(3)}) == 24
+    assert np.array_equal(_u64(host), _u64(np.transpose(dev, (2, 0, 1))))
+    assert np.array_equal(hst, dst.cpu().numpy().astype(np.uint32))
+    # one singular instance (L = 0), bit 0x20 preset on it and on a regular one
+    bad = np.insert(table, 1, table[0], axis=0)
+    bad[1, slotL] = 0.0
+    params = eng.upload_params(bad.T)
+    x, _, _ = eng.dc(params)
+    st = torch.tensor([0, 0x20, 0, 0x20], dtype=torch.int32, device=params.device)
+    out, st2 = eng.ac(params, x, freqs=f, probes=probes, status=st)
+    torch.cuda.synchronize()
+    assert st2 is st and st.tolist() == [0, 0x24, 0, 0x20]
+    out = out.cpu().numpy()
+    assert np.all(out[:, :, 1] == 0)
+    assert np.array_equal(_u64(out[:, :, [0, 2, 3]]), _u64(dev))

@@ -40,12 +40,15 @@ def test_ir_struct_layout_matches_header(buffer_nl):
 
 @pytest.mark.skipif(has_gpu(), reason="checks the no-GPU behaviour")
 def test_engine_refuses_without_gpu(buffer_nl):
-    from circuitsimulator_amd import Engine, lu_solve_batch
+    from circuitsimulator_amd import Engine, ac_solve_batch, lu_solve_batch
     with pytest.raises(CsimError) as e:
         Engine(buffer_nl, 0)
     assert e.value.code == capi.CSIM_ERR_NO_DEVICE
     with pytest.raises(CsimError) as e:
         lu_solve_batch(np.eye(2)[None], np.ones((1, 2)))
+    assert e.value.code == capi.CSIM_ERR_NO_DEVICE
+    with pytest.raises(CsimError) as e:
+        ac_solve_batch(np.eye(2)[None], np.zeros((1, 2, 2)), np.ones((1, 2), dtype=complex), [0.0, 1.0])
     assert e.value.code == capi.CSIM_ERR_NO_DEVICE
 
 
