@@ -57,6 +57,13 @@ PROTOTYPES = {
     "csim_netlist_mc_kinds": (C.c_int, [_vp, _vp]),
     "csim_netlist_ac": (C.c_int, [_vp, _pi32, _pi32, _pi32, _pdbl, _pdbl]),
     "csim_netlist_ac_source": (C.c_int, [_vp, _i32, _pdbl, _pdbl]),
+    "csim_netlist_noise": (C.c_int, [_vp, _pi32, _pi32, _pi32, _pi32, _pi32, _pi32, _pdbl, _pdbl]),
+    "csim_netlist_num_noise_sources": (C.c_int, [_vp]),
+    "csim_netlist_noise_source": (C.c_int, [_vp, _i32, _pi32, _pi32, _pi32]),
+    "csim_noise_batch_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "csim_noise_batch": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _vp, _vp]),
+    "csim_noise_solve_batch": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32,
+                                         _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "csim_ac_num_freqs": (_i64, [_i32, _i32, _dbl, _dbl]),
     "csim_ac_freqs": (C.c_int, [_i32, _i32, _dbl, _dbl, _vp]),
     "csim_ac_batch_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),

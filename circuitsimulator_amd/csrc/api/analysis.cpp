@@ -84,6 +84,25 @@ BatchAcResult BatchEngine::ac(const std::vector<double>& params, int B, const st
     return r;
 }
 
+BatchNoiseResult BatchEngine::noise(const std::vector<double>& params, int B, const std::vector<double>& freqs, int outP,
+                                    int outM, int srcElem, double tempK, bool wantContrib)
+{
+    BatchNoiseResult r;
+    r.freqs = freqs;
+    r.nSources = csim_netlist_num_noise_sources(nl_);
+    const std::size_t FB = static_cast<std::size_t>(B) * freqs.size();
+    r.onoise.assign(FB, 0.0);
+    if (srcElem >= 0) r.gain.assign(FB, std::complex<double>());
+    if (wantContrib) r.contrib.assign(FB * static_cast<std::size_t>(r.nSources), 0.0);
+    r.status.assign(static_cast<std::size_t>(B), 0);
+    if (csim_noise_batch(eng_, params.empty() ? nullptr : params.data(), B, freqs.data(), static_cast<int>(freqs.size()),
+                         outP, outM, srcElem, tempK, r.onoise.data(),
+                         srcElem >= 0 ? reinterpret_cast<double*>(r.gain.data()) : nullptr,
+                         wantContrib ? r.contrib.data() : nullptr, nullptr, r.status.data()) != CSIM_OK)
+        fail("csim_noise_batch");
+    return r;
+}
+
 BatchTranResult BatchEngine::tran(const std::vector<double>& params, int B, double tstep, double tstop,
                                   double tstart, const std::vector<int32_t>& probeEq, int outStride)
 {

@@ -41,6 +41,15 @@ struct BatchAcResult {
     std::vector<uint32_t> status;                 // DC and AC bits (CSIM_ST_LU_TINY_PIVOT: a singular frequency)
 };
 
+struct BatchNoiseResult {
+    std::vector<double> freqs;                    // [F] Hz
+    int nSources = 0;                             // S noise generators (csim_netlist_noise_source order)
+    std::vector<double> onoise;                   // [B][F] output noise PSD, V^2/Hz
+    std::vector<std::complex<double>> gain;       // [B][F] input source -> output (empty without a source)
+    std::vector<double> contrib;                  // [B][F][S] (empty unless asked for)
+    std::vector<uint32_t> status;                 // DC and LU bits (CSIM_ST_LU_TINY_PIVOT: a singular frequency)
+};
+
 // One engine per (circuit, GPU).  Throws std::runtime_error when no HIP
 // device is usable: there is no CPU path.
 class BatchEngine {
@@ -67,6 +76,11 @@ public:
     // frequency of freqs (Hz); probeEq empty = every unknown.
     BatchAcResult ac(const std::vector<double>& params, int B, const std::vector<double>& freqs,
                      const std::vector<int32_t>& probeEq = {});
+
+    // Small-signal noise (csim_noise_batch, include/csim.h): DC operating point, then one adjoint solve per frequency.
+    // Output V(outP) - V(outM) (equations; outM = -1: ground); srcElem: V/I element for the gain, -1 none.
+    BatchNoiseResult noise(const std::vector<double>& params, int B, const std::vector<double>& freqs, int outP,
+                           int outM = -1, int srcElem = -1, double tempK = 300.15, bool wantContrib = false);
 
     // the transient of instance `instance` of params ([B][P], empty = nominal) as the reference's CSV
     // (src/tanalisis.cpp:189-231); probeEq empty: the netlist's .PLOTNV/.PRINT probes when `sim` names any, else

@@ -3,7 +3,7 @@
 //   whose first non-blank is '*' or ';' is a comment; a leading '+' continues
 //   the previous logical line; tokens split on blanks.
 //   Devices by first letter (any case): R C L V I M.   Cards: .MODEL (read in
-//   a first pass, so it may follow its users) .TRAN .OP .DC .AC .HB .PRINT
+//   a first pass, so it may follow its users) .TRAN .OP .DC .AC .NOISE .HB .PRINT
 //   .PLOTNV .PLOTNC; anything else is reported and skipped.
 #include "parser.hpp"
 
@@ -378,6 +378,7 @@ void NetlistParser::dotCard(const Statement& st)
     else if (head == ".dc")     dcCard(st);
     else if (head == ".tran")   tranCard(st);
     else if (head == ".ac")     acCard(st);
+    else if (head == ".noise")  noiseCard(st);
     else if (head == ".print")  printCard(st);
     else if (head == ".model")  modelCard(st);
     else if (head == ".hb")     hbCard(st);
@@ -452,6 +453,47 @@ void NetlistParser::acCard(const Statement& st)
     }
     cfg.enabled = true;
     sim.ac = cfg;
+}
+
+// .NOISE V(out[,ref]) [src] {LIN|DEC|OCT} npoints fstart fstop
+void NetlistParser::noiseCard(const Statement& st)
+{
+    // the output may be written with blanks inside its parentheses: join tokens up to the closing one
+    std::vector<std::string> t;
+    for (std::size_t i = 0; i < st.tokens.size(); ++i) {
+        if (i >= 2 && t.size() == 2 && t[1].find('(') != std::string::npos && t[1].find(')') == std::string::npos)
+            t[1] += st.tokens[i];
+        else
+            t.push_back(st.tokens[i]);
+    }
+    auto isSweep = [](const std::string& s) { const std::string l = toLower(s); return l == "dec" || l == "oct" || l == "lin"; };
+    const std::size_t at = t.size() > 2 && isSweep(t[2]) ? 2 : 3;      // the source may be left out
+    if (t.size() < at + 4 || !isSweep(t[at])) {
+        std::cerr << "Line " << st.lineNo << ": invalid .NOISE syntax: " << st.raw << "\n";
+        return;
+    }
+    const ProbeSpec out = probeFromToken(t[1]);
+    if ((out.kind != ProbeKind::NodeVoltage && out.kind != ProbeKind::DiffVoltage) || out.node1.empty()) {
+        std::cerr << "Line " << st.lineNo << ": .NOISE output must be V(node) or V(node,ref): " << st.raw << "\n";
+        return;
+    }
+    NoiseConfig cfg;
+    cfg.outNode = out.node1;
+    cfg.refNode = out.node2;
+    if (at == 3) cfg.srcName = t[2];
+    const std::string sweep = toLower(t[at]);
+    cfg.sweepType = sweep == "lin" ? AcSweepType::LIN : (sweep == "oct" ? AcSweepType::OCT : AcSweepType::DEC);
+    try {
+        cfg.nPoints = std::stoi(t[at + 1]);
+        cfg.fstart  = parseSpiceNumber(t[at + 2]);
+        cfg.fstop   = parseSpiceNumber(t[at + 3]);
+    } catch (const std::exception& e) {
+        std::cerr << "Line " << st.lineNo << ": cannot parse .NOISE arguments: " << e.what()
+                  << " in '" << st.raw << "'\n";
+        return;
+    }
+    cfg.enabled = true;
+    sim.noise = cfg;
 }
 
 // .HB f0 nharm

@@ -144,6 +144,16 @@ struct AcConfig {
     double fstart = 0.0, fstop = 0.0;
 };
 
+// .NOISE V(out[,ref]) [src] {DEC|OCT|LIN} n fstart fstop -- names as written; netlist_capi.cpp resolves them
+struct NoiseConfig {
+    bool enabled = false;
+    std::string outNode, refNode;   // refNode empty or "0": ground
+    std::string srcName;            // input source for the gain, empty: none
+    AcSweepType sweepType = AcSweepType::DEC;
+    int nPoints = 0;
+    double fstart = 0.0, fstop = 0.0;
+};
+
 struct HbConfig {
     bool enabled = false;
     double f0 = 0.0;
@@ -168,6 +178,7 @@ public:
     std::vector<DCSweepConfig> dcSweeps;
     TranConfig tran;
     AcConfig ac;
+    NoiseConfig noise;
     HbConfig hb;
     std::vector<PrintCommand> printCommands;
 

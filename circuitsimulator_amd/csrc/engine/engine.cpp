@@ -14,6 +14,7 @@
 #include <utility>
 #include <vector>
 
+#include "ac_noise.hpp"
 #include "codegen.hpp"
 #include "csim.h"
 #include "engine_internal.hpp"
@@ -296,6 +297,24 @@ int csim_engine_create(const csim_netlist* nl, int32_t device, csim_engine** out
         eng->acFstart = a.fstart;
         eng->acFstop = a.fstop;
     }
+    if (!rc) {
+        const std::vector<csim::NoiseSource> src = csim::noiseSources(c);
+        std::vector<int32_t> el, ta, tb;
+        for (const csim::NoiseSource& g : src) { el.push_back(g.elem); ta.push_back(g.a); tb.push_back(g.b); }
+        eng->nNoiseSrc = static_cast<int>(src.size());
+        rc = upload(eng, el, &eng->dNoiseElem);
+        if (!rc) rc = upload(eng, ta, &eng->dNoiseA);
+        if (!rc) rc = upload(eng, tb, &eng->dNoiseB);
+        const NoiseConfig& nc = nl->sim.noise;
+        eng->noiseEnabled = nc.enabled ? 1 : 0;
+        eng->noiseOutP = nl->noiseOutP;
+        eng->noiseOutM = nl->noiseOutM;
+        eng->noiseSrcElem = nl->noiseSrcElem;
+        eng->noiseSweep = nc.sweepType == AcSweepType::DEC ? 0 : (nc.sweepType == AcSweepType::OCT ? 1 : 2);
+        eng->noisePoints = nc.nPoints;
+        eng->noiseFstart = nc.fstart;
+        eng->noiseFstop = nc.fstop;
+    }
     if (!rc) rc = fillGenPlan(eng, eng->plan.dc, eng->gpDc);
     if (!rc) rc = fillGenPlan(eng, eng->plan.tran, eng->gpTran);
     if (rc) { csim_engine_destroy(eng); return rc; }
@@ -326,6 +345,7 @@ void csim_engine_destroy(csim_engine* eng)
             if (s.d) (void)hipFree(s.d);
         }
     if (eng->dAcSys) (void)hipFree(eng->dAcSys);
+    if (eng->dNoisePsd) (void)hipFree(eng->dNoisePsd);
     if (eng->schedLib) dlclose(eng->schedLib);
     delete eng;
 }
@@ -843,6 +863,32 @@ static int acUpload(std::vector<csim_engine::AcList>& ring, int& cur, const void
     return CSIM_OK;
 }
 
+// w = 2 pi f of a sweep's frequency list on the device: uploaded when the list changes, cached otherwise
+static int acOmega(csim_engine* eng, const double* freqs, int F, const double** dOmega)
+{
+    std::vector<double> omega((size_t)F);
+    for (int f = 0; f < F; ++f) omega[(size_t)f] = 2.0 * eng->cir.ir.k.pi * freqs[f];
+    if (eng->acOmegaCur < 0 || omega != eng->acOmegaCache) {
+        eng->acOmegaCache.clear();
+        if (const int rc = acUpload(eng->acOmegaSlots, eng->acOmegaCur, omega.data(), sizeof(double) * (size_t)F)) return rc;
+        eng->acOmegaCache = omega;
+    }
+    *dOmega = static_cast<const double*>(eng->acOmegaSlots[(size_t)eng->acOmegaCur].d);
+    return CSIM_OK;
+}
+
+// the per-chunk system scratch, grown to `chunk` instances
+static int acSysScratch(csim_engine* eng, int chunk)
+{
+    if (eng->acSysCap >= chunk) return CSIM_OK;
+    if (eng->dAcSys) HIPCHK(hipFree(eng->dAcSys));
+    eng->dAcSys = nullptr;
+    eng->acSysCap = 0;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&eng->dAcSys), sizeof(double) * csim::acSystemDoubles(eng->plan.N) * (size_t)chunk));
+    eng->acSysCap = chunk;
+    return CSIM_OK;
+}
+
 int csim_ac_system_dev(csim_engine* eng, const double* d_params, int32_t B, const double* d_xop, double* d_sys, void* stream)
 {
     if (!eng || B < 0 || (B > 0 && (!d_params || !d_xop || !d_sys))) { setError("csim_ac_system_dev: bad argument"); return CSIM_ERR_ARG; }
@@ -877,14 +923,8 @@ int csim_ac_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const
     hipStream_t hs = static_cast<hipStream_t>(stream);
 
     // angular frequencies and the probe list: uploaded when they change, cached otherwise
-    std::vector<double> omega((size_t)F);
-    for (int f = 0; f < F; ++f) omega[(size_t)f] = 2.0 * eng->cir.ir.k.pi * freqs[f];
-    if (eng->acOmegaCur < 0 || omega != eng->acOmegaCache) {
-        eng->acOmegaCache.clear();
-        if (const int rc = acUpload(eng->acOmegaSlots, eng->acOmegaCur, omega.data(), sizeof(double) * (size_t)F)) return rc;
-        eng->acOmegaCache = omega;
-    }
-    const double* dOmega = static_cast<const double*>(eng->acOmegaSlots[(size_t)eng->acOmegaCur].d);
+    const double* dOmega = nullptr;
+    if (const int rc = acOmega(eng, freqs, F, &dOmega)) return rc;
     const int32_t* dProbe = nullptr;
     if (probe_eq) {
         std::vector<int32_t> want(probe_eq, probe_eq + n_probe);
@@ -896,13 +936,7 @@ int csim_ac_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const
         dProbe = static_cast<const int32_t*>(eng->acProbeSlots[(size_t)eng->acProbeCur].d);
     }
     const int chunk = acChunk(eng, B);
-    if (eng->acSysCap < chunk) {
-        if (eng->dAcSys) HIPCHK(hipFree(eng->dAcSys));
-        eng->dAcSys = nullptr;
-        eng->acSysCap = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&eng->dAcSys), sizeof(double) * csim::acSystemDoubles(N) * (size_t)chunk));
-        eng->acSysCap = chunk;
-    }
+    if (const int rc = acSysScratch(eng, chunk)) return rc;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int Bc = std::min(chunk, B - b0);
         HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, b0, Bc, d_xop, eng->dAcSys, hs));
@@ -960,6 +994,188 @@ int csim_ac_batch(csim_engine* eng, const double* params, int32_t B, const doubl
                 out[dst] = h[src];
                 out[dst + 1] = h[src + 1];
             }
+    return CSIM_OK;
+}
+
+// ---- noise analysis ---------------------------------------------------------
+
+// the netlist's .NOISE card as a frequency list
+static int noiseCardFreqs(const csim_engine* eng, std::vector<double>& card)
+{
+    if (!eng->noiseEnabled) { setError("noise analysis: no frequencies given and the netlist has no .NOISE card"); return CSIM_ERR_CONFIG; }
+    const int64_t n = csim_ac_num_freqs(eng->noiseSweep, eng->noisePoints, eng->noiseFstart, eng->noiseFstop);
+    if (n < 0) return static_cast<int>(n);
+    card.resize((size_t)n);
+    return csim_ac_freqs(eng->noiseSweep, eng->noisePoints, eng->noiseFstart, eng->noiseFstop, card.data());
+}
+
+// output pair, input source and temperature of a noise call -> the kernels' numbers
+static int noiseSetup(const csim_engine* eng, int out_p, int out_m, int src_elem, double temp_k, csim::NoiseArgs& a, double& kT4)
+{
+    const int N = eng->plan.N;
+    if (N > 63) { setError("noise analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
+    if (out_p < 0 || out_p >= N || out_m < -1 || out_m >= N || out_p == out_m) {
+        setError("noise analysis: the output needs two different equations, out_p >= 0 (out_m = -1: ground)");
+        return CSIM_ERR_ARG;
+    }
+    a.inKind = csim::NOISE_IN_NONE;
+    a.inA = a.inB = -1;
+    if (src_elem >= 0) {
+        const csim::CircuitIR& c = eng->cir;
+        if (src_elem >= c.ir.n_elems) { setError("noise analysis: bad input source element"); return CSIM_ERR_ARG; }
+        const int kind = c.kind[(size_t)src_elem];
+        if (kind == CSIM_V) {
+            a.inKind = csim::NOISE_IN_V;
+            a.inA = c.branchEq[(size_t)src_elem];
+            if (a.inA < 0 || a.inA >= N) { setError("noise analysis: the input source has no branch equation"); return CSIM_ERR_ARG; }
+        } else if (kind == CSIM_I) {                         // stampAC: J(p) -= I, J(m) += I (element.cpp:68-81)
+            a.inKind = csim::NOISE_IN_I;
+            a.inA = c.eq[4 * (size_t)src_elem + 1];
+            a.inB = c.eq[4 * (size_t)src_elem + 0];
+        } else { setError("noise analysis: the input source must be a V or I element"); return CSIM_ERR_ARG; }
+    }
+    if (!(temp_k > 0.0) || !std::isfinite(temp_k)) { setError("noise analysis: the temperature must be positive and finite (kelvin)"); return CSIM_ERR_CONFIG; }
+    kT4 = 4.0 * 1.380649e-23 * temp_k;
+    a.N = N;
+    a.outP = out_p;
+    a.outM = out_m;
+    a.S = eng->nNoiseSrc;
+    a.srcA = eng->dNoiseA;
+    a.srcB = eng->dNoiseB;
+    a.eps = eng->cir.ir.k.lu_eps;
+    return CSIM_OK;
+}
+
+int csim_noise_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const double* d_xop, const double* freqs,
+                         int32_t F, int32_t out_p_eq, int32_t out_m_eq, int32_t src_elem, double temp_k, double* d_onoise,
+                         double* d_gain, double* d_contrib, double* d_psd, uint32_t* d_status, void* stream)
+{
+    if (!eng || B < 0 || F < 0 || (B > 0 && F > 0 && (!d_params || !d_xop || !freqs || !d_onoise || !d_status))) {
+        setError("csim_noise_batch_dev: bad argument");
+        return CSIM_ERR_ARG;
+    }
+    csim::NoiseArgs a{};
+    double kT4 = 0.0;
+    if (const int rc = noiseSetup(eng, out_p_eq, out_m_eq, src_elem, temp_k, a, kT4)) return rc;
+    const int N = a.N, S = a.S;
+    int which = eng->cfg.acKernel;
+    if (which == csim::AC_KERNEL_AUTO) which = N <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
+    if (which == csim::AC_KERNEL_PACKED && N > 32) { setError("ac_kernel=packed covers N <= 32"); return CSIM_ERR_UNSUPPORTED; }
+    if (B == 0 || F == 0) return CSIM_OK;
+    HIPCHK(hipSetDevice(eng->device));
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+
+    const double* dOmega = nullptr;
+    if (const int rc = acOmega(eng, freqs, F, &dOmega)) return rc;
+    const int chunk = acChunk(eng, B);
+    if (const int rc = acSysScratch(eng, chunk)) return rc;
+    if (!d_psd && eng->noisePsdCap < (size_t)S * (size_t)chunk) {
+        if (eng->dNoisePsd) HIPCHK(hipFree(eng->dNoisePsd));
+        eng->dNoisePsd = nullptr;
+        eng->noisePsdCap = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&eng->dNoisePsd), sizeof(double) * (size_t)S * (size_t)chunk));
+        eng->noisePsdCap = (size_t)S * (size_t)chunk;
+    }
+    a.F = F;
+    a.B = B;
+    a.sys = eng->dAcSys;
+    a.omega = dOmega;
+    a.onoise = d_onoise;
+    a.gain = d_gain;
+    a.contrib = d_contrib;
+    a.y = nullptr;
+    a.status = d_status;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int Bc = std::min(chunk, B - b0);
+        a.b0 = b0;
+        a.Bc = Bc;
+        a.psd = d_psd ? d_psd : eng->dNoisePsd;
+        a.psdStride = d_psd ? (size_t)B : (size_t)chunk;
+        a.psdOff = d_psd ? (size_t)b0 : 0;
+        HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, b0, Bc, d_xop, eng->dAcSys, hs));
+        HIPCHK(csim::launchNoisePsd(eng->gpTran, eng->dNoiseElem, S, d_params, B, b0, Bc, d_xop, kT4,
+                                    d_psd ? d_psd : eng->dNoisePsd, a.psdStride, a.psdOff, hs));
+        HIPCHK(csim::launchNoiseSweep(which, a, hs));
+    }
+    HIPCHK(hipEventRecord(eng->acOmegaSlots[(size_t)eng->acOmegaCur].done, hs));
+    return CSIM_OK;
+}
+
+int csim_noise_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F, int32_t out_p_eq,
+                     int32_t out_m_eq, int32_t src_elem, double temp_k, double* onoise, double* gain, double* contrib,
+                     double* psd, uint32_t* status)
+{
+    if (!eng || B < 0) { setError("csim_noise_batch: bad argument"); return CSIM_ERR_ARG; }
+    if (eng->plan.N > 63) { setError("noise analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
+    std::vector<double> card;
+    if (!freqs) {
+        if (const int rc = noiseCardFreqs(eng, card)) return rc;
+        freqs = card.data();
+        F = static_cast<int32_t>(card.size());
+    }
+    if (out_p_eq == -2) {
+        if (!eng->noiseEnabled) { setError("csim_noise_batch: no output given and the netlist has no .NOISE card"); return CSIM_ERR_CONFIG; }
+        out_p_eq = eng->noiseOutP;
+        out_m_eq = eng->noiseOutM;
+        src_elem = eng->noiseSrcElem;
+    }
+    if (F < 0 || (B > 0 && F > 0 && !onoise)) { setError("csim_noise_batch: bad argument"); return CSIM_ERR_ARG; }
+    {
+        csim::NoiseArgs probe{};
+        double kT4 = 0.0;
+        if (const int rc = noiseSetup(eng, out_p_eq, out_m_eq, src_elem, temp_k, probe, kT4)) return rc;
+    }
+    if (B == 0) return CSIM_OK;
+    HIPCHK(hipSetDevice(eng->device));
+    const int N = eng->plan.N, S = eng->nNoiseSrc;
+    const bool wantGain = gain && src_elem >= 0;
+    DevBuf dParams, dX, dIt, dSt, dOn, dGain, dCon, dPsd;
+    int rc = stageParams(eng, params, B, dParams);
+    if (rc) return rc;
+    const size_t FB = (size_t)F * (size_t)B;
+    HIPCHK(dX.alloc(sizeof(double) * (size_t)N * B));
+    HIPCHK(dIt.alloc(sizeof(int32_t) * (size_t)B));
+    HIPCHK(dSt.alloc(sizeof(uint32_t) * (size_t)B));
+    HIPCHK(dOn.alloc(sizeof(double) * FB));
+    if (wantGain) HIPCHK(dGain.alloc(sizeof(double) * 2 * FB));
+    if (contrib) HIPCHK(dCon.alloc(sizeof(double) * FB * (size_t)S));
+    if (psd) HIPCHK(dPsd.alloc(sizeof(double) * (size_t)S * (size_t)B));
+    rc = csim_dc_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), dIt.as<int32_t>(), dSt.as<uint32_t>(), nullptr);
+    if (rc) return rc;
+    rc = csim_noise_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), freqs, F, out_p_eq, out_m_eq, src_elem, temp_k,
+                              dOn.as<double>(), wantGain ? dGain.as<double>() : nullptr, contrib ? dCon.as<double>() : nullptr,
+                              psd ? dPsd.as<double>() : nullptr, dSt.as<uint32_t>(), nullptr);
+    if (rc) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    if (status) HIPCHK(hipMemcpy(status, dSt.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    std::vector<double> h;
+    if (FB) {                                                // [F][B] -> [B][F]
+        h.resize(2 * FB);
+        HIPCHK(hipMemcpy(h.data(), dOn.p, sizeof(double) * FB, hipMemcpyDeviceToHost));
+        for (int f = 0; f < F; ++f)
+            for (int b = 0; b < B; ++b) onoise[(size_t)b * F + f] = h[(size_t)f * B + b];
+        if (wantGain) {
+            HIPCHK(hipMemcpy(h.data(), dGain.p, sizeof(double) * 2 * FB, hipMemcpyDeviceToHost));
+            for (int f = 0; f < F; ++f)
+                for (int b = 0; b < B; ++b) {
+                    gain[((size_t)b * F + f) * 2] = h[((size_t)f * B + b) * 2];
+                    gain[((size_t)b * F + f) * 2 + 1] = h[((size_t)f * B + b) * 2 + 1];
+                }
+        }
+    }
+    if (contrib && FB && S) {                                // [F][S][B] -> [B][F][S]
+        h.resize(FB * (size_t)S);
+        HIPCHK(hipMemcpy(h.data(), dCon.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+        for (int f = 0; f < F; ++f)
+            for (int s = 0; s < S; ++s)
+                for (int b = 0; b < B; ++b) contrib[((size_t)b * F + f) * S + s] = h[((size_t)f * S + s) * B + b];
+    }
+    if (psd && S && F) {                                     // [S][B] -> [B][S]
+        h.resize((size_t)S * B);
+        HIPCHK(hipMemcpy(h.data(), dPsd.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+        for (int s = 0; s < S; ++s)
+            for (int b = 0; b < B; ++b) psd[(size_t)b * S + s] = h[(size_t)s * B + b];
+    }
     return CSIM_OK;
 }
 
@@ -1241,6 +1457,25 @@ int csim_lu_solve_batch(int32_t device, int32_t n, int32_t B, const double* A, c
     return CSIM_OK;
 }
 
+// [B][n][n] row-major -> the layout the sweep kernels read: G, C column-major, J re, J im (zeros without a J)
+static std::vector<double> packAcSystems(int n, int B, const double* G, const double* Cm, const double* J)
+{
+    const size_t nn = (size_t)n * n, per = csim::acSystemDoubles(n);
+    std::vector<double> sys(per * (size_t)B);
+    for (int b = 0; b < B; ++b) {
+        double* s = sys.data() + per * (size_t)b;
+        for (int i = 0; i < n; ++i) {
+            for (int j = 0; j < n; ++j) {
+                s[(size_t)j * n + i] = G[nn * b + (size_t)i * n + j];
+                s[nn + (size_t)j * n + i] = Cm[nn * b + (size_t)i * n + j];
+            }
+            s[2 * nn + i] = J ? J[((size_t)b * n + i) * 2] : 0.0;
+            s[2 * nn + n + i] = J ? J[((size_t)b * n + i) * 2 + 1] : 0.0;
+        }
+    }
+    return sys;
+}
+
 // the complex counterpart: any (G + jwC) x = J through the AC sweep kernels, without an engine or a netlist
 int csim_ac_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* Cm, const double* J,
                         const double* omega, int32_t F, int32_t kernel, double* x, uint32_t* flags)
@@ -1261,20 +1496,7 @@ int csim_ac_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, c
     if (which == csim::AC_KERNEL_PACKED && n > 32) { setError("csim_ac_solve_batch: the packed kernel covers n <= 32"); return CSIM_ERR_UNSUPPORTED; }
     if (n == 0 || B == 0 || F == 0) return CSIM_OK;
     HIPCHK(hipSetDevice(device));
-    // [B][n][n] row-major -> the layout launchAcSweep reads: G, C column-major, J re, J im
-    const size_t nn = (size_t)n * n, per = csim::acSystemDoubles(n);
-    std::vector<double> sys(per * (size_t)B);
-    for (int b = 0; b < B; ++b) {
-        double* s = sys.data() + per * (size_t)b;
-        for (int i = 0; i < n; ++i) {
-            for (int j = 0; j < n; ++j) {
-                s[(size_t)j * n + i] = G[nn * b + (size_t)i * n + j];
-                s[nn + (size_t)j * n + i] = Cm[nn * b + (size_t)i * n + j];
-            }
-            s[2 * nn + i] = J[((size_t)b * n + i) * 2];
-            s[2 * nn + n + i] = J[((size_t)b * n + i) * 2 + 1];
-        }
-    }
+    const std::vector<double> sys = packAcSystems(n, B, G, Cm, J);
     const size_t outDoubles = (size_t)2 * F * n * B;
     DevBuf dSys, dOmega, dOut, dF;
     HIPCHK(dSys.alloc(sizeof(double) * sys.size()));
@@ -1298,6 +1520,118 @@ int csim_ac_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, c
                 x[dst] = h[src];
                 x[dst + 1] = h[src + 1];
             }
+    if (flags) HIPCHK(hipMemcpy(flags, dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    return CSIM_OK;
+}
+
+// the engine-free counterpart for the noise kernels: any system, any generator table
+int csim_noise_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* Cm, int32_t out_p,
+                           int32_t out_m, int32_t S, const int32_t* src_a, const int32_t* src_b, const double* psd,
+                           int32_t in_kind, int32_t in_a, int32_t in_b, const double* omega, int32_t F, int32_t kernel,
+                           double* onoise, double* contrib, double* gain, double* y, uint32_t* flags)
+{
+    const bool work = n > 0 && B > 0 && F > 0;
+    if (n < 0 || B < 0 || F < 0 || S < 0 || kernel < csim::AC_KERNEL_AUTO || kernel > csim::AC_KERNEL_PACKED ||
+        in_kind < csim::NOISE_IN_NONE || in_kind > csim::NOISE_IN_I ||
+        (work && (!G || !Cm || !omega || !onoise || (S > 0 && (!src_a || !src_b || !psd))))) {
+        setError("csim_noise_solve_batch: bad argument");
+        return CSIM_ERR_ARG;
+    }
+    if (n > 0) {
+        bool ok = out_p >= 0 && out_p < n && out_m >= -1 && out_m < n && out_p != out_m;
+        for (int s = 0; s < S && ok && src_a && src_b; ++s)
+            ok = src_a[s] >= -1 && src_a[s] < n && src_b[s] >= -1 && src_b[s] < n;
+        if (in_kind == csim::NOISE_IN_V) ok = ok && in_a >= 0 && in_a < n;
+        if (in_kind == csim::NOISE_IN_I) ok = ok && in_a >= -1 && in_a < n && in_b >= -1 && in_b < n;
+        if (!ok) { setError("csim_noise_solve_batch: equation index out of range (or out_p == out_m)"); return CSIM_ERR_ARG; }
+    }
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
+        setError("csim_noise_solve_batch: no usable HIP device (this library has no CPU path)");
+        return CSIM_ERR_NO_DEVICE;
+    }
+    if (n > 63) { setError("csim_noise_solve_batch covers n <= 63"); return CSIM_ERR_UNSUPPORTED; }
+    int which = kernel;
+    if (which == csim::AC_KERNEL_AUTO) which = n <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
+    if (which == csim::AC_KERNEL_PACKED && n > 32) { setError("csim_noise_solve_batch: the packed kernel covers n <= 32"); return CSIM_ERR_UNSUPPORTED; }
+    if (!work) return CSIM_OK;
+    HIPCHK(hipSetDevice(device));
+    const std::vector<double> sys = packAcSystems(n, B, G, Cm, nullptr);
+    std::vector<double> psdT((size_t)S * B);                 // [B][S] -> [S][B]
+    for (int b = 0; b < B; ++b)
+        for (int s = 0; s < S; ++s) psdT[(size_t)s * B + b] = psd[(size_t)b * S + s];
+    const size_t FB = (size_t)F * (size_t)B;
+    const bool wantGain = gain && in_kind != csim::NOISE_IN_NONE;
+    DevBuf dSys, dOmega, dA, dB, dPsd, dOn, dCon, dGain, dY, dF;
+    HIPCHK(dSys.alloc(sizeof(double) * sys.size()));
+    HIPCHK(dOmega.alloc(sizeof(double) * (size_t)F));
+    HIPCHK(dA.alloc(sizeof(int32_t) * (size_t)S));
+    HIPCHK(dB.alloc(sizeof(int32_t) * (size_t)S));
+    HIPCHK(dPsd.alloc(sizeof(double) * psdT.size()));
+    HIPCHK(dOn.alloc(sizeof(double) * FB));
+    HIPCHK(dF.alloc(sizeof(uint32_t) * (size_t)B));
+    if (contrib) HIPCHK(dCon.alloc(sizeof(double) * FB * (size_t)S));
+    if (wantGain) HIPCHK(dGain.alloc(sizeof(double) * 2 * FB));
+    if (y) HIPCHK(dY.alloc(sizeof(double) * 2 * FB * (size_t)n));
+    HIPCHK(hipMemcpy(dSys.p, sys.data(), sizeof(double) * sys.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dOmega.p, omega, sizeof(double) * (size_t)F, hipMemcpyHostToDevice));
+    if (S > 0) {
+        HIPCHK(hipMemcpy(dA.p, src_a, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dB.p, src_b, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dPsd.p, psdT.data(), sizeof(double) * psdT.size(), hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemset(dF.p, 0, sizeof(uint32_t) * (size_t)B));
+    csim::NoiseArgs a{};
+    a.N = n; a.F = F; a.S = S; a.B = B; a.b0 = 0; a.Bc = B;
+    a.outP = out_p; a.outM = out_m;
+    a.inKind = in_kind; a.inA = in_a; a.inB = in_b;
+    a.eps = 1e-15;
+    a.sys = dSys.as<double>();
+    a.omega = dOmega.as<double>();
+    a.srcA = dA.as<int32_t>();
+    a.srcB = dB.as<int32_t>();
+    a.psd = dPsd.as<double>();
+    a.psdStride = (size_t)B;
+    a.psdOff = 0;
+    a.onoise = dOn.as<double>();
+    a.gain = wantGain ? dGain.as<double>() : nullptr;
+    a.contrib = contrib ? dCon.as<double>() : nullptr;
+    a.y = y ? dY.as<double>() : nullptr;
+    a.status = dF.as<uint32_t>();
+    HIPCHK(csim::launchNoiseSweep(which, a, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<double> h(FB);                               // [F][B] -> [B][F]
+    HIPCHK(hipMemcpy(h.data(), dOn.p, sizeof(double) * FB, hipMemcpyDeviceToHost));
+    for (int f = 0; f < F; ++f)
+        for (int b = 0; b < B; ++b) onoise[(size_t)b * F + f] = h[(size_t)f * B + b];
+    if (wantGain) {
+        h.resize(2 * FB);
+        HIPCHK(hipMemcpy(h.data(), dGain.p, sizeof(double) * 2 * FB, hipMemcpyDeviceToHost));
+        for (int f = 0; f < F; ++f)
+            for (int b = 0; b < B; ++b) {
+                gain[((size_t)b * F + f) * 2] = h[((size_t)f * B + b) * 2];
+                gain[((size_t)b * F + f) * 2 + 1] = h[((size_t)f * B + b) * 2 + 1];
+            }
+    }
+    if (contrib && S > 0) {                                  // [F][S][B] -> [B][F][S]
+        h.resize(FB * (size_t)S);
+        HIPCHK(hipMemcpy(h.data(), dCon.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+        for (int f = 0; f < F; ++f)
+            for (int s = 0; s < S; ++s)
+                for (int b = 0; b < B; ++b) contrib[((size_t)b * F + f) * S + s] = h[((size_t)f * S + s) * B + b];
+    }
+    if (y) {                                                 // [F][n][B] -> [B][F][n]
+        h.resize(2 * FB * (size_t)n);
+        HIPCHK(hipMemcpy(h.data(), dY.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+        for (int f = 0; f < F; ++f)
+            for (int p = 0; p < n; ++p)
+                for (int b = 0; b < B; ++b) {
+                    const size_t src = (((size_t)f * n + p) * B + b) * 2;
+                    const size_t dst = (((size_t)b * F + f) * n + p) * 2;
+                    y[dst] = h[src];
+                    y[dst + 1] = h[src + 1];
+                }
+    }
     if (flags) HIPCHK(hipMemcpy(flags, dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
     return CSIM_OK;
 }

@@ -120,6 +120,15 @@ struct csim_engine {
     double* dAcSys = nullptr;
     int acSysCap = 0;                      // instances
 
+    // Noise analysis: the netlist's .NOISE card (resolved), the generator list (element, terminals; uploaded once) and
+    // the PSD scratch of one chunk, used when the caller does not ask for the PSDs
+    int noiseEnabled = 0, noiseOutP = -2, noiseOutM = -1, noiseSrcElem = -1, noiseSweep = 0, noisePoints = 0;
+    double noiseFstart = 0.0, noiseFstop = 0.0;
+    int nNoiseSrc = 0;
+    const int32_t *dNoiseElem = nullptr, *dNoiseA = nullptr, *dNoiseB = nullptr;
+    double* dNoisePsd = nullptr;
+    size_t noisePsdCap = 0;                // doubles
+
     std::vector<int> netlistProbes;        // .PLOTNV / .PRINT node-voltage probes of the netlist (default CSV columns)
 
     // probe list of the most recent transient call

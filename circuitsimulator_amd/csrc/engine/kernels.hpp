@@ -88,6 +88,28 @@ hipError_t launchAcAssemble(const GenPlan& pl, const double* dAcRe, const double
 hipError_t launchAcSweep(int which, int N, const double* dSys, const double* dOmega, int F, const int32_t* dProbe,
                          int nProbe, int B, int b0, int Bc, double eps, double* dOut, uint32_t* dStatus, hipStream_t stream);
 
+// Noise analysis (kernels_noise.hip) on the systems launchAcAssemble leaves.  Generator s of chunk instance c has
+// its PSD at psd[s * psdStride + psdOff + c].  Equation indices are checked by the callers: they index LDS.
+struct NoiseArgs {
+    int N, F, S, B, b0, Bc;
+    int outP, outM;                     // d = +1 at outP, -1 at outM (-1: ground)
+    int inKind, inA, inB;               // ac_noise.hpp NOISE_IN_*
+    double eps;
+    const double* sys;
+    const double* omega;
+    const int32_t *srcA, *srcB;         // [S] generator terminals (equations, -1 ground)
+    const double* psd;
+    size_t psdStride, psdOff;
+    double* onoise;                     // [F][B]
+    double* gain;                       // [F][B] complex or null
+    double* contrib;                    // [F][S][B] or null
+    double* y;                          // [F][N][B] complex or null: the adjoint solution
+    uint32_t* status;                   // [B], OR-ed
+};
+hipError_t launchNoisePsd(const GenPlan& pl, const int32_t* dSrcElem, int S, const double* dParams, int B, int b0, int Bc,
+                          const double* dXop, double kT4, double* dPsd, size_t psdStride, size_t psdOff, hipStream_t stream);
+hipError_t launchNoiseSweep(int which, const NoiseArgs& a, hipStream_t stream);
+
 // layout helpers (transpose.hip): [rows][cols] <-> [cols][rows] of doubles
 hipError_t launchTranspose(const double* dIn, double* dOut, int rows, int cols, hipStream_t stream);
 

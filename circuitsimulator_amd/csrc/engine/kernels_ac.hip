@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ac_lu.hpp"
+#include "ac_sweep.hpp"
 #include "device_common.hpp"
 #include "kernels.hpp"
 
@@ -151,65 +152,7 @@ __global__ void __launch_bounds__(64) ac_sweep_wave_kernel(int N, const double* 
         for (int i = lane; i < N; i += 64) { Ar[i * LD + N] = Jr[i]; Ai[i * LD + N] = Ji[i]; }
         wave_sync();
 
-        bool failed = false;
-        for (int k = 0; k < N; ++k) {
-            const bool cand = lane >= k && lane < N;
-            const double v = cand ? cpx_abs2({Ar[lane * LD + k], Ai[lane * LD + k]}) : -1.0;
-            const double dv = read_lane(v, k);
-            int piv = k;
-            double maxv = dv;
-            if (dv == dv) {                  // a NaN diagonal keeps the pivot
-                maxv = wave_max(v);          // v_max_f64 drops NaN candidates, as "v > maxv" never takes them
-                piv = __ffsll((long long)__ballot(cand && v == maxv)) - 1;
-            }
-            if (maxv < eps2) { failed = true; break; }
-            if (piv != k) {
-                for (int j = k + lane; j <= N; j += 64) {
-                    double t = Ar[k * LD + j]; Ar[k * LD + j] = Ar[piv * LD + j]; Ar[piv * LD + j] = t;
-                    t = Ai[k * LD + j]; Ai[k * LD + j] = Ai[piv * LD + j]; Ai[piv * LD + j] = t;
-                }
-                wave_sync();
-            }
-            const cpx p = {Ar[k * LD + k], Ai[k * LD + k]};
-            if (lane > k && lane < N) {
-                const cpx l = cpx_div({Ar[lane * LD + k], Ai[lane * LD + k]}, p);
-                Lr[lane] = l.re;
-                Li[lane] = l.im;
-            }
-            wave_sync();
-            const int cols = N - k, total = (N - k - 1) * cols;
-            for (int e = lane; e < total; e += 64) {
-                const int di = e / cols;
-                const int i = k + 1 + di, j = k + 1 + (e - di * cols);
-                const cpx l = {Lr[i], Li[i]};
-                if (cpx_is_zero(l)) continue;
-                const cpx r = cpx_elim({Ar[i * LD + j], Ai[i * LD + j]}, l, {Ar[k * LD + j], Ai[k * LD + j]});
-                Ar[i * LD + j] = r.re;
-                Ai[i * LD + j] = r.im;
-            }
-            wave_sync();
-        }
-
-        if (failed) {
-            flags |= CSIM_ST_LU_TINY_PIVOT;
-            if (lane < N) { Xr[lane] = 0.0; Xi[lane] = 0.0; }
-        } else {
-            for (int i = N - 1; i >= 0; --i) {
-                if (lane > i && lane < N) {              // products U(i,j) x(j), then their ordered sum
-                    const cpx pr = cpx_mul({Ar[i * LD + lane], Ai[i * LD + lane]}, {Xr[lane], Xi[lane]});
-                    Lr[lane] = pr.re;
-                    Li[lane] = pr.im;
-                }
-                wave_sync();
-                cpx s = {Ar[i * LD + N], Ai[i * LD + N]};
-                for (int j = i + 1; j < N; ++j) s = cpx_sub(s, {Lr[j], Li[j]});
-                const cpx xv = cpx_div(s, {Ar[i * LD + i], Ai[i * LD + i]});
-                wave_sync();
-                if (lane == 0) { Xr[i] = xv.re; Xi[i] = xv.im; }
-                wave_sync();
-            }
-        }
-        wave_sync();
+        if (acw_solve(N, LD, Ar, Ai, Lr, Li, Xr, Xi, eps2, lane)) flags |= CSIM_ST_LU_TINY_PIVOT;
         for (int p = lane; p < nProbe; p += 64) {
             const int eq = probe ? probe[p] : p;
             const size_t at = ac_out_at(f, p, nProbe, B, b);
@@ -220,84 +163,7 @@ __global__ void __launch_bounds__(64) ac_sweep_wave_kernel(int N, const double* 
     }
     if (lane == 0 && flags) status[b] |= flags;
 }
-
-// ---- register-resident, 32 lanes per system (N <= NP <= 32)
-constexpr int ACP_LANES = 32;
-
-__device__ __forceinline__ unsigned half_ballot(bool pred, int h)
-{
-    return (unsigned)((__ballot(pred) >> (h * ACP_LANES)) & 0xFFFFFFFFull);
-}
-__device__ __forceinline__ double half_max(double v)
-{
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, ACP_LANES));
-    return v;
-}
-__device__ __forceinline__ int half_min(int v)
-{
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m, ACP_LANES));
-    return v;
-}
-
-// column K of the elimination: pivot search over the positions K..N-1, logical exchange of positions K and
-// the pivot's, pivot row to every lane, rows below apply their multiplier
-template <int NP, int K>
-__device__ __forceinline__ void acp_column(double (&ar)[NP + 1], double (&ai)[NP + 1], int N, int& pos, bool& failed,
-                                           double eps2, int h)
-{
-    if constexpr (K < NP) {
-        if (K < N) {
-            const bool cand = pos >= K && pos < N;
-            const double v = cand ? cpx_abs2({ar[K], ai[K]}) : -1.0;
-            const int dl = __ffs((int)half_ballot(pos == K, h)) - 1;
-            const double dv = __shfl(v, dl, ACP_LANES);
-            const double m = half_max(v);
-            const int first = half_min((cand && v == m) ? pos : 1 << 20);
-            const bool nanDiag = dv != dv;                   // a NaN diagonal keeps the pivot
-            const int pivPos = nanDiag ? K : first;
-            const double maxv = nanDiag ? dv : m;
-            if (maxv < eps2) failed = true;
-            const int pl = __ffs((int)half_ballot(pos == pivPos, h)) - 1;
-            if (pos == pivPos) pos = K;
-            else if (pos == K) pos = pivPos;
-            const cpx p = {__shfl(ar[K], pl, ACP_LANES), __shfl(ai[K], pl, ACP_LANES)};
-            cpx l = {0.0, 0.0};
-            if (pos > K && pos < N) l = cpx_div({ar[K], ai[K]}, p);
-            const bool upd = !cpx_is_zero(l);
-#pragma unroll
-            for (int j = K + 1; j <= NP; ++j) {
-                const cpx u = {__shfl(ar[j], pl, ACP_LANES), __shfl(ai[j], pl, ACP_LANES)};
-                if (upd) {
-                    const cpx r = cpx_elim({ar[j], ai[j]}, l, u);
-                    ar[j] = r.re;
-                    ai[j] = r.im;
-                }
-            }
-        }
-        acp_column<NP, K + 1>(ar, ai, N, pos, failed, eps2, h);
-    }
-}
-
-// row I of the back substitution: every lane sums on its own row, the lane holding position I stores x(I)
-template <int NP, int I>
-__device__ __forceinline__ void acp_back(const double (&ar)[NP + 1], const double (&ai)[NP + 1], int N, int pos,
-                                         double* Xr, double* Xi)
-{
-    if constexpr (I >= 0) {
-        if (I < N) {
-            cpx s = {ar[NP], ai[NP]};
-#pragma unroll
-            for (int j = I + 1; j < NP; ++j)
-                if (j < N) s = cpx_sub(s, cpx_mul({ar[j], ai[j]}, {Xr[j], Xi[j]}));
-            const cpx xv = cpx_div(s, {ar[I], ai[I]});
-            if (pos == I) { Xr[I] = xv.re; Xi[I] = xv.im; }
-            __syncthreads();
-        }
-        acp_back<NP, I - 1>(ar, ai, N, pos, Xr, Xi);
-    }
-}
+// ---- register-resident, 32 lanes per system (N <= NP <= 32): acp_column / acp_back of ac_sweep.hpp
 
 template <int NP>
 __global__ void __launch_bounds__(64) ac_sweep_packed_kernel(int N, const double* __restrict__ sys, const double* __restrict__ omega,

@@ -41,6 +41,20 @@ int finishNetlist(csim_netlist* nl)
         }
     }
 
+    // .NOISE card: names -> equation / element indices
+    if (nl->sim.noise.enabled) {
+        const NoiseConfig& nc = nl->sim.noise;
+        auto eqOf = [&](const std::string& name) {
+            if (name == "0") return -1;
+            const auto hit = nl->ckt.nodeNameToId.find(name);
+            return hit == nl->ckt.nodeNameToId.end() ? -2 : nl->ckt.nodes[static_cast<std::size_t>(hit->second)].eqIndex;
+        };
+        nl->noiseOutP = eqOf(nc.outNode);
+        nl->noiseOutM = nc.refNode.empty() ? -1 : eqOf(nc.refNode);
+        for (std::size_t e = 0; e < nl->ckt.elements.size() && !nc.srcName.empty(); ++e)
+            if (toLower(nl->ckt.elements[e]->getName()) == toLower(nc.srcName)) { nl->noiseSrcElem = static_cast<int>(e); break; }
+    }
+
     // reference CSV header: time, V(node) in node order, I(elem) for V sources
     // and inductors in element order (src/tanalisis.cpp:191-206) == equation order
     std::ostringstream h;
@@ -153,6 +167,35 @@ int csim_netlist_ac_source(const csim_netlist* nl, int32_t elem, double* mag, do
     if (!nl || elem < 0 || elem >= nl->cir.ir.n_elems) { csim::setError("csim_netlist_ac_source: bad element index"); return CSIM_ERR_ARG; }
     if (mag) *mag = nl->cir.acMag[static_cast<std::size_t>(elem)];
     if (phase_deg) *phase_deg = nl->cir.acPhaseDeg[static_cast<std::size_t>(elem)];
+    return CSIM_OK;
+}
+
+int csim_netlist_noise(const csim_netlist* nl, int32_t* enabled, int32_t* out_p_eq, int32_t* out_m_eq, int32_t* src_elem,
+                       int32_t* sweep, int32_t* n_points, double* fstart, double* fstop)
+{
+    if (!nl) return CSIM_ERR_ARG;
+    const NoiseConfig& a = nl->sim.noise;
+    if (enabled)  *enabled = a.enabled ? 1 : 0;
+    if (out_p_eq) *out_p_eq = nl->noiseOutP;
+    if (out_m_eq) *out_m_eq = nl->noiseOutM;
+    if (src_elem) *src_elem = nl->noiseSrcElem;
+    if (sweep)    *sweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
+    if (n_points) *n_points = a.nPoints;
+    if (fstart)   *fstart = a.fstart;
+    if (fstop)    *fstop = a.fstop;
+    return CSIM_OK;
+}
+
+int csim_netlist_num_noise_sources(const csim_netlist* nl) { return nl ? static_cast<int>(csim::noiseSources(nl->cir).size()) : 0; }
+
+int csim_netlist_noise_source(const csim_netlist* nl, int32_t i, int32_t* elem, int32_t* eq_a, int32_t* eq_b)
+{
+    if (!nl) return CSIM_ERR_ARG;
+    const std::vector<csim::NoiseSource> src = csim::noiseSources(nl->cir);
+    if (i < 0 || i >= static_cast<int32_t>(src.size())) { csim::setError("csim_netlist_noise_source: bad index"); return CSIM_ERR_ARG; }
+    if (elem) *elem = src[static_cast<std::size_t>(i)].elem;
+    if (eq_a) *eq_a = src[static_cast<std::size_t>(i)].a;
+    if (eq_b) *eq_b = src[static_cast<std::size_t>(i)].b;
     return CSIM_OK;
 }
 

@@ -59,6 +59,34 @@ class Netlist:
         # the .AC card: None, or (sweep "dec" | "oct" | "lin", n_points, fstart, fstop)
         self.ac = (AC_SWEEPS[sw.value], npt.value, f0.value, f1.value) if en.value else None
 
+    @property
+    def noise(self):
+        """The .NOISE card: None, or (out_p_eq, out_m_eq, src_elem, sweep, n_points, fstart, fstop); out_m_eq -1 =
+        ground, src_elem -1 = no input source."""
+        v = [C.c_int32() for _ in range(6)]
+        f0, f1 = C.c_double(), C.c_double()
+        capi.check(capi.lib().csim_netlist_noise(self._h, *[C.byref(x) for x in v], C.byref(f0), C.byref(f1)))
+        en, op, om, src, sw, npt = [x.value for x in v]
+        return (op, om, src, AC_SWEEPS[sw], npt, f0.value, f1.value) if en else None
+
+    def noise_freqs(self):
+        """Frequency grid of the .NOISE card (numpy, Hz)."""
+        card = self.noise
+        if card is None:
+            raise capi.CsimError(capi.CSIM_ERR_CONFIG, "the netlist has no .NOISE card")
+        return ac_freqs(*card[3:])
+
+    @property
+    def noise_sources(self):
+        """The noise generators in element order: [(element index, eq_a, eq_b)], -1 = ground."""
+        L = capi.lib()
+        out = []
+        for i in range(L.csim_netlist_num_noise_sources(self._h)):
+            e, a, b = C.c_int32(), C.c_int32(), C.c_int32()
+            capi.check(L.csim_netlist_noise_source(self._h, i, C.byref(e), C.byref(a), C.byref(b)))
+            out.append((e.value, a.value, b.value))
+        return out
+
     def ac_freqs(self):
         """Frequency grid of the .AC card (numpy, Hz)."""
         if self.ac is None:
@@ -305,6 +333,68 @@ class Engine:
                                             f.ctypes.data, len(f), pe, n_probe, out.ctypes.data, st.ctypes.data))
         return out[..., 0] + 1j * out[..., 1], st
 
+    def _noise_args(self, freqs, out, src):
+        """-> (freqs, out_p, out_m, src_elem); None takes the .NOISE card's value (src: -1 without a card)"""
+        card = self.netlist.noise
+        if freqs is None:
+            f = self.netlist.noise_freqs()
+        else:
+            f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        if out is None:
+            if card is None:
+                raise capi.CsimError(capi.CSIM_ERR_CONFIG, "no output given and the netlist has no .NOISE card")
+            out_p, out_m = card[0], card[1]
+        elif isinstance(out, (tuple, list)):
+            out_p, out_m = int(out[0]), int(out[1])
+        else:
+            out_p, out_m = int(out), -1
+        if src is None:
+            src = card[2] if card is not None else -1
+        return f, out_p, out_m, int(src)
+
+    def noise(self, params, x_op, freqs=None, out=None, src=None, temp=300.15, contrib=False, psd=False, status=None):
+        """Noise sweep of the batch around the operating points x_op (device [N][B], from dc()); csim_noise_batch_dev.
+        freqs: Hz; out: equation or (out_p, out_m), -1 = ground; src: V/I element index for the gain, -1 = none --
+        None takes each from the .NOISE card.  temp in kelvin.
+        -> dict(freqs, onoise [F][B] V^2/Hz, gain complex [F][B] or None, contrib [F][S][B] or None,
+                psd [S][B] or None, status [B]); device tensors; status is OR-ed into `status` when given."""
+        torch = _torch()
+        B = params.shape[1]
+        f, out_p, out_m, src = self._noise_args(freqs, out, src)
+        S = len(self.netlist.noise_sources)
+        dev = self._dev()
+        on = torch.zeros((len(f), B), dtype=torch.float64, device=dev)
+        g = torch.zeros((len(f), B, 2), dtype=torch.float64, device=dev) if src >= 0 else None
+        con = torch.zeros((len(f), S, B), dtype=torch.float64, device=dev) if contrib else None
+        ps = torch.zeros((S, B), dtype=torch.float64, device=dev) if psd else None
+        st = status if status is not None else torch.zeros(B, dtype=torch.int32, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None     # noqa: E731
+        capi.check(capi.lib().csim_noise_batch_dev(self._h, params.data_ptr(), B, x_op.data_ptr(), f.ctypes.data, len(f),
+                                                   out_p, out_m, src, float(temp), on.data_ptr(), ptr(g), ptr(con),
+                                                   ptr(ps), st.data_ptr(), self._stream()))
+        return dict(freqs=f, onoise=on, gain=torch.view_as_complex(g) if g is not None else None, contrib=con, psd=ps,
+                    status=st)
+
+    def noise_host(self, params=None, B=1, freqs=None, out=None, src=None, temp=300.15, contrib=False, psd=False):
+        """DC operating point + noise sweep (csim_noise_batch): numpy, instance-major.
+        -> dict(freqs, onoise [B][F], gain complex [B][F] or None, contrib [B][F][S] or None, psd [B][S] or None,
+                status [B])"""
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=np.float64)
+            B = params.shape[0]
+        f, out_p, out_m, src = self._noise_args(freqs, out, src)
+        S = len(self.netlist.noise_sources)
+        on = np.zeros((B, len(f)))
+        g = np.zeros((B, len(f), 2)) if src >= 0 else None
+        con = np.zeros((B, len(f), S)) if contrib else None
+        ps = np.zeros((B, S)) if psd else None
+        st = np.zeros(B, dtype=np.uint32)
+        ptr = lambda a: a.ctypes.data if a is not None else None    # noqa: E731
+        capi.check(capi.lib().csim_noise_batch(self._h, ptr(params), B, f.ctypes.data, len(f), out_p, out_m, src,
+                                               float(temp), on.ctypes.data, ptr(g), ptr(con), ptr(ps), st.ctypes.data))
+        return dict(freqs=f, onoise=on, gain=g[..., 0] + 1j * g[..., 1] if g is not None else None, contrib=con, psd=ps,
+                    status=st)
+
     def dc_host(self, params=None, B=1):
         if params is not None:
             params = np.ascontiguousarray(params, dtype=np.float64)
@@ -518,6 +608,37 @@ def ac_solve_batch(G, Cm, J, omega, kernel="auto", device=0):
                                               omega.ctypes.data, len(omega), ("auto", "wave", "packed").index(kernel),
                                               x.ctypes.data, flags.ctypes.data))
     return x, flags
+
+
+def noise_solve_batch(G, Cm, out, src_a, src_b, psd, omega, gain_in=None, kernel="auto", device=0, want_y=True):
+    """Batched noise solve through the noise kernels (csim_noise_solve_batch): A^T y = d with A = G + j w C.
+    G, Cm [B][n][n] real; out = (out_p, out_m), -1 = ground; generators src_a, src_b [S] with psd [B][S];
+    omega [F] rad/s; gain_in None | ("v", k) | ("i", a, b): H = y[k] | y[a] - y[b]; kernel auto | wave | packed.
+    -> dict(onoise [B][F], contrib [B][F][S], gain complex [B][F] or None, y complex [B][F][n] or None, flags [B])"""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    Cm = np.ascontiguousarray(Cm, dtype=np.float64)
+    omega = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
+    src_a = np.ascontiguousarray(src_a, dtype=np.int32).reshape(-1)
+    src_b = np.ascontiguousarray(src_b, dtype=np.int32).reshape(-1)
+    B, n = G.shape[0], G.shape[1]
+    S, F = len(src_a), len(omega)
+    psd = np.ascontiguousarray(psd, dtype=np.float64).reshape(B, S)
+    kind, in_a, in_b = 0, -1, -1
+    if gain_in is not None:
+        kind = {"v": 1, "i": 2}[gain_in[0]]
+        in_a = int(gain_in[1])
+        in_b = int(gain_in[2]) if kind == 2 else -1
+    onoise = np.zeros((B, F))
+    contrib = np.zeros((B, F, S))
+    gain = np.zeros((B, F), dtype=np.complex128) if kind else None
+    y = np.zeros((B, F, n), dtype=np.complex128) if want_y else None
+    flags = np.zeros(B, dtype=np.uint32)
+    capi.check(capi.lib().csim_noise_solve_batch(
+        device, n, B, G.ctypes.data, Cm.ctypes.data, int(out[0]), int(out[1]), S, src_a.ctypes.data, src_b.ctypes.data,
+        psd.ctypes.data, kind, in_a, in_b, omega.ctypes.data, F, ("auto", "wave", "packed").index(kernel),
+        onoise.ctypes.data, contrib.ctypes.data, gain.ctypes.data if gain is not None else None,
+        y.ctypes.data if y is not None else None, flags.ctypes.data))
+    return dict(onoise=onoise, contrib=contrib, gain=gain, y=y, flags=flags)
 
 
 def gs_solve_batch(A, b, x0=None, max_iters=1000, tol=1e-10, device=0):

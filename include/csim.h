@@ -78,7 +78,7 @@ extern "C" {
 #define CSIM_ERR_HIP          -4   /* a HIP runtime call failed                    */
 #define CSIM_ERR_UNSUPPORTED  -5   /* circuit outside what the kernels cover       */
 #define CSIM_ERR_EMPTY        -6   /* circuit has no unknowns                      */
-#define CSIM_ERR_CONFIG       -7   /* invalid .TRAN / .AC numbers, no AC source    */
+#define CSIM_ERR_CONFIG       -7   /* invalid .TRAN / .AC / .NOISE numbers, no AC source */
 
 typedef struct csim_netlist csim_netlist;
 typedef struct csim_engine  csim_engine;
@@ -131,6 +131,14 @@ int  csim_netlist_ac(const csim_netlist* nl, int32_t* enabled, int32_t* sweep, i
 /* AC excitation of element `elem` (`AC mag [phase_deg]` on a V/I line; 0, 0 for any other element).
  * Kept beside the IR, not in the parameter vector: P and the slots are those of the netlist without AC. */
 int  csim_netlist_ac_source(const csim_netlist* nl, int32_t elem, double* mag, double* phase_deg);
+/* .NOISE V(out[,ref]) [src] DEC|OCT|LIN n fstart fstop: output equations (out_m_eq -1: ground; -2: a node the
+ * netlist does not have), input source element (-1: none named, or no such element), the sweep as for .AC.      */
+int  csim_netlist_noise(const csim_netlist* nl, int32_t* enabled, int32_t* out_p_eq, int32_t* out_m_eq,
+                        int32_t* src_elem, int32_t* sweep, int32_t* n_points, double* fstart, double* fstop);
+/* Noise generators ("Noise analysis" below), in element order: element index and the two equations the current
+ * generator lies between (-1: ground).  Resistors between their terminals, MOSFET channels drain - source.    */
+int  csim_netlist_num_noise_sources(const csim_netlist* nl);
+int  csim_netlist_noise_source(const csim_netlist* nl, int32_t i, int32_t* elem, int32_t* eq_a, int32_t* eq_b);
 /* Monte-Carlo recipe per parameter slot: 0 fixed, 1 scaled by (1+sigma z),
  * 2 MOS K rebuilt from a MU draw: K = (MU(1+sigma z))*COX*(W/L)              */
 int  csim_netlist_mc_kinds(const csim_netlist* nl, int32_t* kinds);
@@ -182,7 +190,7 @@ int  csim_engine_set_kernel(csim_engine* eng, int32_t which);
  *   near_test_rollback (0)                  test aid: every verified near-threshold decision is treated as a
  *                                           mismatch, so the roll-back path runs (results must not change)
  *   hybrid_sync (CSIM_HYBRID_SYNC, 1)       see "Streams" above
- *   ac_kernel (auto)                        test aid: AC sweep kernel, auto | wave | packed (see csim_ac_batch_dev)
+ *   ac_kernel (auto)                        test aid: AC and noise sweep kernel, auto | wave | packed (see csim_ac_batch_dev)
  *   dc_fast (CSIM_DC_FAST, 0)               DC operating points start on the fast generated kernel (FMA
  *                                           contraction, reciprocal pivots; controller decisions within
  *                                           its rounding noise are replayed) instead of the faithful one
@@ -299,6 +307,46 @@ int  csim_ac_batch(csim_engine* eng, const double* params, int32_t B, const doub
 int  csim_ac_system_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int32_t B, const double* d_xop,
                         double* d_sys, void* stream);
 
+/* ---- Noise analysis (.NOISE; small-signal output noise by one adjoint solve per frequency) ----
+ * For instance b and angular frequency w let A = G + j w C be exactly the matrix of "AC analysis" above (the same
+ * assembly: an element AC leaves out is left out here).
+ *   Adjoint system  A^T y = d, d real: +1 at equation out_p, -1 at out_m (out_m = -1: ground, no entry).
+ *      out_p == out_m or out_p < 0: CSIM_ERR_ARG.  The solve is the AC algorithm applied to the matrix A^T: the same
+ *      pivot rule on the transposed matrix, multiplier, elimination order, zero-multiplier skip and ascending back
+ *      substitution.  Load A^T(i,j) = G(j,i) + j (w C(j,i)), w C one product.  No FMA contraction anywhere.
+ *   Generators  in element order, S per circuit (csim_netlist_noise_source), each a current PSD in A^2/Hz between two
+ *      equations (a, b).  kT4 = 4.0 * 1.380649e-23 * temp_k, computed once on the host.
+ *        resistor, R != 0:  psd = kT4 * (1.0 / R)      (R == 0: psd 0, the stamp is skipped, src/element.cpp:20-24)
+ *        MOSFET channel, drain - source (SPICE3 MOS1):  psd = kT4 * ((2.0 / 3.0) * fabs(gg)), gg the gate
+ *        transconductance of mos_eval at x_op, the call the G pass makes.
+ *      Noiseless: capacitors, inductors, sources, tran_gmin, the MOS off-conductance.  No flicker noise (the model
+ *      cards carry no KF / AF).
+ *   Per generator s   z = y[a] - y[b] (ground = (0, 0));  contrib[s] = (z.re z.re + z.im z.im) * psd[s]
+ *   Output noise      onoise = 0.0 + contrib[0] + contrib[1] + ... in ascending order, V^2/Hz
+ *   Gain (src_elem >= 0)  H = transfer from a unit AC excitation of that V / I element to the output, read off the
+ *      adjoint: V source with branch equation k: H = y[k]; I source (p, m): H = y[m] - y[p] (stampAC,
+ *      src/element.cpp:68-81).  Any other element: CSIM_ERR_ARG.  Input-referred noise is onoise / |H|^2, formed by
+ *      the caller.
+ *   Failed factorisation  a column maximum below lu_eps^2 at some frequency: onoise, every contrib and the gain are
+ *      +0.0 there, CSIM_ST_LU_TINY_PIVOT is OR-ed into the instance's status, the sweep goes on.
+ * Circuits of up to 63 unknowns (CSIM_ERR_UNSUPPORTED beyond).  S == 0 is legal: onoise = 0.  temp_k <= 0 or not
+ * finite: CSIM_ERR_CONFIG.  No AC source is needed.
+ *
+ * Enqueues the sweep; never waits for it; frequency lists as csim_ac_batch_dev (same buffers, same discipline).
+ *   d_onoise [F][B]    d_gain [F][B] complex (re, im) or NULL (not written when src_elem < 0)
+ *   d_contrib [F][S][B] or NULL    d_psd [S][B] or NULL: the generators' PSDs    d_status [B], OR-ed
+ * The engine option ac_kernel picks the kernel as for AC; both give bit-identical results.                        */
+int  csim_noise_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int32_t B, const double* d_xop,
+                          const double* freqs, int32_t F, int32_t out_p_eq, int32_t out_m_eq, int32_t src_elem,
+                          double temp_k, double* d_onoise, double* d_gain, double* d_contrib, double* d_psd,
+                          uint32_t* d_status, void* stream);
+/* DC operating point, then the sweep.  params [B][P] or NULL (nominal); freqs NULL = the grid of the netlist's
+ * .NOISE card (F ignored); out_p_eq == -2 = the card's output and source (out_m_eq, src_elem ignored); no card:
+ * CSIM_ERR_CONFIG.  onoise [B][F]; gain [B][F] complex or NULL; contrib [B][F][S] or NULL; psd [B][S] or NULL.   */
+int  csim_noise_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F,
+                      int32_t out_p_eq, int32_t out_m_eq, int32_t src_elem, double temp_k, double* onoise,
+                      double* gain, double* contrib, double* psd, uint32_t* status);
+
 /* Batched dense solve A x = b with the engine's pivoted LU
  * (Solver::solveLinearSystemLU semantics: first-maximum partial pivoting,
  * tiny pivot -> zero vector).  A [B][n][n] row-major, b/x [B][n], host
@@ -315,6 +363,17 @@ int  csim_lu_solve_batch(int32_t device, int32_t n, int32_t B, const double* A,
 int  csim_ac_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* C,
                          const double* J, const double* omega, int32_t F, int32_t kernel,
                          double* x, uint32_t* flags);
+
+/* The noise kernels on systems and generator tables given directly (host pointers; lu_eps = 1e-15), the counterpart
+ * of csim_ac_solve_batch for "Noise analysis".  G, C [B][n][n] row-major; generators src_a, src_b [S] (equations, -1
+ * ground) with psd [B][S]; in_kind 0: no gain, 1: H = y[in_a], 2: H = y[in_a] - y[in_b] (-1 ground); omega [F] rad/s.
+ * onoise [B][F]; contrib [B][F][S], gain [B][F] complex, y [B][F][n] complex (the adjoint solution, zeros where
+ * the factorisation fails) and flags [B] are optional.  kernel and sizes as csim_ac_solve_batch; an equation index
+ * out of range: CSIM_ERR_ARG.                                                                                     */
+int  csim_noise_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* C, int32_t out_p,
+                            int32_t out_m, int32_t S, const int32_t* src_a, const int32_t* src_b, const double* psd,
+                            int32_t in_kind, int32_t in_a, int32_t in_b, const double* omega, int32_t F,
+                            int32_t kernel, double* onoise, double* contrib, double* gain, double* y, uint32_t* flags);
 
 /* ---- Gauss-Seidel variant of the reference (never reached from its main(), kept as public API) ----
  * Batched Solver::solveLinearSystemGaussSeidel (include/solver.hpp:139-204): sweeps in row order with the
