@@ -2,6 +2,7 @@
 // are the batch-of-one case of the GPU engine.
 #include "analysis.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <fstream>
@@ -100,6 +101,31 @@ BatchNoiseResult BatchEngine::noise(const std::vector<double>& params, int B, co
                          srcElem >= 0 ? reinterpret_cast<double*>(r.gain.data()) : nullptr,
                          wantContrib ? r.contrib.data() : nullptr, nullptr, r.status.data()) != CSIM_OK)
         fail("csim_noise_batch");
+    return r;
+}
+
+BatchSpResult BatchEngine::sp(const std::vector<double>& params, int B, const std::vector<double>& freqs, bool wantS)
+{
+    BatchSpResult r;
+    r.freqs = freqs;
+    if (r.freqs.empty()) {                                  // the .SP card
+        int32_t enabled = 0, sweep = 0, nPoints = 0;
+        double fstart = 0.0, fstop = 0.0;
+        if (csim_netlist_sp(nl_, &enabled, &sweep, &nPoints, &fstart, &fstop) != CSIM_OK) fail("csim_netlist_sp");
+        const int64_t n = enabled ? csim_ac_num_freqs(sweep, nPoints, fstart, fstop) : 0;
+        if (n <= 0) { csim::setError("BatchEngine::sp: no frequencies given and the netlist has no .SP card"); fail("BatchEngine::sp"); }
+        r.freqs.resize(static_cast<std::size_t>(n));
+        if (csim_ac_freqs(sweep, nPoints, fstart, fstop, r.freqs.data()) != CSIM_OK) fail("csim_ac_freqs");
+    }
+    r.nPorts = std::max(0, csim_netlist_num_ports(nl_));
+    const std::size_t n = static_cast<std::size_t>(B) * r.freqs.size() * static_cast<std::size_t>(r.nPorts * r.nPorts);
+    r.y.assign(n, std::complex<double>());
+    if (wantS) r.s.assign(n, std::complex<double>());
+    r.status.assign(static_cast<std::size_t>(B), 0);
+    if (csim_sp_batch(eng_, params.empty() ? nullptr : params.data(), B, r.freqs.data(), static_cast<int>(r.freqs.size()),
+                      reinterpret_cast<double*>(r.y.data()), wantS ? reinterpret_cast<double*>(r.s.data()) : nullptr,
+                      r.status.data()) != CSIM_OK)
+        fail("csim_sp_batch");
     return r;
 }
 

@@ -50,6 +50,13 @@ struct BatchNoiseResult {
     std::vector<uint32_t> status;                 // DC and LU bits (CSIM_ST_LU_TINY_PIVOT: a singular frequency)
 };
 
+struct BatchSpResult {
+    std::vector<double> freqs;                    // [F] Hz
+    int nPorts = 0;                               // P (csim_netlist_port order)
+    std::vector<std::complex<double>> y, s;       // [B][F][P][P], row i then column j (s empty unless asked for)
+    std::vector<uint32_t> status;                 // DC and LU bits (CSIM_ST_LU_TINY_PIVOT: a singular frequency)
+};
+
 // One engine per (circuit, GPU).  Throws std::runtime_error when no HIP
 // device is usable: there is no CPU path.
 class BatchEngine {
@@ -81,6 +88,11 @@ public:
     // Output V(outP) - V(outM) (equations; outM = -1: ground); srcElem: V/I element for the gain, -1 none.
     BatchNoiseResult noise(const std::vector<double>& params, int B, const std::vector<double>& freqs, int outP,
                            int outM = -1, int srcElem = -1, double tempK = 300.15, bool wantContrib = false);
+
+    // S-parameters of the netlist's ports (csim_sp_batch, include/csim.h): DC operating point, then one factorisation
+    // with one right-hand side per port and frequency; Y always, S when asked for.  freqs empty: the .SP card (an
+    // error when the netlist has none).
+    BatchSpResult sp(const std::vector<double>& params, int B, const std::vector<double>& freqs, bool wantS = true);
 
     // the transient of instance `instance` of params ([B][P], empty = nominal) as the reference's CSV
     // (src/tanalisis.cpp:189-231); probeEq empty: the netlist's .PLOTNV/.PRINT probes when `sim` names any, else

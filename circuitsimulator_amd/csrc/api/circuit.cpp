@@ -247,6 +247,8 @@ CircuitIR flatten(const Circuit& ckt)
         else if (const auto* i = dynamic_cast<const CurrentSource*>(e.get())) src = &i->getSpec();
         out.acMag.push_back(src ? src->acMag : 0.0);
         out.acPhaseDeg.push_back(src ? src->acPhaseDeg : 0.0);
+        out.portNum.push_back(src && r.kind == CSIM_V ? src->portNum : 0);
+        out.portZ0.push_back(src ? src->portZ0 : 50.0);
         if (r.branchEq >= 0 && r.branchEq < nNode + nBranch)
             out.eqNames[static_cast<std::size_t>(r.branchEq)] = e->getName();
         const bool mos = (r.kind == CSIM_NMOS || r.kind == CSIM_PMOS);

@@ -84,6 +84,9 @@ struct CircuitIR {
     // Not part of the parameter vector: AC analysis does not perturb it, and P stays that of the
     // netlist without AC tokens.
     std::vector<double> acMag, acPhaseDeg;
+    // S-parameter ports per element (`PORTNUM k [Z0 r]` on a V source line; 0 elsewhere), beside the IR like acMag
+    std::vector<int32_t> portNum;
+    std::vector<double> portZ0;
     // names for output headers: node name per node equation, element name per
     // branch equation
     std::vector<std::string> eqNames;

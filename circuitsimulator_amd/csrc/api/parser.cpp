@@ -3,10 +3,11 @@
 //   whose first non-blank is '*' or ';' is a comment; a leading '+' continues
 //   the previous logical line; tokens split on blanks.
 //   Devices by first letter (any case): R C L V I M.   Cards: .MODEL (read in
-//   a first pass, so it may follow its users) .TRAN .OP .DC .AC .NOISE .HB .PRINT
+//   a first pass, so it may follow its users) .TRAN .OP .DC .AC .NOISE .SP .HB .PRINT
 //   .PLOTNV .PLOTNC; anything else is reported and skipped.
 #include "parser.hpp"
 
+#include <algorithm>
 #include <cctype>
 #include <exception>
 #include <fstream>
@@ -139,6 +140,13 @@ void NetlistParser::parseStatements()
 
 void NetlistParser::deviceStatement(const Statement& st)
 {
+    // PORTNUM k [Z0 r] makes a V source a port of the S-parameter analysis; nothing else can be one
+    if (upperHead(st.tokens[0]) != 'V')
+        for (std::size_t i = 1; i < st.tokens.size(); ++i)
+            if (toLower(st.tokens[i]) == "portnum") {
+                std::cerr << "Line " << st.lineNo << ": PORTNUM needs a voltage source: " << st.raw << "\n";
+                return;
+            }
     switch (upperHead(st.tokens[0])) {
         case 'R': case 'C': case 'L': twoTerminal(st, upperHead(st.tokens[0])); break;
         case 'V': voltageSource(st); break;
@@ -240,6 +248,39 @@ bool isWaveKeyword(const std::string& token)
            startsWithKeyword(token, "pwl") || startsWithKeyword(token, "sin");
 }
 
+// `PORTNUM k [Z0 r]` (ngspice's spelling) anywhere after the nodes of a V line: taken out of the token list, so the
+// DC / AC / waveform tokens parse as they do without it.  False (with a message) when k or r is not acceptable.
+bool takePortSpec(std::vector<std::string>& t, int lineNo, const std::string& raw, SourceSpec& spec)
+{
+    std::size_t at = 3;
+    while (at < t.size() && toLower(t[at]) != "portnum") ++at;
+    if (at >= t.size()) return true;
+    std::size_t end = at + 2;
+    bool ok = at + 1 < t.size();
+    double k = 0.0, z0 = 50.0;
+    try {
+        if (ok) k = parseSpiceNumber(t[at + 1]);
+        if (ok && end < t.size() && toLower(t[end]) == "z0") {
+            ok = end + 1 < t.size();
+            if (ok) z0 = parseSpiceNumber(t[end + 1]);
+            end += 2;
+        }
+    } catch (const std::exception&) {
+        ok = false;
+    }
+    ok = ok && k >= 1.0 && k <= 1e6 && k == static_cast<double>(static_cast<int>(k)) && z0 > 0.0 && z0 <= 1.7e308;
+    for (std::size_t i = std::min(end, t.size()); ok && i < t.size(); ++i) ok = toLower(t[i]) != "portnum";
+    if (!ok) {
+        std::cerr << "Line " << lineNo << ": PORTNUM needs a port number >= 1 and, after Z0, a finite resistance > 0: "
+                  << raw << "\n";
+        return false;
+    }
+    spec.portNum = static_cast<int>(k);
+    spec.portZ0 = z0;
+    t.erase(t.begin() + static_cast<std::ptrdiff_t>(at), t.begin() + static_cast<std::ptrdiff_t>(end));
+    return true;
+}
+
 bool parseAcSpec(const std::vector<std::string>& t, std::size_t& next, int lineNo, const std::string& raw, SourceSpec& spec)
 {
     if (next >= t.size() || toLower(t[next]) != "ac") return true;
@@ -264,15 +305,17 @@ bool parseAcSpec(const std::vector<std::string>& t, std::size_t& next, int lineN
 
 // Vname np nm <value> [AC mag [phase]] [SIN ...] | Vname np nm DC <value> [AC ...] [SIN ...] |
 // Vname np nm [AC mag [phase]] SIN v0 va freq [td [phi]]
+// each with `PORTNUM k [Z0 r]` anywhere after the nodes (usually last): port k of the .SP analysis
 void NetlistParser::voltageSource(const Statement& st)
 {
-    const auto& t = st.tokens;
+    std::vector<std::string> t = st.tokens;
+    SourceSpec spec;
+    if (!takePortSpec(t, st.lineNo, st.raw, spec)) return;
     if (t.size() < 4) {
         std::cerr << "Line " << st.lineNo << ": invalid voltage source: " << st.raw << "\n";
         return;
     }
 
-    SourceSpec spec;
     std::size_t next = 3;      // token where a waveform keyword may start
     try {
         if (t.size() >= 5 && toLower(t[3]) == "dc") {
@@ -379,6 +422,7 @@ void NetlistParser::dotCard(const Statement& st)
     else if (head == ".tran")   tranCard(st);
     else if (head == ".ac")     acCard(st);
     else if (head == ".noise")  noiseCard(st);
+    else if (head == ".sp")     spCard(st);
     else if (head == ".print")  printCard(st);
     else if (head == ".model")  modelCard(st);
     else if (head == ".hb")     hbCard(st);
@@ -453,6 +497,30 @@ void NetlistParser::acCard(const Statement& st)
     }
     cfg.enabled = true;
     sim.ac = cfg;
+}
+
+// .SP {LIN|DEC|OCT} npoints fstart fstop
+void NetlistParser::spCard(const Statement& st)
+{
+    const auto& t = st.tokens;
+    const std::string sweep = t.size() > 1 ? toLower(t[1]) : std::string();
+    if (t.size() < 5 || (sweep != "lin" && sweep != "oct" && sweep != "dec")) {
+        std::cerr << "Line " << st.lineNo << ": invalid .SP syntax: " << st.raw << "\n";
+        return;
+    }
+    SpConfig cfg;
+    cfg.sweepType = sweep == "lin" ? AcSweepType::LIN : (sweep == "oct" ? AcSweepType::OCT : AcSweepType::DEC);
+    try {
+        cfg.nPoints = std::stoi(t[2]);
+        cfg.fstart  = parseSpiceNumber(t[3]);
+        cfg.fstop   = parseSpiceNumber(t[4]);
+    } catch (const std::exception& e) {
+        std::cerr << "Line " << st.lineNo << ": cannot parse .SP arguments: " << e.what()
+                  << " in '" << st.raw << "'\n";
+        return;
+    }
+    cfg.enabled = true;
+    sim.sp = cfg;
 }
 
 // .NOISE V(out[,ref]) [src] {LIN|DEC|OCT} npoints fstart fstop

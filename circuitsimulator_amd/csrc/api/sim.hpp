@@ -113,6 +113,8 @@ struct SourceSpec {
     double dcValue    = 0.0;
     double acMag      = 0.0;
     double acPhaseDeg = 0.0;
+    int    portNum    = 0;      // PORTNUM k [Z0 r]: port k of the S-parameter analysis (0: no port); kept beside the IR
+    double portZ0     = 50.0;
     TranWaveform tran;
 
     // operating point value: SIN sources contribute their offset v0, the
@@ -154,6 +156,14 @@ struct NoiseConfig {
     double fstart = 0.0, fstop = 0.0;
 };
 
+// .SP {DEC|OCT|LIN} n fstart fstop
+struct SpConfig {
+    bool enabled = false;
+    AcSweepType sweepType = AcSweepType::DEC;
+    int nPoints = 0;
+    double fstart = 0.0, fstop = 0.0;
+};
+
 struct HbConfig {
     bool enabled = false;
     double f0 = 0.0;
@@ -179,6 +189,7 @@ public:
     TranConfig tran;
     AcConfig ac;
     NoiseConfig noise;
+    SpConfig sp;
     HbConfig hb;
     std::vector<PrintCommand> printCommands;
 

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ac_noise.hpp"
+#include "ac_port.hpp"
 #include "codegen.hpp"
 #include "csim.h"
 #include "engine_internal.hpp"
@@ -315,6 +316,16 @@ int csim_engine_create(const csim_netlist* nl, int32_t device, csim_engine** out
         eng->noiseFstart = nc.fstart;
         eng->noiseFstop = nc.fstop;
     }
+    if (!rc) {
+        for (const csim::Port& p : nl->ports) { eng->spPortEq.push_back(p.branchEq); eng->spZ0.push_back(p.z0); }
+        eng->spPortError = nl->portError;
+        const SpConfig& sc = nl->sim.sp;
+        eng->spEnabled = sc.enabled ? 1 : 0;
+        eng->spSweep = sc.sweepType == AcSweepType::DEC ? 0 : (sc.sweepType == AcSweepType::OCT ? 1 : 2);
+        eng->spPoints = sc.nPoints;
+        eng->spFstart = sc.fstart;
+        eng->spFstop = sc.fstop;
+    }
     if (!rc) rc = fillGenPlan(eng, eng->plan.dc, eng->gpDc);
     if (!rc) rc = fillGenPlan(eng, eng->plan.tran, eng->gpTran);
     if (rc) { csim_engine_destroy(eng); return rc; }
@@ -418,10 +429,13 @@ int csim_engine_set_option(csim_engine* eng, const char* key, const char* value)
     return CSIM_OK;
 }
 
+static size_t acChunkCap(const csim_engine* eng);
+
 int64_t csim_engine_stat(const csim_engine* eng, const char* key)
 {
     if (!eng || !key) return -1;
     const std::string k(key);
+    if (k == "ac_chunk") return (int64_t)acChunkCap(eng);
     if (k == "near_verified") return eng->nearVerified;
     if (k == "near_rolled_back") return eng->nearRolledBack;
     return -1;
@@ -812,11 +826,15 @@ int csim_dc_batch(csim_engine* eng, const double* params, int32_t B, double* x_o
 
 // the system of every instance lives in device scratch between assembly and sweep; instances are processed in
 // chunks that keep it below 256 MiB
-static int acChunk(const csim_engine* eng, int B)
+static size_t acChunkCap(const csim_engine* eng)
 {
     const size_t per = sizeof(double) * csim::acSystemDoubles(eng->plan.N);
-    const size_t cap = std::max<size_t>(256, ((size_t)256 << 20) / per);
-    return (int)std::min<size_t>((size_t)B, cap);
+    return std::max<size_t>(256, ((size_t)256 << 20) / per);
+}
+
+static int acChunk(const csim_engine* eng, int B)
+{
+    return (int)std::min<size_t>((size_t)B, acChunkCap(eng));
 }
 
 static int acCheck(const csim_engine* eng)
@@ -1176,6 +1194,128 @@ int csim_noise_batch(csim_engine* eng, const double* params, int32_t B, const do
         for (int s = 0; s < S; ++s)
             for (int b = 0; b < B; ++b) psd[(size_t)b * S + s] = h[(size_t)s * B + b];
     }
+    return CSIM_OK;
+}
+
+// ---- S-parameter analysis ---------------------------------------------------
+
+// the engine's ports -> the kernels' numbers (include/csim.h "S-parameter analysis")
+static int spSetup(const csim_engine* eng, csim::SpArgs& a)
+{
+    const int N = eng->plan.N;
+    if (!eng->spPortError.empty()) { setError(eng->spPortError); return CSIM_ERR_CONFIG; }
+    const int P = (int)eng->spPortEq.size();
+    if (P == 0) { setError("S-parameter analysis: the netlist declares no port (V ... PORTNUM k [Z0 r])"); return CSIM_ERR_CONFIG; }
+    if (N > 63) { setError("S-parameter analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
+    a.N = N;
+    a.K = a.P = P;
+    for (int i = 0; i < P; ++i) {
+        a.portEq[i] = eng->spPortEq[(size_t)i];
+        a.sz[i] = std::sqrt(eng->spZ0[(size_t)i]);
+        if (a.portEq[i] < 0 || a.portEq[i] >= N) { setError("S-parameter analysis: a port has no branch equation"); return CSIM_ERR_ARG; }
+    }
+    a.eps = eng->cir.ir.k.lu_eps;
+    return CSIM_OK;
+}
+
+int csim_sp_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const double* d_xop, const double* freqs,
+                      int32_t F, double* d_y, double* d_s, uint32_t* d_status, void* stream)
+{
+    if (!eng || B < 0 || F < 0) { setError("csim_sp_batch_dev: bad argument"); return CSIM_ERR_ARG; }
+    csim::SpArgs a{};
+    if (const int rc = spSetup(eng, a)) return rc;          // no port: CSIM_ERR_CONFIG, whatever the buffers
+    if (B > 0 && F > 0 && (!d_params || !d_xop || !freqs || !d_y || !d_status)) {
+        setError("csim_sp_batch_dev: bad argument");
+        return CSIM_ERR_ARG;
+    }
+    const int N = a.N;
+    int which = eng->cfg.acKernel;
+    if (which == csim::AC_KERNEL_AUTO) which = N <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
+    if (which == csim::AC_KERNEL_PACKED && N > 32) { setError("ac_kernel=packed covers N <= 32"); return CSIM_ERR_UNSUPPORTED; }
+    if (B == 0 || F == 0) return CSIM_OK;
+    HIPCHK(hipSetDevice(eng->device));
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+
+    const double* dOmega = nullptr;
+    if (const int rc = acOmega(eng, freqs, F, &dOmega)) return rc;
+    const int chunk = acChunk(eng, B);
+    if (const int rc = acSysScratch(eng, chunk)) return rc;
+    a.F = F;
+    a.B = B;
+    a.sys = eng->dAcSys;
+    a.omega = dOmega;
+    a.y = d_y;
+    a.s = d_s;
+    a.status = d_status;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        a.b0 = b0;
+        a.Bc = std::min(chunk, B - b0);
+        HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, b0, a.Bc, d_xop, eng->dAcSys, hs));
+        HIPCHK(csim::launchSpSweep(which, a, hs));
+    }
+    HIPCHK(hipEventRecord(eng->acOmegaSlots[(size_t)eng->acOmegaCur].done, hs));
+    return CSIM_OK;
+}
+
+// [F][P][P][B] complex on the device -> [B][F][P][P] on the host
+static int spToHost(const double* dSrc, int F, int PP, int B, double* dst)
+{
+    const size_t n = (size_t)2 * F * PP * B;
+    if (n == 0) return CSIM_OK;
+    std::vector<double> h(n);
+    HIPCHK(hipMemcpy(h.data(), dSrc, sizeof(double) * n, hipMemcpyDeviceToHost));
+    for (int f = 0; f < F; ++f)
+        for (int t = 0; t < PP; ++t)
+            for (int b = 0; b < B; ++b) {
+                const size_t src = (((size_t)f * PP + t) * B + b) * 2;
+                const size_t at = (((size_t)b * F + f) * PP + t) * 2;
+                dst[at] = h[src];
+                dst[at + 1] = h[src + 1];
+            }
+    return CSIM_OK;
+}
+
+int csim_sp_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F, double* y, double* s,
+                  uint32_t* status)
+{
+    if (!eng || B < 0) { setError("csim_sp_batch: bad argument"); return CSIM_ERR_ARG; }
+    {
+        csim::SpArgs probe{};
+        if (const int rc = spSetup(eng, probe)) return rc;
+    }
+    std::vector<double> card;
+    if (!freqs) {
+        if (!eng->spEnabled) { setError("csim_sp_batch: no frequencies given and the netlist has no .SP card"); return CSIM_ERR_CONFIG; }
+        const int64_t n = csim_ac_num_freqs(eng->spSweep, eng->spPoints, eng->spFstart, eng->spFstop);
+        if (n < 0) return static_cast<int>(n);
+        card.resize((size_t)n);
+        if (const int rc = csim_ac_freqs(eng->spSweep, eng->spPoints, eng->spFstart, eng->spFstop, card.data())) return rc;
+        freqs = card.data();
+        F = static_cast<int32_t>(n);
+    }
+    if (F < 0 || (B > 0 && F > 0 && !y)) { setError("csim_sp_batch: bad argument"); return CSIM_ERR_ARG; }
+    if (B == 0) return CSIM_OK;
+    HIPCHK(hipSetDevice(eng->device));
+    const int N = eng->plan.N, PP = (int)(eng->spPortEq.size() * eng->spPortEq.size());
+    const size_t outDoubles = (size_t)2 * F * PP * B;
+    DevBuf dParams, dX, dIt, dSt, dY, dS;
+    int rc = stageParams(eng, params, B, dParams);
+    if (rc) return rc;
+    HIPCHK(dX.alloc(sizeof(double) * (size_t)N * B));
+    HIPCHK(dIt.alloc(sizeof(int32_t) * (size_t)B));
+    HIPCHK(dSt.alloc(sizeof(uint32_t) * (size_t)B));
+    HIPCHK(dY.alloc(sizeof(double) * outDoubles));
+    if (s) HIPCHK(dS.alloc(sizeof(double) * outDoubles));
+    rc = csim_dc_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), dIt.as<int32_t>(), dSt.as<uint32_t>(), nullptr);
+    if (rc) return rc;
+    rc = csim_sp_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), freqs, F, dY.as<double>(),
+                           s ? dS.as<double>() : nullptr, dSt.as<uint32_t>(), nullptr);
+    if (rc) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    if (status) HIPCHK(hipMemcpy(status, dSt.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    if (outDoubles == 0) return CSIM_OK;
+    if (const int r2 = spToHost(dY.as<double>(), F, PP, B, y)) return r2;
+    if (s) return spToHost(dS.as<double>(), F, PP, B, s);
     return CSIM_OK;
 }
 
@@ -1631,6 +1771,80 @@ int csim_noise_solve_batch(int32_t device, int32_t n, int32_t B, const double* G
                     y[dst] = h[src];
                     y[dst + 1] = h[src + 1];
                 }
+    }
+    if (flags) HIPCHK(hipMemcpy(flags, dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    return CSIM_OK;
+}
+
+// the engine-free counterpart for the S-parameter kernels: K right-hand sides per system, or (port_eq given) the
+// ports' unit vectors with Y and S
+int csim_sp_solve_batch(int32_t device, int32_t n, int32_t B, int32_t K, const double* G, const double* Cm, const double* J,
+                        const double* omega, int32_t F, int32_t kernel, double* x, uint32_t* flags, const int32_t* port_eq,
+                        const double* z0, double* y, double* s)
+{
+    const bool work = n > 0 && B > 0 && F > 0;
+    const bool ports = port_eq != nullptr;
+    if (n < 0 || B < 0 || F < 0 || kernel < csim::AC_KERNEL_AUTO || kernel > csim::AC_KERNEL_PACKED ||
+        (work && (!G || !Cm || !omega || (ports ? (!z0 || !y) : (!J || !x))))) {
+        setError("csim_sp_solve_batch: bad argument");
+        return CSIM_ERR_ARG;
+    }
+    if (K < 1 || K > csim::SP_MAX_PORTS) { setError("csim_sp_solve_batch: 1 to 4 right-hand sides / ports"); return CSIM_ERR_ARG; }
+    if (ports && n > 0)
+        for (int i = 0; i < K; ++i) {
+            if (port_eq[i] < 0 || port_eq[i] >= n) { setError("csim_sp_solve_batch: port equation out of range"); return CSIM_ERR_ARG; }
+            if (!(z0[i] > 0.0) || !std::isfinite(z0[i])) { setError("csim_sp_solve_batch: Z0 must be finite and > 0"); return CSIM_ERR_ARG; }
+        }
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
+        setError("csim_sp_solve_batch: no usable HIP device (this library has no CPU path)");
+        return CSIM_ERR_NO_DEVICE;
+    }
+    if (n > 63) { setError("csim_sp_solve_batch covers n <= 63"); return CSIM_ERR_UNSUPPORTED; }
+    int which = kernel;
+    if (which == csim::AC_KERNEL_AUTO) which = n <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
+    if (which == csim::AC_KERNEL_PACKED && n > 32) { setError("csim_sp_solve_batch: the packed kernel covers n <= 32"); return CSIM_ERR_UNSUPPORTED; }
+    if (!work) return CSIM_OK;
+    HIPCHK(hipSetDevice(device));
+    const std::vector<double> sys = packAcSystems(n, B, G, Cm, nullptr);
+    const size_t xDoubles = (size_t)2 * F * K * n * B, yDoubles = (size_t)2 * F * K * K * B;
+    const bool wantX = x != nullptr;
+    DevBuf dSys, dOmega, dJ, dX, dY, dS, dF;
+    HIPCHK(dSys.alloc(sizeof(double) * sys.size()));
+    HIPCHK(dOmega.alloc(sizeof(double) * (size_t)F));
+    HIPCHK(dF.alloc(sizeof(uint32_t) * (size_t)B));
+    HIPCHK(hipMemcpy(dSys.p, sys.data(), sizeof(double) * sys.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dOmega.p, omega, sizeof(double) * (size_t)F, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(dF.p, 0, sizeof(uint32_t) * (size_t)B));
+    csim::SpArgs a{};
+    a.N = n; a.K = K; a.P = ports ? K : 0; a.F = F; a.B = B; a.b0 = 0; a.Bc = B;
+    a.eps = 1e-15;
+    a.sys = dSys.as<double>();
+    a.omega = dOmega.as<double>();
+    a.status = dF.as<uint32_t>();
+    if (wantX) {
+        HIPCHK(dX.alloc(sizeof(double) * xDoubles));
+        HIPCHK(hipMemset(dX.p, 0, sizeof(double) * xDoubles));
+        a.x = dX.as<double>();
+    }
+    if (ports) {
+        for (int i = 0; i < K; ++i) { a.portEq[i] = port_eq[i]; a.sz[i] = std::sqrt(z0[i]); }
+        HIPCHK(dY.alloc(sizeof(double) * yDoubles));
+        a.y = dY.as<double>();
+        if (s) { HIPCHK(dS.alloc(sizeof(double) * yDoubles)); a.s = dS.as<double>(); }
+    } else {
+        HIPCHK(dJ.alloc(sizeof(double) * (size_t)2 * K * n * B));
+        HIPCHK(hipMemcpy(dJ.p, J, sizeof(double) * (size_t)2 * K * n * B, hipMemcpyHostToDevice));
+        a.rhs = dJ.as<double>();
+    }
+    HIPCHK(csim::launchSpSweep(which, a, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    if (wantX) {                                             // [F][K][n][B] -> [B][F][K][n]
+        if (const int rc = spToHost(dX.as<double>(), F, K * n, B, x)) return rc;
+    }
+    if (ports) {
+        if (const int rc = spToHost(dY.as<double>(), F, K * K, B, y)) return rc;
+        if (s) { if (const int rc = spToHost(dS.as<double>(), F, K * K, B, s)) return rc; }
     }
     if (flags) HIPCHK(hipMemcpy(flags, dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
     return CSIM_OK;

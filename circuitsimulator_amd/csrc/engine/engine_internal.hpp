@@ -129,6 +129,14 @@ struct csim_engine {
     double* dNoisePsd = nullptr;
     size_t noisePsdCap = 0;                // doubles
 
+    // S-parameter analysis: the netlist's .SP card and its ports in port order (branch equation, Z0); spPortError
+    // says what is wrong with the PORTNUM numbering, if anything
+    int spEnabled = 0, spSweep = 0, spPoints = 0;
+    double spFstart = 0.0, spFstop = 0.0;
+    std::vector<int32_t> spPortEq;
+    std::vector<double> spZ0;
+    std::string spPortError;
+
     std::vector<int> netlistProbes;        // .PLOTNV / .PRINT node-voltage probes of the netlist (default CSV columns)
 
     // probe list of the most recent transient call

@@ -110,6 +110,24 @@ hipError_t launchNoisePsd(const GenPlan& pl, const int32_t* dSrcElem, int S, con
                           const double* dXop, double kT4, double* dPsd, size_t psdStride, size_t psdOff, hipStream_t stream);
 hipError_t launchNoiseSweep(int which, const NoiseArgs& a, hipStream_t stream);
 
+// S-parameter analysis (kernels_sp.hip) on the systems launchAcAssemble leaves: one factorisation with K right-hand
+// sides per (instance, frequency).  P = K > 0: unit right-hand sides at portEq, Y (and S) formed on the device.
+// P = 0: the right-hand sides are given and only the solutions are stored (the engine-free test entry).
+struct SpArgs {
+    int N, K, P, F, B, b0, Bc;
+    int32_t portEq[4];                  // branch equations of the ports; checked by the launcher: they index LDS
+    double sz[4];                       // sqrt(Z0) of the ports
+    double eps;
+    const double* sys;
+    const double* omega;
+    const double* rhs;                  // [Bc][K][N] complex (P == 0)
+    double* x;                          // [F][K][N][B] complex or null (required when P == 0)
+    double* y;                          // [F][P][P][B] complex (P > 0)
+    double* s;                          // [F][P][P][B] complex or null
+    uint32_t* status;                   // [B], OR-ed
+};
+hipError_t launchSpSweep(int which, const SpArgs& a, hipStream_t stream);
+
 // layout helpers (transpose.hip): [rows][cols] <-> [cols][rows] of doubles
 hipError_t launchTranspose(const double* dIn, double* dOut, int rows, int cols, hipStream_t stream);
 

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstring>
 #include <fstream>
+#include <iostream>
 #include <sstream>
 
 #include "mc_draw.h"
@@ -54,6 +55,10 @@ int finishNetlist(csim_netlist* nl)
         for (std::size_t e = 0; e < nl->ckt.elements.size() && !nc.srcName.empty(); ++e)
             if (toLower(nl->ckt.elements[e]->getName()) == toLower(nc.srcName)) { nl->noiseSrcElem = static_cast<int>(e); break; }
     }
+
+    // PORTNUM tokens: the ports in port order
+    nl->portError = csim::portList(nl->cir, nl->ports);
+    if (!nl->portError.empty()) std::cerr << nl->portError << "\n";
 
     // reference CSV header: time, V(node) in node order, I(elem) for V sources
     // and inductors in element order (src/tanalisis.cpp:191-206) == equation order
@@ -196,6 +201,35 @@ int csim_netlist_noise_source(const csim_netlist* nl, int32_t i, int32_t* elem, 
     if (elem) *elem = src[static_cast<std::size_t>(i)].elem;
     if (eq_a) *eq_a = src[static_cast<std::size_t>(i)].a;
     if (eq_b) *eq_b = src[static_cast<std::size_t>(i)].b;
+    return CSIM_OK;
+}
+
+int csim_netlist_num_ports(const csim_netlist* nl)
+{
+    if (!nl) return CSIM_ERR_ARG;
+    if (!nl->portError.empty()) { csim::setError(nl->portError); return CSIM_ERR_CONFIG; }
+    return static_cast<int>(nl->ports.size());
+}
+
+int csim_netlist_port(const csim_netlist* nl, int32_t i, int32_t* elem, int32_t* branch_eq, double* z0)
+{
+    if (!nl || i < 0 || i >= static_cast<int32_t>(nl->ports.size())) { csim::setError("csim_netlist_port: bad index"); return CSIM_ERR_ARG; }
+    const csim::Port& p = nl->ports[static_cast<std::size_t>(i)];
+    if (elem) *elem = p.elem;
+    if (branch_eq) *branch_eq = p.branchEq;
+    if (z0) *z0 = p.z0;
+    return CSIM_OK;
+}
+
+int csim_netlist_sp(const csim_netlist* nl, int32_t* enabled, int32_t* sweep, int32_t* n_points, double* fstart, double* fstop)
+{
+    if (!nl) return CSIM_ERR_ARG;
+    const SpConfig& a = nl->sim.sp;
+    if (enabled)  *enabled = a.enabled ? 1 : 0;
+    if (sweep)    *sweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
+    if (n_points) *n_points = a.nPoints;
+    if (fstart)   *fstart = a.fstart;
+    if (fstop)    *fstop = a.fstop;
     return CSIM_OK;
 }
 

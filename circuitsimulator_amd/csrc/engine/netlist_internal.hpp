@@ -9,6 +9,10 @@
 #include "../api/parser.hpp"
 #include "../api/sim.hpp"
 
+namespace csim {
+struct Port { int32_t elem, branchEq; double z0; };     // a V source with PORTNUM k, its branch equation and Z0
+}
+
 struct csim_netlist {
     Circuit ckt;
     SimulationConfig sim;
@@ -17,6 +21,9 @@ struct csim_netlist {
     std::string csvHeader;
     // .NOISE card resolved to indices: output equations (-1 ground, -2 unknown node), input source element (-1 none)
     int noiseOutP = -2, noiseOutM = -1, noiseSrcElem = -1;
+    // the ports (PORTNUM) in port order, or what is wrong with their numbering
+    std::vector<csim::Port> ports;
+    std::string portError;
 };
 
 namespace csim {
@@ -34,5 +41,32 @@ inline std::vector<NoiseSource> noiseSources(const CircuitIR& c)
         else if (c.kind[e] == CSIM_NMOS || c.kind[e] == CSIM_PMOS) out.push_back({static_cast<int32_t>(e), q[0], q[2]});
     }
     return out;
+}
+
+// Ports of a circuit in port order (include/csim.h "S-parameter analysis"): V sources with PORTNUM 1 .. P.  Returns an
+// empty string, or what is wrong with the numbering (then `out` is empty).
+inline std::string portList(const CircuitIR& c, std::vector<Port>& out)
+{
+    out.clear();
+    std::vector<Port> found;
+    std::vector<int> num;
+    for (std::size_t e = 0; e < c.portNum.size(); ++e)
+        if (c.portNum[e] > 0) {
+            found.push_back({static_cast<int32_t>(e), c.branchEq[e], c.portZ0[e]});
+            num.push_back(c.portNum[e]);
+        }
+    const int P = static_cast<int>(found.size());
+    if (P > 4) return "ports: at most 4 ports (PORTNUM 1 .. 4)";
+    std::vector<Port> ordered(static_cast<std::size_t>(P));
+    std::vector<bool> seen(static_cast<std::size_t>(P), false);
+    for (int i = 0; i < P; ++i) {
+        const int k = num[static_cast<std::size_t>(i)];
+        if (k > P) return "ports: PORTNUM must run from 1 to the number of ports without a gap";
+        if (seen[static_cast<std::size_t>(k - 1)]) return "ports: PORTNUM " + std::to_string(k) + " is given twice";
+        seen[static_cast<std::size_t>(k - 1)] = true;
+        ordered[static_cast<std::size_t>(k - 1)] = found[static_cast<std::size_t>(i)];
+    }
+    out = ordered;
+    return std::string();
 }
 }

@@ -87,6 +87,36 @@ class Netlist:
             out.append((e.value, a.value, b.value))
         return out
 
+    @property
+    def ports(self):
+        """The ports (V sources with PORTNUM k [Z0 r]) in port order: [(element index, branch equation, Z0)].
+        Raises CsimError(CSIM_ERR_CONFIG) when the numbering has a gap or a duplicate or there are more than 4."""
+        L = capi.lib()
+        n = L.csim_netlist_num_ports(self._h)
+        if n < 0:
+            capi.check(n)
+        out = []
+        for i in range(n):
+            e, k, z = C.c_int32(), C.c_int32(), C.c_double()
+            capi.check(L.csim_netlist_port(self._h, i, C.byref(e), C.byref(k), C.byref(z)))
+            out.append((e.value, k.value, z.value))
+        return out
+
+    @property
+    def sp(self):
+        """The .SP card: None, or (sweep "dec" | "oct" | "lin", n_points, fstart, fstop)."""
+        en, sw, npt = C.c_int32(), C.c_int32(), C.c_int32()
+        f0, f1 = C.c_double(), C.c_double()
+        capi.check(capi.lib().csim_netlist_sp(self._h, C.byref(en), C.byref(sw), C.byref(npt), C.byref(f0), C.byref(f1)))
+        return (AC_SWEEPS[sw.value], npt.value, f0.value, f1.value) if en.value else None
+
+    def sp_freqs(self):
+        """Frequency grid of the .SP card (numpy, Hz)."""
+        card = self.sp
+        if card is None:
+            raise capi.CsimError(capi.CSIM_ERR_CONFIG, "the netlist has no .SP card")
+        return ac_freqs(*card)
+
     def ac_freqs(self):
         """Frequency grid of the .AC card (numpy, Hz)."""
         if self.ac is None:
@@ -223,7 +253,7 @@ class Engine:
         capi.check(capi.lib().csim_engine_set_option(self._h, str(key).encode(), str(value).encode()))
 
     def stat(self, key):
-        """csim_engine_stat: "near_verified", "near_rolled_back" (include/csim.h)"""
+        """csim_engine_stat: "near_verified", "near_rolled_back", "ac_chunk" (include/csim.h)"""
         return int(capi.lib().csim_engine_stat(self._h, str(key).encode()))
 
     # -- device-pointer forms (torch tensors on cuda:<device>, slot-major) ----
@@ -394,6 +424,40 @@ class Engine:
                                                float(temp), on.ctypes.data, ptr(g), ptr(con), ptr(ps), st.ctypes.data))
         return dict(freqs=f, onoise=on, gain=g[..., 0] + 1j * g[..., 1] if g is not None else None, contrib=con, psd=ps,
                     status=st)
+
+    def sp(self, params, x_op, freqs=None, want_s=True, status=None):
+        """S-parameter sweep of the batch around the operating points x_op (device [N][B], from dc());
+        csim_sp_batch_dev.  freqs: Hz, None = the .SP card.
+        -> dict(freqs, y complex [F][P][P][B], s the same or None, status [B]); device tensors; status is OR-ed into
+        `status` when given."""
+        torch = _torch()
+        B = params.shape[1]
+        f = self.netlist.sp_freqs() if freqs is None else np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        P = len(self.netlist.ports)
+        dev = self._dev()
+        y = torch.zeros((len(f), P, P, B, 2), dtype=torch.float64, device=dev)
+        s = torch.zeros((len(f), P, P, B, 2), dtype=torch.float64, device=dev) if want_s else None
+        st = status if status is not None else torch.zeros(B, dtype=torch.int32, device=dev)
+        capi.check(capi.lib().csim_sp_batch_dev(self._h, params.data_ptr(), B, x_op.data_ptr(), f.ctypes.data, len(f),
+                                                y.data_ptr(), s.data_ptr() if s is not None else None, st.data_ptr(),
+                                                self._stream()))
+        return dict(freqs=f, y=torch.view_as_complex(y), s=torch.view_as_complex(s) if s is not None else None, status=st)
+
+    def sp_host(self, params=None, B=1, freqs=None, want_s=True):
+        """DC operating point + S-parameter sweep (csim_sp_batch): numpy, instance-major.
+        -> dict(freqs, y complex [B][F][P][P], s the same or None, status [B])"""
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=np.float64)
+            B = params.shape[0]
+        f = self.netlist.sp_freqs() if freqs is None else np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        P = len(self.netlist.ports)
+        y = np.zeros((B, len(f), P, P), dtype=np.complex128)
+        s = np.zeros((B, len(f), P, P), dtype=np.complex128) if want_s else None
+        st = np.zeros(B, dtype=np.uint32)
+        capi.check(capi.lib().csim_sp_batch(self._h, params.ctypes.data if params is not None else None, B, f.ctypes.data,
+                                            len(f), y.ctypes.data, s.ctypes.data if s is not None else None,
+                                            st.ctypes.data))
+        return dict(freqs=f, y=y, s=s, status=st)
 
     def dc_host(self, params=None, B=1):
         if params is not None:
@@ -639,6 +703,40 @@ def noise_solve_batch(G, Cm, out, src_a, src_b, psd, omega, gain_in=None, kernel
         onoise.ctypes.data, contrib.ctypes.data, gain.ctypes.data if gain is not None else None,
         y.ctypes.data if y is not None else None, flags.ctypes.data))
     return dict(onoise=onoise, contrib=contrib, gain=gain, y=y, flags=flags)
+
+
+def sp_solve_batch(G, Cm, J, omega, kernel="auto", device=0, port_eq=None, z0=None, want_s=True):
+    """The S-parameter kernels on systems given directly (csim_sp_solve_batch): (G + j w C) X = J with K = 1 .. 4
+    right-hand sides.  G, Cm [B][n][n] real; omega [F] rad/s; kernel auto | wave | packed.
+    J [B][K][n] complex -> (x complex [B][F][K][n], flags [B]).
+    With port_eq [P] and z0 [P] (J is ignored, may be None) the right-hand sides are the unit vectors at port_eq
+    -> dict(x [B][F][P][n], y [B][F][P][P], s the same or None, flags [B])."""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    Cm = np.ascontiguousarray(Cm, dtype=np.float64)
+    omega = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
+    B, n, F = G.shape[0], G.shape[1], len(omega)
+    which = ("auto", "wave", "packed").index(kernel)
+    flags = np.zeros(B, dtype=np.uint32)
+    L = capi.lib()
+    if port_eq is None:
+        J = np.ascontiguousarray(J, dtype=np.complex128)
+        K = J.shape[1] if J.ndim == 3 else 0
+        x = np.zeros((B, F, K, n), dtype=np.complex128)
+        capi.check(L.csim_sp_solve_batch(device, n, B, K, G.ctypes.data, Cm.ctypes.data, J.ctypes.data, omega.ctypes.data,
+                                         F, which, x.ctypes.data, flags.ctypes.data, None, None, None, None))
+        return x, flags
+    pe = np.ascontiguousarray(port_eq, dtype=np.int32).reshape(-1)
+    z = np.ascontiguousarray(z0, dtype=np.float64).reshape(-1)
+    P = len(pe)
+    if len(z) != P:
+        raise ValueError("port_eq and z0 differ in length")
+    x = np.zeros((B, F, P, n), dtype=np.complex128)
+    y = np.zeros((B, F, P, P), dtype=np.complex128)
+    s = np.zeros((B, F, P, P), dtype=np.complex128) if want_s else None
+    capi.check(L.csim_sp_solve_batch(device, n, B, P, G.ctypes.data, Cm.ctypes.data, None, omega.ctypes.data, F, which,
+                                     x.ctypes.data, flags.ctypes.data, pe.ctypes.data, z.ctypes.data, y.ctypes.data,
+                                     s.ctypes.data if s is not None else None))
+    return dict(x=x, y=y, s=s, flags=flags)
 
 
 def gs_solve_batch(A, b, x0=None, max_iters=1000, tol=1e-10, device=0):

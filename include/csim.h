@@ -78,7 +78,7 @@ extern "C" {
 #define CSIM_ERR_HIP          -4   /* a HIP runtime call failed                    */
 #define CSIM_ERR_UNSUPPORTED  -5   /* circuit outside what the kernels cover       */
 #define CSIM_ERR_EMPTY        -6   /* circuit has no unknowns                      */
-#define CSIM_ERR_CONFIG       -7   /* invalid .TRAN / .AC / .NOISE numbers, no AC source */
+#define CSIM_ERR_CONFIG       -7   /* invalid .TRAN / .AC / .NOISE numbers, no AC source, no port */
 
 typedef struct csim_netlist csim_netlist;
 typedef struct csim_engine  csim_engine;
@@ -139,6 +139,15 @@ int  csim_netlist_noise(const csim_netlist* nl, int32_t* enabled, int32_t* out_p
  * generator lies between (-1: ground).  Resistors between their terminals, MOSFET channels drain - source.    */
 int  csim_netlist_num_noise_sources(const csim_netlist* nl);
 int  csim_netlist_noise_source(const csim_netlist* nl, int32_t i, int32_t* elem, int32_t* eq_a, int32_t* eq_b);
+/* Ports of "S-parameter analysis" below: V sources carrying `PORTNUM k [Z0 r]`, in port order (port k is index k - 1).
+ * The values are kept beside the IR like the AC excitation: P, the slots and the Monte-Carlo draws are those of the
+ * netlist without the tokens.  csim_netlist_num_ports: the number of ports (0 .. 4), or CSIM_ERR_CONFIG when the
+ * numbering has a gap or a duplicate, or there are more than 4 ports.                                              */
+int  csim_netlist_num_ports(const csim_netlist* nl);
+int  csim_netlist_port(const csim_netlist* nl, int32_t i, int32_t* elem, int32_t* branch_eq, double* z0);
+/* .SP DEC|OCT|LIN n fstart fstop: the sweep as for .AC */
+int  csim_netlist_sp(const csim_netlist* nl, int32_t* enabled, int32_t* sweep, int32_t* n_points, double* fstart,
+                     double* fstop);
 /* Monte-Carlo recipe per parameter slot: 0 fixed, 1 scaled by (1+sigma z),
  * 2 MOS K rebuilt from a MU draw: K = (MU(1+sigma z))*COX*(W/L)              */
 int  csim_netlist_mc_kinds(const csim_netlist* nl, int32_t* kinds);
@@ -190,7 +199,7 @@ int  csim_engine_set_kernel(csim_engine* eng, int32_t which);
  *   near_test_rollback (0)                  test aid: every verified near-threshold decision is treated as a
  *                                           mismatch, so the roll-back path runs (results must not change)
  *   hybrid_sync (CSIM_HYBRID_SYNC, 1)       see "Streams" above
- *   ac_kernel (auto)                        test aid: AC and noise sweep kernel, auto | wave | packed (see csim_ac_batch_dev)
+ *   ac_kernel (auto)                        test aid: AC, noise and S-parameter sweep kernel, auto | wave | packed (see csim_ac_batch_dev)
  *   dc_fast (CSIM_DC_FAST, 0)               DC operating points start on the fast generated kernel (FMA
  *                                           contraction, reciprocal pivots; controller decisions within
  *                                           its rounding noise are replayed) instead of the faithful one
@@ -200,7 +209,10 @@ int  csim_engine_set_option(csim_engine* eng, const char* key, const char* value
  * (hybrid_sync = 1) only:
  *   "near_verified"      near-threshold convergence decisions of the fast transient kernels that the
  *                        faithful kernel re-did (src/tanalisis.cpp:369; DESIGN.md "near-threshold guard")
- *   "near_rolled_back"   of those, the ones whose pass count differed: the instance was rolled back      */
+ *   "near_rolled_back"   of those, the ones whose pass count differed: the instance was rolled back
+ * A constant of the engine, in any mode:
+ *   "ac_chunk"           the largest number of instances the small-signal sweeps (AC, noise, S-parameter)
+ *                        assemble and solve at once; a larger batch runs in chunks of this size           */
 int64_t csim_engine_stat(const csim_engine* eng, const char* key);
 
 /* Monte-Carlo parameter table on the device: instance b_first+i of the global
@@ -347,6 +359,42 @@ int  csim_noise_batch(csim_engine* eng, const double* params, int32_t B, const d
                       int32_t out_p_eq, int32_t out_m_eq, int32_t src_elem, double temp_k, double* onoise,
                       double* gain, double* contrib, double* psd, uint32_t* status);
 
+/* ---- S-parameter analysis (.SP; Y and S of the declared ports by one factorisation per frequency) ----
+ * Ports.  A V source becomes port k by `PORTNUM k [Z0 r]` after its DC / waveform / AC tokens (ngspice's spelling,
+ *   any case).  k runs 1 .. P without a gap or a duplicate, P <= 4; Z0 defaults to 50 and must be finite and > 0.
+ *   PORTNUM on anything but a V source is a parse error (reported, the statement dropped, like the other card
+ *   errors).  Card: `.SP DEC|OCT|LIN n fstart fstop`, the grid of csim_ac_freqs.
+ * System.  For instance b and angular frequency w, A = G + j w C is exactly the matrix of "AC analysis" above: the
+ *   same assembly, the same elements left out, tran_gmin.  For port j the right-hand side is the real unit vector at
+ *   the branch equation k_j of its V source.  Every `AC mag` of the netlist is ignored; all other V sources are AC
+ *   shorts and I sources open, which is what a zero right-hand side says.
+ * Multi-RHS solve.  The AC algorithm carried to K right-hand-side columns n .. n+K-1 of the augmented matrix: pivot
+ *   search, exchange, multiplier and zero-multiplier skip unchanged; the elimination runs j = k+1 .. n+K-1; the back
+ *   substitution runs per column.  Pivoting never looks at a right-hand side, so column c of the result is bit for
+ *   bit the single-RHS solve with that column alone.  A column maximum below lu_eps^2 makes all K vectors +0.0 and
+ *   sets CSIM_ST_LU_TINY_PIVOT.
+ * Y(i,j) = -x(j)[k_i], both parts negated: the branch current of the V-source stamp flows from the + node through
+ *   the source to the - node, the current into the network at + is its negative.  A resistor R across a single port
+ *   gives Y = +1/R.
+ * S.  s_i = sqrt(Z0_i), computed once on the host.  M(i,j) = delta_ij + (s_i * Y(i,j)) * s_j, the two products in
+ *   that order on re and im separately, the diagonal as 1.0 + re.  M X = 2 I by the same multi-RHS solve with n = P,
+ *   K = P and the same lu_eps.  S(i,j) = X(i,j) - delta_ij, only the real part and only on the diagonal touched:
+ *   S = (I - y)(I + y)^-1 = 2 (I + y)^-1 - I with y the normalised admittance.
+ * Failures.  M fails its pivot test: S of that (instance, frequency) is all +0.0, Y is kept, the flag is set.  A
+ *   fails: Y and S are both +0.0.  The sweep goes on either way.
+ * No FMA contraction anywhere.  Circuits of up to 63 unknowns (CSIM_ERR_UNSUPPORTED beyond); no port, or a bad port
+ * numbering: CSIM_ERR_CONFIG.  No AC source is needed.
+ *
+ * Enqueues the sweep; never waits for it; frequency lists as csim_ac_batch_dev (same buffers, same discipline).
+ *   d_y, d_s [F][P][P][B] complex (re, im), row i then column j, instance fastest; d_s may be NULL; d_status [B], OR-ed
+ * The engine option ac_kernel picks the kernel as for AC; both give bit-identical results.                        */
+int  csim_sp_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int32_t B, const double* d_xop,
+                       const double* freqs, int32_t F, double* d_y, double* d_s, uint32_t* d_status, void* stream);
+/* DC operating point, then the sweep.  params [B][P] or NULL (nominal); freqs NULL = the grid of the netlist's .SP
+ * card (F ignored; no card: CSIM_ERR_CONFIG).  y, s [B][F][P][P] complex; s may be NULL.                           */
+int  csim_sp_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F, double* y,
+                   double* s, uint32_t* status);
+
 /* Batched dense solve A x = b with the engine's pivoted LU
  * (Solver::solveLinearSystemLU semantics: first-maximum partial pivoting,
  * tiny pivot -> zero vector).  A [B][n][n] row-major, b/x [B][n], host
@@ -374,6 +422,17 @@ int  csim_noise_solve_batch(int32_t device, int32_t n, int32_t B, const double* 
                             int32_t out_m, int32_t S, const int32_t* src_a, const int32_t* src_b, const double* psd,
                             int32_t in_kind, int32_t in_a, int32_t in_b, const double* omega, int32_t F,
                             int32_t kernel, double* onoise, double* contrib, double* gain, double* y, uint32_t* flags);
+
+/* The S-parameter kernels on systems given directly (host pointers; lu_eps = 1e-15), the counterpart of
+ * csim_ac_solve_batch for "S-parameter analysis".  G, C [B][n][n] row-major; omega [F] rad/s; 1 <= K <= 4.
+ *   port_eq == NULL: K right-hand sides J [B][K][n] complex, solutions x [B][F][K][n] complex.
+ *   port_eq [K], z0 [K]: the right-hand sides are the unit vectors at port_eq (J is not read); y [B][F][K][K] complex,
+ *   s the same or NULL, x optional.
+ * flags [B] optional.  kernel and sizes as csim_ac_solve_batch; K outside 1 .. 4, an equation out of range or a Z0
+ * that is not finite and > 0: CSIM_ERR_ARG.                                                                        */
+int  csim_sp_solve_batch(int32_t device, int32_t n, int32_t B, int32_t K, const double* G, const double* C,
+                         const double* J, const double* omega, int32_t F, int32_t kernel, double* x, uint32_t* flags,
+                         const int32_t* port_eq, const double* z0, double* y, double* s);
 
 /* ---- Gauss-Seidel variant of the reference (never reached from its main(), kept as public API) ----
  * Batched Solver::solveLinearSystemGaussSeidel (include/solver.hpp:139-204): sweeps in row order with the
