@@ -5,10 +5,7 @@
 // port: the real unit vector at the branch equation of the port's V source.  The kernels (kernels_sp.hip) and the
 // sequential routines below share ac_lu.hpp's primitives and their order:
 //
-//   multi-RHS solve  ac_lu_solve() with K right-hand-side columns n .. n+K-1: pivot search, exchange, multiplier and
-//                    zero-multiplier skip unchanged, elimination over j = k+1 .. n+K-1, back substitution per column.
-//                    Pivoting never looks at a right-hand side: column c of the result is bit for bit the single-RHS
-//                    solve with that column alone.  A failed factorisation zeroes all K vectors.
+//   multi-RHS solve  ac_lu.hpp ac_lu_solve_multi(), one column per port
 //   Y                Y(i,j) = -x(j)[k_i], both parts negated (the branch current flows from + through the source)
 //   S                M(i,j) = delta_ij + (s_i Y(i,j)) s_j with s_i = sqrt(Z0_i), the two products in that order on re
 //                    and im separately, the diagonal as 1.0 + re;  M X = 2 I by the same multi-RHS solve (n = K = P);
@@ -25,55 +22,6 @@
 namespace csim {
 
 enum { SP_MAX_PORTS = 4 };
-
-// ac_lu_solve() carried to K right-hand sides: augmented matrix on re/im planes, row i at i * ld, RHS c in column
-// n + c (ld >= n + K).  Solution c goes to xr/xi[c * ldx + 0 .. n-1].  Returns CSIM_ST_* flags.
-CSIM_AC_HD inline unsigned ac_lu_solve_multi(int n, int K, int ld, double* ar, double* ai, double eps, double* xr,
-                                             double* xi, int ldx)
-{
-    const double eps2 = eps * eps;
-    const int w = n + K;
-    for (int k = 0; k < n; ++k) {
-        int piv = k;
-        double maxv = cpx_abs2({ar[k * ld + k], ai[k * ld + k]});
-        if (maxv == maxv) {
-            for (int i = k + 1; i < n; ++i) {
-                const double v = cpx_abs2({ar[i * ld + k], ai[i * ld + k]});
-                if (v > maxv) { maxv = v; piv = i; }
-            }
-        }
-        if (maxv < eps2) {
-            for (int c = 0; c < K; ++c)
-                for (int i = 0; i < n; ++i) { xr[c * ldx + i] = 0.0; xi[c * ldx + i] = 0.0; }
-            return CSIM_ST_LU_TINY_PIVOT;
-        }
-        if (piv != k)
-            for (int j = k; j < w; ++j) {
-                double t = ar[k * ld + j]; ar[k * ld + j] = ar[piv * ld + j]; ar[piv * ld + j] = t;
-                t = ai[k * ld + j]; ai[k * ld + j] = ai[piv * ld + j]; ai[piv * ld + j] = t;
-            }
-        const cpx p = {ar[k * ld + k], ai[k * ld + k]};
-        for (int i = k + 1; i < n; ++i) {
-            const cpx l = cpx_div({ar[i * ld + k], ai[i * ld + k]}, p);
-            if (cpx_is_zero(l)) continue;
-            for (int j = k + 1; j < w; ++j) {
-                const cpx r = cpx_elim({ar[i * ld + j], ai[i * ld + j]}, l, {ar[k * ld + j], ai[k * ld + j]});
-                ar[i * ld + j] = r.re;
-                ai[i * ld + j] = r.im;
-            }
-        }
-    }
-    for (int c = 0; c < K; ++c)
-        for (int i = n - 1; i >= 0; --i) {
-            cpx s = {ar[i * ld + n + c], ai[i * ld + n + c]};
-            for (int j = i + 1; j < n; ++j)
-                s = cpx_sub(s, cpx_mul({ar[i * ld + j], ai[i * ld + j]}, {xr[c * ldx + j], xi[c * ldx + j]}));
-            const cpx x = cpx_div(s, {ar[i * ld + i], ai[i * ld + i]});
-            xr[c * ldx + i] = x.re;
-            xi[c * ldx + i] = x.im;
-        }
-    return 0u;
-}
 
 // Y [P][P] (row i, column j) from the P solutions (solution j at x[j * ldx ...]); all +0.0 when A failed
 CSIM_AC_HD inline void sp_read_y(int P, const int32_t* portEq, bool failed, const double* xr, const double* xi, int ldx,

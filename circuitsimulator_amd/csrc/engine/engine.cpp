@@ -966,6 +966,23 @@ int csim_ac_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const
     return CSIM_OK;
 }
 
+// [F][X][B] on the device, W doubles per entry (1: real, 2: complex) -> [B][F][X] on the host
+static int toHost(const double* dSrc, int F, int X, int B, int W, double* dst)
+{
+    const size_t n = (size_t)W * F * X * B;
+    if (n == 0) return CSIM_OK;
+    std::vector<double> h(n);
+    HIPCHK(hipMemcpy(h.data(), dSrc, sizeof(double) * n, hipMemcpyDeviceToHost));
+    for (int f = 0; f < F; ++f)
+        for (int t = 0; t < X; ++t)
+            for (int b = 0; b < B; ++b) {
+                const size_t src = (((size_t)f * X + t) * B + b) * W;
+                const size_t at = (((size_t)b * F + f) * X + t) * W;
+                for (int k = 0; k < W; ++k) dst[at + k] = h[src + k];
+            }
+    return CSIM_OK;
+}
+
 int csim_ac_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F,
                   const int32_t* probe_eq, int32_t n_probe, double* out, uint32_t* status)
 {
@@ -1001,18 +1018,7 @@ int csim_ac_batch(csim_engine* eng, const double* params, int32_t B, const doubl
     if (rc) return rc;
     HIPCHK(hipDeviceSynchronize());
     if (status) HIPCHK(hipMemcpy(status, dSt.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    if (outDoubles == 0) return CSIM_OK;
-    std::vector<double> h(outDoubles);                       // [F][n_probe][B] -> [B][F][n_probe]
-    HIPCHK(hipMemcpy(h.data(), dOut.p, sizeof(double) * outDoubles, hipMemcpyDeviceToHost));
-    for (int f = 0; f < F; ++f)
-        for (int p = 0; p < nProbe; ++p)
-            for (int b = 0; b < B; ++b) {
-                const size_t src = (((size_t)f * nProbe + p) * B + b) * 2;
-                const size_t dst = (((size_t)b * F + f) * nProbe + p) * 2;
-                out[dst] = h[src];
-                out[dst + 1] = h[src + 1];
-            }
-    return CSIM_OK;
+    return toHost(dOut.as<double>(), F, std::max(nProbe, 0), B, 2, out);
 }
 
 // ---- noise analysis ---------------------------------------------------------
@@ -1166,34 +1172,10 @@ int csim_noise_batch(csim_engine* eng, const double* params, int32_t B, const do
     if (rc) return rc;
     HIPCHK(hipDeviceSynchronize());
     if (status) HIPCHK(hipMemcpy(status, dSt.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    std::vector<double> h;
-    if (FB) {                                                // [F][B] -> [B][F]
-        h.resize(2 * FB);
-        HIPCHK(hipMemcpy(h.data(), dOn.p, sizeof(double) * FB, hipMemcpyDeviceToHost));
-        for (int f = 0; f < F; ++f)
-            for (int b = 0; b < B; ++b) onoise[(size_t)b * F + f] = h[(size_t)f * B + b];
-        if (wantGain) {
-            HIPCHK(hipMemcpy(h.data(), dGain.p, sizeof(double) * 2 * FB, hipMemcpyDeviceToHost));
-            for (int f = 0; f < F; ++f)
-                for (int b = 0; b < B; ++b) {
-                    gain[((size_t)b * F + f) * 2] = h[((size_t)f * B + b) * 2];
-                    gain[((size_t)b * F + f) * 2 + 1] = h[((size_t)f * B + b) * 2 + 1];
-                }
-        }
-    }
-    if (contrib && FB && S) {                                // [F][S][B] -> [B][F][S]
-        h.resize(FB * (size_t)S);
-        HIPCHK(hipMemcpy(h.data(), dCon.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
-        for (int f = 0; f < F; ++f)
-            for (int s = 0; s < S; ++s)
-                for (int b = 0; b < B; ++b) contrib[((size_t)b * F + f) * S + s] = h[((size_t)f * S + s) * B + b];
-    }
-    if (psd && S && F) {                                     // [S][B] -> [B][S]
-        h.resize((size_t)S * B);
-        HIPCHK(hipMemcpy(h.data(), dPsd.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
-        for (int s = 0; s < S; ++s)
-            for (int b = 0; b < B; ++b) psd[(size_t)b * S + s] = h[(size_t)s * B + b];
-    }
+    if ((rc = toHost(dOn.as<double>(), F, 1, B, 1, onoise))) return rc;
+    if (wantGain && (rc = toHost(dGain.as<double>(), F, 1, B, 2, gain))) return rc;
+    if (contrib && (rc = toHost(dCon.as<double>(), F, S, B, 1, contrib))) return rc;
+    if (psd && F) return toHost(dPsd.as<double>(), 1, S, B, 1, psd);           // [S][B] -> [B][S]
     return CSIM_OK;
 }
 
@@ -1257,24 +1239,6 @@ int csim_sp_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const
     return CSIM_OK;
 }
 
-// [F][P][P][B] complex on the device -> [B][F][P][P] on the host
-static int spToHost(const double* dSrc, int F, int PP, int B, double* dst)
-{
-    const size_t n = (size_t)2 * F * PP * B;
-    if (n == 0) return CSIM_OK;
-    std::vector<double> h(n);
-    HIPCHK(hipMemcpy(h.data(), dSrc, sizeof(double) * n, hipMemcpyDeviceToHost));
-    for (int f = 0; f < F; ++f)
-        for (int t = 0; t < PP; ++t)
-            for (int b = 0; b < B; ++b) {
-                const size_t src = (((size_t)f * PP + t) * B + b) * 2;
-                const size_t at = (((size_t)b * F + f) * PP + t) * 2;
-                dst[at] = h[src];
-                dst[at + 1] = h[src + 1];
-            }
-    return CSIM_OK;
-}
-
 int csim_sp_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F, double* y, double* s,
                   uint32_t* status)
 {
@@ -1313,9 +1277,8 @@ int csim_sp_batch(csim_engine* eng, const double* params, int32_t B, const doubl
     if (rc) return rc;
     HIPCHK(hipDeviceSynchronize());
     if (status) HIPCHK(hipMemcpy(status, dSt.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    if (outDoubles == 0) return CSIM_OK;
-    if (const int r2 = spToHost(dY.as<double>(), F, PP, B, y)) return r2;
-    if (s) return spToHost(dS.as<double>(), F, PP, B, s);
+    if ((rc = toHost(dY.as<double>(), F, PP, B, 2, y))) return rc;
+    if (s) return toHost(dS.as<double>(), F, PP, B, 2, s);
     return CSIM_OK;
 }
 
@@ -1616,6 +1579,37 @@ static std::vector<double> packAcSystems(int n, int B, const double* G, const do
     return sys;
 }
 
+// The common front of the engine-free *_solve_batch entries: device check, kernel choice and its refusals; then, when
+// there is work, the packed systems, the angular frequencies and zeroed flags on the device.
+struct AcSolveFront {
+    int which = csim::AC_KERNEL_AUTO;
+    DevBuf dSys, dOmega, dF;
+};
+static int acSolveFront(const char* entry, int device, int n, int B, const double* G, const double* Cm, const double* J,
+                        const double* omega, int F, int kernel, bool work, AcSolveFront& fr)
+{
+    const std::string name(entry);
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
+        setError(name + ": no usable HIP device (this library has no CPU path)");
+        return CSIM_ERR_NO_DEVICE;
+    }
+    if (n > 63) { setError(name + " covers n <= 63"); return CSIM_ERR_UNSUPPORTED; }
+    fr.which = kernel;
+    if (fr.which == csim::AC_KERNEL_AUTO) fr.which = n <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
+    if (fr.which == csim::AC_KERNEL_PACKED && n > 32) { setError(name + ": the packed kernel covers n <= 32"); return CSIM_ERR_UNSUPPORTED; }
+    if (!work) return CSIM_OK;
+    HIPCHK(hipSetDevice(device));
+    const std::vector<double> sys = packAcSystems(n, B, G, Cm, J);
+    HIPCHK(fr.dSys.alloc(sizeof(double) * sys.size()));
+    HIPCHK(fr.dOmega.alloc(sizeof(double) * (size_t)F));
+    HIPCHK(fr.dF.alloc(sizeof(uint32_t) * (size_t)B));
+    HIPCHK(hipMemcpy(fr.dSys.p, sys.data(), sizeof(double) * sys.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(fr.dOmega.p, omega, sizeof(double) * (size_t)F, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(fr.dF.p, 0, sizeof(uint32_t) * (size_t)B));
+    return CSIM_OK;
+}
+
 // the complex counterpart: any (G + jwC) x = J through the AC sweep kernels, without an engine or a netlist
 int csim_ac_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* Cm, const double* J,
                         const double* omega, int32_t F, int32_t kernel, double* x, uint32_t* flags)
@@ -1625,42 +1619,19 @@ int csim_ac_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, c
         setError("csim_ac_solve_batch: bad argument");
         return CSIM_ERR_ARG;
     }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
-        setError("csim_ac_solve_batch: no usable HIP device (this library has no CPU path)");
-        return CSIM_ERR_NO_DEVICE;
-    }
-    if (n > 63) { setError("csim_ac_solve_batch covers n <= 63"); return CSIM_ERR_UNSUPPORTED; }
-    int which = kernel;
-    if (which == csim::AC_KERNEL_AUTO) which = n <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
-    if (which == csim::AC_KERNEL_PACKED && n > 32) { setError("csim_ac_solve_batch: the packed kernel covers n <= 32"); return CSIM_ERR_UNSUPPORTED; }
-    if (n == 0 || B == 0 || F == 0) return CSIM_OK;
-    HIPCHK(hipSetDevice(device));
-    const std::vector<double> sys = packAcSystems(n, B, G, Cm, J);
+    const bool work = n > 0 && B > 0 && F > 0;
+    AcSolveFront fr;
+    if (const int rc = acSolveFront("csim_ac_solve_batch", device, n, B, G, Cm, J, omega, F, kernel, work, fr)) return rc;
+    if (!work) return CSIM_OK;
     const size_t outDoubles = (size_t)2 * F * n * B;
-    DevBuf dSys, dOmega, dOut, dF;
-    HIPCHK(dSys.alloc(sizeof(double) * sys.size()));
-    HIPCHK(dOmega.alloc(sizeof(double) * (size_t)F));
+    DevBuf dOut;
     HIPCHK(dOut.alloc(sizeof(double) * outDoubles));
-    HIPCHK(dF.alloc(sizeof(uint32_t) * (size_t)B));
-    HIPCHK(hipMemcpy(dSys.p, sys.data(), sizeof(double) * sys.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dOmega.p, omega, sizeof(double) * (size_t)F, hipMemcpyHostToDevice));
     HIPCHK(hipMemset(dOut.p, 0, sizeof(double) * outDoubles));
-    HIPCHK(hipMemset(dF.p, 0, sizeof(uint32_t) * (size_t)B));
-    HIPCHK(csim::launchAcSweep(which, n, dSys.as<double>(), dOmega.as<double>(), F, nullptr, n, B, 0, B, 1e-15,
-                               dOut.as<double>(), dF.as<uint32_t>(), nullptr));
+    HIPCHK(csim::launchAcSweep(fr.which, n, fr.dSys.as<double>(), fr.dOmega.as<double>(), F, nullptr, n, B, 0, B, 1e-15,
+                               dOut.as<double>(), fr.dF.as<uint32_t>(), nullptr));
     HIPCHK(hipDeviceSynchronize());
-    std::vector<double> h(outDoubles);                       // [F][n][B] -> [B][F][n]
-    HIPCHK(hipMemcpy(h.data(), dOut.p, sizeof(double) * outDoubles, hipMemcpyDeviceToHost));
-    for (int f = 0; f < F; ++f)
-        for (int p = 0; p < n; ++p)
-            for (int b = 0; b < B; ++b) {
-                const size_t src = (((size_t)f * n + p) * B + b) * 2;
-                const size_t dst = (((size_t)b * F + f) * n + p) * 2;
-                x[dst] = h[src];
-                x[dst + 1] = h[src + 1];
-            }
-    if (flags) HIPCHK(hipMemcpy(flags, dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    if (const int rc = toHost(dOut.as<double>(), F, n, B, 2, x)) return rc;
+    if (flags) HIPCHK(hipMemcpy(flags, fr.dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
     return CSIM_OK;
 }
 
@@ -1685,49 +1656,34 @@ int csim_noise_solve_batch(int32_t device, int32_t n, int32_t B, const double* G
         if (in_kind == csim::NOISE_IN_I) ok = ok && in_a >= -1 && in_a < n && in_b >= -1 && in_b < n;
         if (!ok) { setError("csim_noise_solve_batch: equation index out of range (or out_p == out_m)"); return CSIM_ERR_ARG; }
     }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
-        setError("csim_noise_solve_batch: no usable HIP device (this library has no CPU path)");
-        return CSIM_ERR_NO_DEVICE;
-    }
-    if (n > 63) { setError("csim_noise_solve_batch covers n <= 63"); return CSIM_ERR_UNSUPPORTED; }
-    int which = kernel;
-    if (which == csim::AC_KERNEL_AUTO) which = n <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
-    if (which == csim::AC_KERNEL_PACKED && n > 32) { setError("csim_noise_solve_batch: the packed kernel covers n <= 32"); return CSIM_ERR_UNSUPPORTED; }
+    AcSolveFront fr;
+    if (const int rc = acSolveFront("csim_noise_solve_batch", device, n, B, G, Cm, nullptr, omega, F, kernel, work, fr)) return rc;
     if (!work) return CSIM_OK;
-    HIPCHK(hipSetDevice(device));
-    const std::vector<double> sys = packAcSystems(n, B, G, Cm, nullptr);
     std::vector<double> psdT((size_t)S * B);                 // [B][S] -> [S][B]
     for (int b = 0; b < B; ++b)
         for (int s = 0; s < S; ++s) psdT[(size_t)s * B + b] = psd[(size_t)b * S + s];
     const size_t FB = (size_t)F * (size_t)B;
     const bool wantGain = gain && in_kind != csim::NOISE_IN_NONE;
-    DevBuf dSys, dOmega, dA, dB, dPsd, dOn, dCon, dGain, dY, dF;
-    HIPCHK(dSys.alloc(sizeof(double) * sys.size()));
-    HIPCHK(dOmega.alloc(sizeof(double) * (size_t)F));
+    DevBuf dA, dB, dPsd, dOn, dCon, dGain, dY;
     HIPCHK(dA.alloc(sizeof(int32_t) * (size_t)S));
     HIPCHK(dB.alloc(sizeof(int32_t) * (size_t)S));
     HIPCHK(dPsd.alloc(sizeof(double) * psdT.size()));
     HIPCHK(dOn.alloc(sizeof(double) * FB));
-    HIPCHK(dF.alloc(sizeof(uint32_t) * (size_t)B));
     if (contrib) HIPCHK(dCon.alloc(sizeof(double) * FB * (size_t)S));
     if (wantGain) HIPCHK(dGain.alloc(sizeof(double) * 2 * FB));
     if (y) HIPCHK(dY.alloc(sizeof(double) * 2 * FB * (size_t)n));
-    HIPCHK(hipMemcpy(dSys.p, sys.data(), sizeof(double) * sys.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dOmega.p, omega, sizeof(double) * (size_t)F, hipMemcpyHostToDevice));
     if (S > 0) {
         HIPCHK(hipMemcpy(dA.p, src_a, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(dB.p, src_b, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(dPsd.p, psdT.data(), sizeof(double) * psdT.size(), hipMemcpyHostToDevice));
     }
-    HIPCHK(hipMemset(dF.p, 0, sizeof(uint32_t) * (size_t)B));
     csim::NoiseArgs a{};
     a.N = n; a.F = F; a.S = S; a.B = B; a.b0 = 0; a.Bc = B;
     a.outP = out_p; a.outM = out_m;
     a.inKind = in_kind; a.inA = in_a; a.inB = in_b;
     a.eps = 1e-15;
-    a.sys = dSys.as<double>();
-    a.omega = dOmega.as<double>();
+    a.sys = fr.dSys.as<double>();
+    a.omega = fr.dOmega.as<double>();
     a.srcA = dA.as<int32_t>();
     a.srcB = dB.as<int32_t>();
     a.psd = dPsd.as<double>();
@@ -1737,42 +1693,15 @@ int csim_noise_solve_batch(int32_t device, int32_t n, int32_t B, const double* G
     a.gain = wantGain ? dGain.as<double>() : nullptr;
     a.contrib = contrib ? dCon.as<double>() : nullptr;
     a.y = y ? dY.as<double>() : nullptr;
-    a.status = dF.as<uint32_t>();
-    HIPCHK(csim::launchNoiseSweep(which, a, nullptr));
+    a.status = fr.dF.as<uint32_t>();
+    HIPCHK(csim::launchNoiseSweep(fr.which, a, nullptr));
     HIPCHK(hipDeviceSynchronize());
-    std::vector<double> h(FB);                               // [F][B] -> [B][F]
-    HIPCHK(hipMemcpy(h.data(), dOn.p, sizeof(double) * FB, hipMemcpyDeviceToHost));
-    for (int f = 0; f < F; ++f)
-        for (int b = 0; b < B; ++b) onoise[(size_t)b * F + f] = h[(size_t)f * B + b];
-    if (wantGain) {
-        h.resize(2 * FB);
-        HIPCHK(hipMemcpy(h.data(), dGain.p, sizeof(double) * 2 * FB, hipMemcpyDeviceToHost));
-        for (int f = 0; f < F; ++f)
-            for (int b = 0; b < B; ++b) {
-                gain[((size_t)b * F + f) * 2] = h[((size_t)f * B + b) * 2];
-                gain[((size_t)b * F + f) * 2 + 1] = h[((size_t)f * B + b) * 2 + 1];
-            }
-    }
-    if (contrib && S > 0) {                                  // [F][S][B] -> [B][F][S]
-        h.resize(FB * (size_t)S);
-        HIPCHK(hipMemcpy(h.data(), dCon.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
-        for (int f = 0; f < F; ++f)
-            for (int s = 0; s < S; ++s)
-                for (int b = 0; b < B; ++b) contrib[((size_t)b * F + f) * S + s] = h[((size_t)f * S + s) * B + b];
-    }
-    if (y) {                                                 // [F][n][B] -> [B][F][n]
-        h.resize(2 * FB * (size_t)n);
-        HIPCHK(hipMemcpy(h.data(), dY.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
-        for (int f = 0; f < F; ++f)
-            for (int p = 0; p < n; ++p)
-                for (int b = 0; b < B; ++b) {
-                    const size_t src = (((size_t)f * n + p) * B + b) * 2;
-                    const size_t dst = (((size_t)b * F + f) * n + p) * 2;
-                    y[dst] = h[src];
-                    y[dst + 1] = h[src + 1];
-                }
-    }
-    if (flags) HIPCHK(hipMemcpy(flags, dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    int rc = toHost(dOn.as<double>(), F, 1, B, 1, onoise);
+    if (!rc && wantGain) rc = toHost(dGain.as<double>(), F, 1, B, 2, gain);
+    if (!rc && contrib) rc = toHost(dCon.as<double>(), F, S, B, 1, contrib);
+    if (!rc && y) rc = toHost(dY.as<double>(), F, n, B, 2, y);
+    if (rc) return rc;
+    if (flags) HIPCHK(hipMemcpy(flags, fr.dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
     return CSIM_OK;
 }
 
@@ -1795,33 +1724,18 @@ int csim_sp_solve_batch(int32_t device, int32_t n, int32_t B, int32_t K, const d
             if (port_eq[i] < 0 || port_eq[i] >= n) { setError("csim_sp_solve_batch: port equation out of range"); return CSIM_ERR_ARG; }
             if (!(z0[i] > 0.0) || !std::isfinite(z0[i])) { setError("csim_sp_solve_batch: Z0 must be finite and > 0"); return CSIM_ERR_ARG; }
         }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
-        setError("csim_sp_solve_batch: no usable HIP device (this library has no CPU path)");
-        return CSIM_ERR_NO_DEVICE;
-    }
-    if (n > 63) { setError("csim_sp_solve_batch covers n <= 63"); return CSIM_ERR_UNSUPPORTED; }
-    int which = kernel;
-    if (which == csim::AC_KERNEL_AUTO) which = n <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
-    if (which == csim::AC_KERNEL_PACKED && n > 32) { setError("csim_sp_solve_batch: the packed kernel covers n <= 32"); return CSIM_ERR_UNSUPPORTED; }
+    AcSolveFront fr;
+    if (const int rc = acSolveFront("csim_sp_solve_batch", device, n, B, G, Cm, nullptr, omega, F, kernel, work, fr)) return rc;
     if (!work) return CSIM_OK;
-    HIPCHK(hipSetDevice(device));
-    const std::vector<double> sys = packAcSystems(n, B, G, Cm, nullptr);
     const size_t xDoubles = (size_t)2 * F * K * n * B, yDoubles = (size_t)2 * F * K * K * B;
     const bool wantX = x != nullptr;
-    DevBuf dSys, dOmega, dJ, dX, dY, dS, dF;
-    HIPCHK(dSys.alloc(sizeof(double) * sys.size()));
-    HIPCHK(dOmega.alloc(sizeof(double) * (size_t)F));
-    HIPCHK(dF.alloc(sizeof(uint32_t) * (size_t)B));
-    HIPCHK(hipMemcpy(dSys.p, sys.data(), sizeof(double) * sys.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dOmega.p, omega, sizeof(double) * (size_t)F, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(dF.p, 0, sizeof(uint32_t) * (size_t)B));
+    DevBuf dJ, dX, dY, dS;
     csim::SpArgs a{};
     a.N = n; a.K = K; a.P = ports ? K : 0; a.F = F; a.B = B; a.b0 = 0; a.Bc = B;
     a.eps = 1e-15;
-    a.sys = dSys.as<double>();
-    a.omega = dOmega.as<double>();
-    a.status = dF.as<uint32_t>();
+    a.sys = fr.dSys.as<double>();
+    a.omega = fr.dOmega.as<double>();
+    a.status = fr.dF.as<uint32_t>();
     if (wantX) {
         HIPCHK(dX.alloc(sizeof(double) * xDoubles));
         HIPCHK(hipMemset(dX.p, 0, sizeof(double) * xDoubles));
@@ -1837,16 +1751,14 @@ int csim_sp_solve_batch(int32_t device, int32_t n, int32_t B, int32_t K, const d
         HIPCHK(hipMemcpy(dJ.p, J, sizeof(double) * (size_t)2 * K * n * B, hipMemcpyHostToDevice));
         a.rhs = dJ.as<double>();
     }
-    HIPCHK(csim::launchSpSweep(which, a, nullptr));
+    HIPCHK(csim::launchSpSweep(fr.which, a, nullptr));
     HIPCHK(hipDeviceSynchronize());
-    if (wantX) {                                             // [F][K][n][B] -> [B][F][K][n]
-        if (const int rc = spToHost(dX.as<double>(), F, K * n, B, x)) return rc;
-    }
-    if (ports) {
-        if (const int rc = spToHost(dY.as<double>(), F, K * K, B, y)) return rc;
-        if (s) { if (const int rc = spToHost(dS.as<double>(), F, K * K, B, s)) return rc; }
-    }
-    if (flags) HIPCHK(hipMemcpy(flags, dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    int rc = CSIM_OK;
+    if (wantX) rc = toHost(dX.as<double>(), F, K * n, B, 2, x);              // [F][K][n][B] -> [B][F][K][n]
+    if (!rc && ports) rc = toHost(dY.as<double>(), F, K * K, B, 2, y);
+    if (!rc && ports && s) rc = toHost(dS.as<double>(), F, K * K, B, 2, s);
+    if (rc) return rc;
+    if (flags) HIPCHK(hipMemcpy(flags, fr.dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
     return CSIM_OK;
 }
 

@@ -128,14 +128,10 @@ __global__ void __launch_bounds__(64) ac_sweep_wave_kernel(int N, const double* 
     extern __shared__ double lds[];
     const int lane = threadIdx.x;
     const int c = blockIdx.x, b = b0 + c;
-    const int LD = (N + 1) | 1;                 // plan.hpp ldFor(): odd, >= N + 1
-    double* Ar = lds;
-    double* Ai = Ar + N * LD;
-    double* Lr = Ai + N * LD;        // multipliers of the current column, then products of the back substitution
-    double* Li = Lr + 64;
-    double* Xr = Li + 64;
-    double* Xi = Xr + 64;
-    const double* Gt = sys + (size_t)c * (2 * N * N + 2 * N);
+    const int LD = acw_ld(N, 1);
+    const AcwLds m = acw_carve(lds, N, 1, LD);
+    double *const Ar = m.Ar, *const Ai = m.Ai, *const Xr = m.Xr, *const Xi = m.Xi;
+    const double* Gt = ac_system_at(sys, c, N);
     const double* Ct = Gt + N * N;
     const double* Jr = Ct + N * N;
     const double* Ji = Jr + N;
@@ -144,15 +140,11 @@ __global__ void __launch_bounds__(64) ac_sweep_wave_kernel(int N, const double* 
 
     for (int f = 0; f < F; ++f) {
         const double w = omega[f];
-        for (int idx = lane; idx < N * N; idx += 64) {
-            const int j = idx / N, i = idx - j * N;
-            Ar[i * LD + j] = Gt[idx];
-            Ai[i * LD + j] = w * Ct[idx];
-        }
+        acw_load<false>(N, LD, Gt, Ct, w, Ar, Ai, lane);
         for (int i = lane; i < N; i += 64) { Ar[i * LD + N] = Jr[i]; Ai[i * LD + N] = Ji[i]; }
         wave_sync();
 
-        if (acw_solve(N, LD, Ar, Ai, Lr, Li, Xr, Xi, eps2, lane)) flags |= CSIM_ST_LU_TINY_PIVOT;
+        if (acw_solve(N, 1, LD, Ar, Ai, m.Lr, m.Li, Xr, Xi, eps2, lane)) flags |= CSIM_ST_LU_TINY_PIVOT;
         for (int p = lane; p < nProbe; p += 64) {
             const int eq = probe ? probe[p] : p;
             const size_t at = ac_out_at(f, p, nProbe, B, b);
@@ -163,7 +155,7 @@ __global__ void __launch_bounds__(64) ac_sweep_wave_kernel(int N, const double* 
     }
     if (lane == 0 && flags) status[b] |= flags;
 }
-// ---- register-resident, 32 lanes per system (N <= NP <= 32): acp_column / acp_back of ac_sweep.hpp
+// ---- register-resident, 32 lanes per system (N <= NP <= 32): acp_column / acp_back of ac_sweep.hpp, one RHS
 
 template <int NP>
 __global__ void __launch_bounds__(64) ac_sweep_packed_kernel(int N, const double* __restrict__ sys, const double* __restrict__ omega,
@@ -172,13 +164,10 @@ __global__ void __launch_bounds__(64) ac_sweep_packed_kernel(int N, const double
                                                              uint32_t* __restrict__ status)
 {
     __shared__ double xs[2][2][ACP_LANES];                  // [instance][re, im][position]
-    const int lane = threadIdx.x;
-    const int h = lane / ACP_LANES, r = lane % ACP_LANES;
-    const int c = blockIdx.x * 2 + h;
-    const bool on = c < Bc;                                 // the second half of the last block may be empty
-    const int cc = on ? c : 0;
-    const int b = b0 + cc;
-    const double* Gt = sys + (size_t)cc * (2 * N * N + 2 * N);
+    const AcpInstance t = acp_instance(b0, Bc);
+    const int h = t.h, r = t.r, b = t.b;
+    const bool on = t.on;
+    const double* Gt = ac_system_at(sys, t.cc, N);
     const double* Ct = Gt + N * N;
     const double* Jr = Ct + N * N;
     const double* Ji = Jr + N;
@@ -200,8 +189,8 @@ __global__ void __launch_bounds__(64) ac_sweep_packed_kernel(int N, const double
         ai[NP] = r < N ? Ji[r] : 0.0;
         int pos = r;
         bool failed = false;
-        acp_column<NP, 0>(ar, ai, N, pos, failed, eps2, h);
-        acp_back<NP, NP - 1>(ar, ai, N, pos, Xr, Xi);
+        acp_column<NP, 1, 0>(ar, ai, N, pos, failed, eps2, h);
+        acp_back<NP, 1, NP - 1>(ar, ai, N, pos, Xr, Xi);
         if (failed) flags |= CSIM_ST_LU_TINY_PIVOT;
         for (int p = r; p < nProbe; p += ACP_LANES) {
             const int eq = probe ? probe[p] : p;
@@ -232,21 +221,18 @@ hipError_t launchAcAssemble(const GenPlan& pl, const double* dAcRe, const double
     return hipGetLastError();
 }
 
-#define CSIM_ACP(NPV) hipLaunchKernelGGL(ac_sweep_packed_kernel<NPV>, dim3(grid), dim3(64), 0, stream, N, dSys, dOmega, F, dProbe, nProbe, B, b0, Bc, eps, dOut, dStatus)
-
 hipError_t launchAcSweep(int which, int N, const double* dSys, const double* dOmega, int F, const int32_t* dProbe,
                          int nProbe, int B, int b0, int Bc, double eps, double* dOut, uint32_t* dStatus, hipStream_t stream)
 {
     if (Bc <= 0 || F <= 0) return hipSuccess;
-    if (N < 1 || N > 63 || (which == AC_KERNEL_PACKED && N > 32)) return hipErrorInvalidValue;
+    if (!ac_sweep_covers(which, N)) return hipErrorInvalidValue;
     if (which == AC_KERNEL_PACKED) {
-        const int grid = (Bc + 1) / 2;
-        if (N <= 8) CSIM_ACP(8);
-        else if (N <= 16) CSIM_ACP(16);
-        else if (N <= 24) CSIM_ACP(24);
-        else CSIM_ACP(32);
+        acp_dispatch(N, [&](auto np) {
+            hipLaunchKernelGGL(ac_sweep_packed_kernel<decltype(np)::value>, dim3((Bc + 1) / 2), dim3(64), 0, stream, N, dSys,
+                               dOmega, F, dProbe, nProbe, B, b0, Bc, eps, dOut, dStatus);
+        });
     } else {
-        const size_t lds = sizeof(double) * (2 * (size_t)N * ldFor(N) + 4 * 64);
+        const size_t lds = acw_lds_bytes(N, 1);
         if (lds > 64 * 1024)
             (void)hipFuncSetAttribute((const void*)ac_sweep_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(ac_sweep_wave_kernel, dim3(Bc), dim3(64), lds, stream, N, dSys, dOmega, F, dProbe, nProbe, B, b0,
@@ -254,6 +240,5 @@ hipError_t launchAcSweep(int which, int N, const double* dSys, const double* dOm
     }
     return hipGetLastError();
 }
-#undef CSIM_ACP
 
 } // namespace csim

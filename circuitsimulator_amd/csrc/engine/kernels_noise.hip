@@ -83,32 +83,24 @@ __global__ void __launch_bounds__(64) ac_noise_wave_kernel(NoiseArgs a)
     const int lane = threadIdx.x;
     const int N = a.N, S = a.S;
     const int c = blockIdx.x, b = a.b0 + c;
-    const int LD = (N + 1) | 1;                 // plan.hpp ldFor(): odd, >= N + 1
-    double* Ar = lds;
-    double* Ai = Ar + N * LD;
-    double* Lr = Ai + N * LD;
-    double* Li = Lr + 64;
-    double* Xr = Li + 64;
-    double* Xi = Xr + 64;
-    const double* Gt = a.sys + (size_t)c * (2 * N * N + 2 * N);
+    const int LD = acw_ld(N, 1);
+    const AcwLds m = acw_carve(lds, N, 1, LD);
+    double *const Ar = m.Ar, *const Ai = m.Ai, *const Xr = m.Xr, *const Xi = m.Xi;
+    const double* Gt = ac_system_at(a.sys, c, N);
     const double* Ct = Gt + N * N;
     const double eps2 = a.eps * a.eps;
     unsigned flags = 0u;
 
     for (int f = 0; f < a.F; ++f) {
         const double w = a.omega[f];
-        for (int idx = lane; idx < N * N; idx += 64) {       // word i * N + j of column-major A is A(j,i) = A^T(i,j)
-            const int i = idx / N, j = idx - i * N;
-            Ar[i * LD + j] = Gt[idx];
-            Ai[i * LD + j] = w * Ct[idx];
-        }
+        acw_load<true>(N, LD, Gt, Ct, w, Ar, Ai, lane);
         for (int i = lane; i < N; i += 64) {
             Ar[i * LD + N] = i == a.outP ? 1.0 : (i == a.outM ? -1.0 : 0.0);
             Ai[i * LD + N] = 0.0;
         }
         wave_sync();
 
-        const bool failed = acw_solve(N, LD, Ar, Ai, Lr, Li, Xr, Xi, eps2, lane);
+        const bool failed = acw_solve(N, 1, LD, Ar, Ai, m.Lr, m.Li, Xr, Xi, eps2, lane);
         if (failed) flags |= CSIM_ST_LU_TINY_PIVOT;
         if (a.y)
             for (int p = lane; p < N; p += 64) {
@@ -140,14 +132,11 @@ __global__ void __launch_bounds__(64) ac_noise_packed_kernel(NoiseArgs a)
     constexpr int LDT = NP + 1;                             // odd: lane r reading word r * LDT + j is conflict-free
     __shared__ double tile[2][NP * LDT];                    // [instance] staged G, then C, as rows of A^T
     __shared__ double xs[2][2][ACP_LANES];                  // [instance][re, im][position]
-    const int lane = threadIdx.x;
     const int N = a.N, S = a.S;
-    const int h = lane / ACP_LANES, r = lane % ACP_LANES;
-    const int c = blockIdx.x * 2 + h;
-    const bool on = c < a.Bc;                               // the second half of the last block may be empty
-    const int cc = on ? c : 0;
-    const int b = a.b0 + cc;
-    const double* Gt = a.sys + (size_t)cc * (2 * N * N + 2 * N);
+    const AcpInstance t = acp_instance(a.b0, a.Bc);
+    const int h = t.h, r = t.r, cc = t.cc, b = t.b;
+    const bool on = t.on;
+    const double* Gt = ac_system_at(a.sys, cc, N);
     const double* Ct = Gt + N * N;
     double* T = tile[h];
     double* Xr = xs[h][0];
@@ -182,8 +171,8 @@ __global__ void __launch_bounds__(64) ac_noise_packed_kernel(NoiseArgs a)
         ai[NP] = 0.0;
         int pos = r;
         bool failed = false;
-        acp_column<NP, 0>(ar, ai, N, pos, failed, eps2, h);
-        acp_back<NP, NP - 1>(ar, ai, N, pos, Xr, Xi);
+        acp_column<NP, 1, 0>(ar, ai, N, pos, failed, eps2, h);
+        acp_back<NP, 1, NP - 1>(ar, ai, N, pos, Xr, Xi);
         if (failed) {
             flags |= CSIM_ST_LU_TINY_PIVOT;
             Xr[r] = 0.0;                                    // as the wave kernel leaves it: the zero vector
@@ -225,28 +214,23 @@ hipError_t launchNoisePsd(const GenPlan& pl, const int32_t* dSrcElem, int S, con
     return hipGetLastError();
 }
 
-#define CSIM_NOISEP(NPV) hipLaunchKernelGGL(ac_noise_packed_kernel<NPV>, dim3(grid), dim3(64), 0, stream, a)
-
 hipError_t launchNoiseSweep(int which, const NoiseArgs& a, hipStream_t stream)
 {
     if (a.Bc <= 0 || a.F <= 0) return hipSuccess;
     const int N = a.N;
-    if (N < 1 || N > 63 || (which == AC_KERNEL_PACKED && N > 32)) return hipErrorInvalidValue;
+    if (!ac_sweep_covers(which, N)) return hipErrorInvalidValue;
     if (a.outP < 0 || a.outP >= N || a.outM < -1 || a.outM >= N || a.S < 0) return hipErrorInvalidValue;
     if (which == AC_KERNEL_PACKED) {
-        const int grid = (a.Bc + 1) / 2;
-        if (N <= 8) CSIM_NOISEP(8);
-        else if (N <= 16) CSIM_NOISEP(16);
-        else if (N <= 24) CSIM_NOISEP(24);
-        else CSIM_NOISEP(32);
+        acp_dispatch(N, [&](auto np) {
+            hipLaunchKernelGGL(ac_noise_packed_kernel<decltype(np)::value>, dim3((a.Bc + 1) / 2), dim3(64), 0, stream, a);
+        });
     } else {
-        const size_t lds = sizeof(double) * (2 * (size_t)N * ldFor(N) + 4 * 64);
+        const size_t lds = acw_lds_bytes(N, 1);
         if (lds > 64 * 1024)
             (void)hipFuncSetAttribute((const void*)ac_noise_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(ac_noise_wave_kernel, dim3(a.Bc), dim3(64), lds, stream, a);
     }
     return hipGetLastError();
 }
-#undef CSIM_NOISEP
 
 } // namespace csim

@@ -4,9 +4,9 @@
 // The system of an instance is the one ac_assemble_kernel leaves (G, C column-major; its J is not read).  Two kernels:
 //
 //   sp_sweep_wave_kernel            one wavefront per instance, N <= 63: the matrix and its K right-hand sides in LDS
-//                                   (odd leading dimension >= N + K), acw_solve_multi() of ac_sweep.hpp.
+//                                   (odd leading dimension >= N + K), acw_solve() of ac_sweep.hpp.
 //   sp_sweep_packed_kernel<NP, KP>  N <= 32: 32 lanes per instance, lane r owns row r in registers ar/ai[NP + KP],
-//                                   acp_column_multi / acp_back_multi.  K is rounded up to KP in {2, 4}; a padded
+//                                   acp_column / acp_back.  K is rounded up to KP in {2, 4}; a padded
 //                                   zero column changes no other column and is never stored.  G, then C, are staged
 //                                   through an LDS tile with an odd leading dimension (the tile of the packed noise
 //                                   kernel, here filled column by column): NP loads in flight instead of 2 NP.
@@ -88,14 +88,10 @@ __global__ void __launch_bounds__(64) sp_sweep_wave_kernel(SpArgs a)
     const int lane = threadIdx.x;
     const int N = a.N, K = a.K, P = a.P;
     const int c0 = blockIdx.x, b = a.b0 + c0;
-    const int LD = (N + K) | 1;                 // odd, >= N + K
-    double* Ar = lds;
-    double* Ai = Ar + N * LD;
-    double* Lr = Ai + N * LD;
-    double* Li = Lr + 64;
-    double* Xr = Li + 64;                       // solution c at c * 64
-    double* Xi = Xr + K * 64;
-    const double* Gt = a.sys + (size_t)c0 * (2 * N * N + 2 * N);
+    const int LD = acw_ld(N, K);
+    const AcwLds m = acw_carve(lds, N, K, LD);
+    double *const Ar = m.Ar, *const Ai = m.Ai, *const Xr = m.Xr, *const Xi = m.Xi;      // solution c at c * 64
+    const double* Gt = ac_system_at(a.sys, c0, N);
     const double* Ct = Gt + N * N;
     const double* rhs = a.rhs ? a.rhs + (size_t)c0 * (size_t)(2 * K * N) : nullptr;
     const double eps2 = a.eps * a.eps;
@@ -105,11 +101,7 @@ __global__ void __launch_bounds__(64) sp_sweep_wave_kernel(SpArgs a)
 
     for (int f = 0; f < a.F; ++f) {
         const double w = a.omega[f];
-        for (int idx = lane; idx < N * N; idx += 64) {
-            const int j = idx / N, i = idx - j * N;
-            Ar[i * LD + j] = Gt[idx];
-            Ai[i * LD + j] = w * Ct[idx];
-        }
+        acw_load<false>(N, LD, Gt, Ct, w, Ar, Ai, lane);
         for (int e = lane; e < N * K; e += 64) {
             const int c = e / N, i = e - c * N;
             Ar[i * LD + N + c] = P > 0 ? (i == epi.eq[c] ? 1.0 : 0.0) : rhs[2 * e];
@@ -117,7 +109,7 @@ __global__ void __launch_bounds__(64) sp_sweep_wave_kernel(SpArgs a)
         }
         wave_sync();
 
-        const bool failed = acw_solve_multi(N, K, LD, Ar, Ai, Lr, Li, Xr, Xi, eps2, lane);
+        const bool failed = acw_solve(N, K, LD, Ar, Ai, m.Lr, m.Li, Xr, Xi, eps2, lane);
         if (failed) flags |= CSIM_ST_LU_TINY_PIVOT;
         if (a.x)
             for (int e = lane; e < N * K; e += 64) {
@@ -144,14 +136,11 @@ __global__ void __launch_bounds__(64) sp_sweep_packed_kernel(SpArgs a)
     __shared__ double tile[2][NP * LDT];                    // [instance] staged G, then C, as rows of A
     __shared__ double xs[2][2][KP * ACP_LANES];             // [instance][re, im][solution c at c * 32]
     __shared__ SpEpi epis[2];
-    const int lane = threadIdx.x;
     const int N = a.N, K = a.K, P = a.P;
-    const int h = lane / ACP_LANES, r = lane % ACP_LANES;
-    const int c0 = blockIdx.x * 2 + h;
-    const bool on = c0 < a.Bc;                              // the second half of the last block may be empty
-    const int cc = on ? c0 : 0;
-    const int b = a.b0 + cc;
-    const double* Gt = a.sys + (size_t)cc * (2 * N * N + 2 * N);
+    const AcpInstance t = acp_instance(a.b0, a.Bc);
+    const int h = t.h, r = t.r, cc = t.cc, b = t.b;
+    const bool on = t.on;
+    const double* Gt = ac_system_at(a.sys, cc, N);
     const double* Ct = Gt + N * N;
     const double* rhs = a.rhs ? a.rhs + (size_t)cc * (size_t)(2 * K * N) : nullptr;
     double* T = tile[h];
@@ -199,8 +188,8 @@ __global__ void __launch_bounds__(64) sp_sweep_packed_kernel(SpArgs a)
         }
         int pos = r;
         bool failed = false;
-        acp_column_multi<NP, KP, 0>(ar, ai, N, pos, failed, eps2, h);
-        acp_back_multi<NP, KP, NP - 1>(ar, ai, N, pos, Xr, Xi);
+        acp_column<NP, KP, 0>(ar, ai, N, pos, failed, eps2, h);
+        acp_back<NP, KP, NP - 1>(ar, ai, N, pos, Xr, Xi);
         if (failed) {
             flags |= CSIM_ST_LU_TINY_PIVOT;
 #pragma unroll
@@ -228,35 +217,29 @@ __global__ void __launch_bounds__(64) sp_sweep_packed_kernel(SpArgs a)
 
 } // namespace
 
-#define CSIM_SPP(NPV)                                                                                         \
-    do {                                                                                                      \
-        if (a.K <= 2) hipLaunchKernelGGL((sp_sweep_packed_kernel<NPV, 2>), dim3(grid), dim3(64), 0, stream, a); \
-        else hipLaunchKernelGGL((sp_sweep_packed_kernel<NPV, 4>), dim3(grid), dim3(64), 0, stream, a);        \
-    } while (0)
-
 hipError_t launchSpSweep(int which, const SpArgs& a, hipStream_t stream)
 {
     if (a.Bc <= 0 || a.F <= 0) return hipSuccess;
     const int N = a.N;
-    if (N < 1 || N > 63 || (which == AC_KERNEL_PACKED && N > 32)) return hipErrorInvalidValue;
+    if (!ac_sweep_covers(which, N)) return hipErrorInvalidValue;
     if (a.K < 1 || a.K > SP_MAX_PORTS || (a.P != 0 && a.P != a.K)) return hipErrorInvalidValue;
     for (int p = 0; p < a.P; ++p)
         if (a.portEq[p] < 0 || a.portEq[p] >= N) return hipErrorInvalidValue;       // they index LDS
     if (a.P == 0 ? (!a.rhs || !a.x) : !a.y) return hipErrorInvalidValue;
     if (which == AC_KERNEL_PACKED) {
-        const int grid = (a.Bc + 1) / 2;
-        if (N <= 8) CSIM_SPP(8);
-        else if (N <= 16) CSIM_SPP(16);
-        else if (N <= 24) CSIM_SPP(24);
-        else CSIM_SPP(32);
+        acp_dispatch(N, [&](auto np) {
+            constexpr int NP = decltype(np)::value;
+            const dim3 grid((a.Bc + 1) / 2);
+            if (a.K <= 2) hipLaunchKernelGGL((sp_sweep_packed_kernel<NP, 2>), grid, dim3(64), 0, stream, a);
+            else hipLaunchKernelGGL((sp_sweep_packed_kernel<NP, 4>), grid, dim3(64), 0, stream, a);
+        });
     } else {
-        const size_t lds = sizeof(double) * (2 * (size_t)N * (size_t)((N + a.K) | 1) + 2 * 64 + 2 * (size_t)a.K * 64);
+        const size_t lds = acw_lds_bytes(N, a.K);
         if (lds + sizeof(SpEpi) > 64 * 1024)
             (void)hipFuncSetAttribute((const void*)sp_sweep_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(sp_sweep_wave_kernel, dim3(a.Bc), dim3(64), lds, stream, a);
     }
     return hipGetLastError();
 }
-#undef CSIM_SPP
 
 } // namespace csim
