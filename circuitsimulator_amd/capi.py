@@ -69,6 +69,11 @@ PROTOTYPES = {
     "csim_netlist_sp": (C.c_int, [_vp, _pi32, _pi32, _pi32, _pdbl, _pdbl]),
     "csim_sp_batch_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "csim_sp_batch": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "csim_netlist_sp_noise": (C.c_int, [_vp, _pi32]),
+    "csim_spnoise_batch_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "csim_spnoise_batch": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "csim_spnoise_solve_batch": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "csim_sp_solve_batch": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "csim_ac_num_freqs": (_i64, [_i32, _i32, _dbl, _dbl]),
     "csim_ac_freqs": (C.c_int, [_i32, _i32, _dbl, _dbl, _vp]),

@@ -129,6 +129,40 @@ BatchSpResult BatchEngine::sp(const std::vector<double>& params, int B, const st
     return r;
 }
 
+BatchSpNoiseResult BatchEngine::spNoise(const std::vector<double>& params, int B, const std::vector<double>& freqs, double tempK)
+{
+    BatchSpNoiseResult r;
+    r.freqs = freqs;
+    if (r.freqs.empty()) {                                  // the .SP card
+        int32_t enabled = 0, sweep = 0, nPoints = 0;
+        double fstart = 0.0, fstop = 0.0;
+        if (csim_netlist_sp(nl_, &enabled, &sweep, &nPoints, &fstart, &fstop) != CSIM_OK) fail("csim_netlist_sp");
+        const int64_t n = enabled ? csim_ac_num_freqs(sweep, nPoints, fstart, fstop) : 0;
+        if (n <= 0) { csim::setError("BatchEngine::spNoise: no frequencies given and the netlist has no .SP card"); fail("BatchEngine::spNoise"); }
+        r.freqs.resize(static_cast<std::size_t>(n));
+        if (csim_ac_freqs(sweep, nPoints, fstart, fstop, r.freqs.data()) != CSIM_OK) fail("csim_ac_freqs");
+    }
+    r.nPorts = std::max(0, csim_netlist_num_ports(nl_));
+    const std::size_t FB = static_cast<std::size_t>(B) * r.freqs.size();
+    const std::size_t n = FB * static_cast<std::size_t>(r.nPorts * r.nPorts);
+    const bool two = r.nPorts == 2;
+    r.y.assign(n, std::complex<double>());
+    r.cy.assign(n, std::complex<double>());
+    if (two) {
+        r.nf.assign(FB, 0.0);
+        r.fmin.assign(FB, 0.0);
+        r.rn.assign(FB, 0.0);
+        r.yopt.assign(FB, std::complex<double>());
+    }
+    r.status.assign(static_cast<std::size_t>(B), 0);
+    if (csim_spnoise_batch(eng_, params.empty() ? nullptr : params.data(), B, r.freqs.data(), static_cast<int>(r.freqs.size()),
+                           tempK, reinterpret_cast<double*>(r.y.data()), reinterpret_cast<double*>(r.cy.data()),
+                           two ? r.nf.data() : nullptr, two ? r.fmin.data() : nullptr, two ? r.rn.data() : nullptr,
+                           two ? reinterpret_cast<double*>(r.yopt.data()) : nullptr, r.status.data()) != CSIM_OK)
+        fail("csim_spnoise_batch");
+    return r;
+}
+
 BatchTranResult BatchEngine::tran(const std::vector<double>& params, int B, double tstep, double tstop,
                                   double tstart, const std::vector<int32_t>& probeEq, int outStride)
 {

@@ -57,6 +57,15 @@ struct BatchSpResult {
     std::vector<uint32_t> status;                 // DC and LU bits (CSIM_ST_LU_TINY_PIVOT: a singular frequency)
 };
 
+struct BatchSpNoiseResult {
+    std::vector<double> freqs;                    // [F] Hz
+    int nPorts = 0;                               // P (csim_netlist_port order)
+    std::vector<std::complex<double>> y, cy;      // [B][F][P][P]: admittance, port noise-current correlation (A^2/Hz)
+    std::vector<double> nf, fmin, rn;             // [B][F], linear; two ports only (empty otherwise)
+    std::vector<std::complex<double>> yopt;       // [B][F]; two ports only
+    std::vector<uint32_t> status;                 // DC and LU bits (CSIM_ST_LU_TINY_PIVOT: a singular frequency)
+};
+
 // One engine per (circuit, GPU).  Throws std::runtime_error when no HIP
 // device is usable: there is no CPU path.
 class BatchEngine {
@@ -93,6 +102,12 @@ public:
     // with one right-hand side per port and frequency; Y always, S when asked for.  freqs empty: the .SP card (an
     // error when the netlist has none).
     BatchSpResult sp(const std::vector<double>& params, int B, const std::vector<double>& freqs, bool wantS = true);
+
+    // Two-port noise of the netlist's ports (csim_spnoise_batch, include/csim.h): DC operating point, then one
+    // factorisation of the transposed system with one adjoint right-hand side per port and frequency; Y and Cy always,
+    // NF / Fmin / Rn / Yopt for two ports.  freqs empty: the .SP card (an error when the netlist has none).
+    BatchSpNoiseResult spNoise(const std::vector<double>& params, int B, const std::vector<double>& freqs,
+                               double tempK = 300.15);
 
     // the transient of instance `instance` of params ([B][P], empty = nominal) as the reference's CSV
     // (src/tanalisis.cpp:189-231); probeEq empty: the netlist's .PLOTNV/.PRINT probes when `sim` names any, else

@@ -499,7 +499,7 @@ void NetlistParser::acCard(const Statement& st)
     sim.ac = cfg;
 }
 
-// .SP {LIN|DEC|OCT} npoints fstart fstop
+// .SP {LIN|DEC|OCT} npoints fstart fstop [0|1]   (a sixth token 1: noise too; anything else is ignored)
 void NetlistParser::spCard(const Statement& st)
 {
     const auto& t = st.tokens;
@@ -519,6 +519,7 @@ void NetlistParser::spCard(const Statement& st)
                   << " in '" << st.raw << "'\n";
         return;
     }
+    cfg.doNoise = t.size() > 5 && t[5] == "1";
     cfg.enabled = true;
     sim.sp = cfg;
 }

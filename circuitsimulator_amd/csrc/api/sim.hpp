@@ -156,9 +156,10 @@ struct NoiseConfig {
     double fstart = 0.0, fstop = 0.0;
 };
 
-// .SP {DEC|OCT|LIN} n fstart fstop
+// .SP {DEC|OCT|LIN} n fstart fstop [0|1]
 struct SpConfig {
     bool enabled = false;
+    bool doNoise = false;           // the trailing 1 (ngspice's donoise): two-port noise wanted with the sweep
     AcSweepType sweepType = AcSweepType::DEC;
     int nPoints = 0;
     double fstart = 0.0, fstop = 0.0;

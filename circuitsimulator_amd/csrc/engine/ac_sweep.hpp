@@ -1,7 +1,8 @@
-// ac_sweep.hpp -- what the sweep kernels of the AC, noise and S-parameter analyses (kernels_ac.hip, kernels_noise.hip,
-// kernels_sp.hip) share: the factorisation and back substitution with K right-hand sides -- ac_lu.hpp's primitives
-// applied in the order of ac_lu_solve_multi(), by one wavefront on a system in LDS, or by 32 lanes on a system in
-// registers -- and the scaffolding around it (LDS carve-up, the G + jwC load, instance indexing, launch dispatch).  AC and noise are K = 1.  Included by those three files only.
+// ac_sweep.hpp -- what the sweep kernels of the AC, noise, S-parameter and two-port noise analyses (kernels_ac.hip,
+// kernels_noise.hip, kernels_sp.hip, kernels_spnoise.hip) share: the factorisation and back substitution with K
+// right-hand sides -- ac_lu.hpp's primitives applied in the order of ac_lu_solve_multi(), by one wavefront on a system
+// in LDS, or by 32 lanes on a system in registers -- and the scaffolding around it (LDS carve-up, the G + jwC load,
+// instance indexing, launch dispatch).  AC and noise are K = 1.  Included by those four files only.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ac_noise.hpp"
+#include "ac_port_noise.hpp"
 #include "ac_port.hpp"
 #include "codegen.hpp"
 #include "csim.h"
@@ -1282,6 +1283,142 @@ int csim_sp_batch(csim_engine* eng, const double* params, int32_t B, const doubl
     return CSIM_OK;
 }
 
+// ---- two-port noise analysis ------------------------------------------------
+
+// the engine's ports, the temperature and the wish for noise parameters -> the kernels' numbers (include/csim.h
+// "Two-port noise analysis"); port and size errors are those of the S-parameter analysis
+static int spNoiseSetup(const csim_engine* eng, double temp_k, bool wantParams, csim::SpNoiseArgs& a, double& kT4)
+{
+    csim::SpArgs sp{};
+    if (const int rc = spSetup(eng, sp)) return rc;
+    if (wantParams && sp.P != 2) { setError("two-port noise analysis: NF, Fmin, Rn and Yopt exist for two ports only"); return CSIM_ERR_CONFIG; }
+    if (!(temp_k > 0.0) || !std::isfinite(temp_k)) { setError("two-port noise analysis: the temperature must be positive and finite (kelvin)"); return CSIM_ERR_CONFIG; }
+    kT4 = 4.0 * 1.380649e-23 * temp_k;
+    a.N = sp.N;
+    a.P = sp.P;
+    for (int i = 0; i < sp.P; ++i) a.portEq[i] = sp.portEq[i];
+    a.eps = sp.eps;
+    a.kT40 = 4.0 * 1.380649e-23 * 290.0;
+    a.gs = 1.0 / eng->spZ0[0];
+    a.S = eng->nNoiseSrc;
+    a.srcA = eng->dNoiseA;
+    a.srcB = eng->dNoiseB;
+    return CSIM_OK;
+}
+
+int csim_spnoise_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const double* d_xop, const double* freqs,
+                           int32_t F, double temp_k, double* d_y, double* d_cy, double* d_nf, double* d_fmin, double* d_rn,
+                           double* d_yopt, uint32_t* d_status, void* stream)
+{
+    if (!eng || B < 0 || F < 0) { setError("csim_spnoise_batch_dev: bad argument"); return CSIM_ERR_ARG; }
+    csim::SpNoiseArgs a{};
+    double kT4 = 0.0;
+    if (const int rc = spNoiseSetup(eng, temp_k, d_nf || d_fmin || d_rn || d_yopt, a, kT4)) return rc;
+    if (B > 0 && F > 0 && (!d_params || !d_xop || !freqs || !d_cy || !d_status)) {
+        setError("csim_spnoise_batch_dev: bad argument");
+        return CSIM_ERR_ARG;
+    }
+    const int N = a.N, S = a.S;
+    int which = eng->cfg.acKernel;
+    if (which == csim::AC_KERNEL_AUTO) which = N <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
+    if (which == csim::AC_KERNEL_PACKED && N > 32) { setError("ac_kernel=packed covers N <= 32"); return CSIM_ERR_UNSUPPORTED; }
+    if (B == 0 || F == 0) return CSIM_OK;
+    HIPCHK(hipSetDevice(eng->device));
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+
+    const double* dOmega = nullptr;
+    if (const int rc = acOmega(eng, freqs, F, &dOmega)) return rc;
+    const int chunk = acChunk(eng, B);
+    if (const int rc = acSysScratch(eng, chunk)) return rc;
+    if (eng->noisePsdCap < (size_t)S * (size_t)chunk) {
+        if (eng->dNoisePsd) HIPCHK(hipFree(eng->dNoisePsd));
+        eng->dNoisePsd = nullptr;
+        eng->noisePsdCap = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&eng->dNoisePsd), sizeof(double) * (size_t)S * (size_t)chunk));
+        eng->noisePsdCap = (size_t)S * (size_t)chunk;
+    }
+    a.F = F;
+    a.B = B;
+    a.sys = eng->dAcSys;
+    a.omega = dOmega;
+    a.psd = eng->dNoisePsd;
+    a.psdStride = (size_t)chunk;
+    a.psdOff = 0;
+    a.y = d_y;
+    a.cy = d_cy;
+    a.nf = d_nf;
+    a.fmin = d_fmin;
+    a.rn = d_rn;
+    a.yopt = d_yopt;
+    a.x = nullptr;
+    a.status = d_status;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        a.b0 = b0;
+        a.Bc = std::min(chunk, B - b0);
+        HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, b0, a.Bc, d_xop, eng->dAcSys, hs));
+        HIPCHK(csim::launchNoisePsd(eng->gpTran, eng->dNoiseElem, S, d_params, B, b0, a.Bc, d_xop, kT4, eng->dNoisePsd,
+                                    a.psdStride, a.psdOff, hs));
+        HIPCHK(csim::launchSpNoiseSweep(which, a, hs));
+    }
+    HIPCHK(hipEventRecord(eng->acOmegaSlots[(size_t)eng->acOmegaCur].done, hs));
+    return CSIM_OK;
+}
+
+int csim_spnoise_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F, double temp_k,
+                       double* y, double* cy, double* nf, double* fmin, double* rn, double* yopt, uint32_t* status)
+{
+    if (!eng || B < 0) { setError("csim_spnoise_batch: bad argument"); return CSIM_ERR_ARG; }
+    const bool wantParams = nf || fmin || rn || yopt;
+    {
+        csim::SpNoiseArgs probe{};
+        double kT4 = 0.0;
+        if (const int rc = spNoiseSetup(eng, temp_k, wantParams, probe, kT4)) return rc;
+    }
+    std::vector<double> card;
+    if (!freqs) {
+        if (!eng->spEnabled) { setError("csim_spnoise_batch: no frequencies given and the netlist has no .SP card"); return CSIM_ERR_CONFIG; }
+        const int64_t n = csim_ac_num_freqs(eng->spSweep, eng->spPoints, eng->spFstart, eng->spFstop);
+        if (n < 0) return static_cast<int>(n);
+        card.resize((size_t)n);
+        if (const int rc = csim_ac_freqs(eng->spSweep, eng->spPoints, eng->spFstart, eng->spFstop, card.data())) return rc;
+        freqs = card.data();
+        F = static_cast<int32_t>(n);
+    }
+    if (F < 0 || (B > 0 && F > 0 && !cy)) { setError("csim_spnoise_batch: bad argument"); return CSIM_ERR_ARG; }
+    if (B == 0) return CSIM_OK;
+    HIPCHK(hipSetDevice(eng->device));
+    const int N = eng->plan.N, PP = (int)(eng->spPortEq.size() * eng->spPortEq.size());
+    const size_t FB = (size_t)F * (size_t)B, ppDoubles = 2 * FB * (size_t)PP;
+    DevBuf dParams, dX, dIt, dSt, dY, dCy, dNf, dFmin, dRn, dYopt;
+    int rc = stageParams(eng, params, B, dParams);
+    if (rc) return rc;
+    HIPCHK(dX.alloc(sizeof(double) * (size_t)N * B));
+    HIPCHK(dIt.alloc(sizeof(int32_t) * (size_t)B));
+    HIPCHK(dSt.alloc(sizeof(uint32_t) * (size_t)B));
+    HIPCHK(dCy.alloc(sizeof(double) * ppDoubles));
+    if (y) HIPCHK(dY.alloc(sizeof(double) * ppDoubles));
+    if (nf) HIPCHK(dNf.alloc(sizeof(double) * FB));
+    if (fmin) HIPCHK(dFmin.alloc(sizeof(double) * FB));
+    if (rn) HIPCHK(dRn.alloc(sizeof(double) * FB));
+    if (yopt) HIPCHK(dYopt.alloc(sizeof(double) * 2 * FB));
+    rc = csim_dc_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), dIt.as<int32_t>(), dSt.as<uint32_t>(), nullptr);
+    if (rc) return rc;
+    rc = csim_spnoise_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), freqs, F, temp_k, y ? dY.as<double>() : nullptr,
+                                dCy.as<double>(), nf ? dNf.as<double>() : nullptr, fmin ? dFmin.as<double>() : nullptr,
+                                rn ? dRn.as<double>() : nullptr, yopt ? dYopt.as<double>() : nullptr, dSt.as<uint32_t>(),
+                                nullptr);
+    if (rc) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    if (status) HIPCHK(hipMemcpy(status, dSt.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    if ((rc = toHost(dCy.as<double>(), F, PP, B, 2, cy))) return rc;
+    if (y && (rc = toHost(dY.as<double>(), F, PP, B, 2, y))) return rc;
+    if (nf && (rc = toHost(dNf.as<double>(), F, 1, B, 1, nf))) return rc;
+    if (fmin && (rc = toHost(dFmin.as<double>(), F, 1, B, 1, fmin))) return rc;
+    if (rn && (rc = toHost(dRn.as<double>(), F, 1, B, 1, rn))) return rc;
+    if (yopt && (rc = toHost(dYopt.as<double>(), F, 1, B, 2, yopt))) return rc;
+    return CSIM_OK;
+}
+
 int csim_tran_batch(csim_engine* eng, const double* params, int32_t B, double tstep, double tstop,
                     double tstart, const int32_t* probe_eq, int32_t n_probe, int32_t out_stride,
                     double* wave_out, double* x_final, int64_t* nr_iters, uint32_t* status)
@@ -1757,6 +1894,87 @@ int csim_sp_solve_batch(int32_t device, int32_t n, int32_t B, int32_t K, const d
     if (wantX) rc = toHost(dX.as<double>(), F, K * n, B, 2, x);              // [F][K][n][B] -> [B][F][K][n]
     if (!rc && ports) rc = toHost(dY.as<double>(), F, K * K, B, 2, y);
     if (!rc && ports && s) rc = toHost(dS.as<double>(), F, K * K, B, 2, s);
+    if (rc) return rc;
+    if (flags) HIPCHK(hipMemcpy(flags, fr.dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    return CSIM_OK;
+}
+
+// the engine-free counterpart for the two-port noise kernels: any system, any ports, any generator table
+int csim_spnoise_solve_batch(int32_t device, int32_t n, int32_t B, int32_t P, const double* G, const double* Cm,
+                             const int32_t* port_eq, const double* z0, int32_t S, const int32_t* src_a, const int32_t* src_b,
+                             const double* psd, const double* omega, int32_t F, int32_t kernel, double* y, double* cy,
+                             double* nf, double* fmin, double* rn, double* yopt, double* x, uint32_t* flags)
+{
+    const bool work = n > 0 && B > 0 && F > 0;
+    if (n < 0 || B < 0 || F < 0 || S < 0 || kernel < csim::AC_KERNEL_AUTO || kernel > csim::AC_KERNEL_PACKED || !port_eq || !z0 ||
+        (work && (!G || !Cm || !omega || !cy || (S > 0 && (!src_a || !src_b || !psd))))) {
+        setError("csim_spnoise_solve_batch: bad argument");
+        return CSIM_ERR_ARG;
+    }
+    if (P < 1 || P > csim::SP_MAX_PORTS) { setError("csim_spnoise_solve_batch: 1 to 4 ports"); return CSIM_ERR_ARG; }
+    for (int i = 0; i < P; ++i)
+        if (!(z0[i] > 0.0) || !std::isfinite(z0[i])) { setError("csim_spnoise_solve_batch: Z0 must be finite and > 0"); return CSIM_ERR_ARG; }
+    if (n > 0) {
+        bool ok = true;
+        for (int i = 0; i < P; ++i) ok = ok && port_eq[i] >= 0 && port_eq[i] < n;
+        for (int s = 0; s < S && ok && src_a && src_b; ++s)
+            ok = src_a[s] >= -1 && src_a[s] < n && src_b[s] >= -1 && src_b[s] < n;
+        if (!ok) { setError("csim_spnoise_solve_batch: equation index out of range"); return CSIM_ERR_ARG; }
+    }
+    if (P != 2 && (nf || fmin || rn || yopt)) { setError("csim_spnoise_solve_batch: NF, Fmin, Rn and Yopt exist for two ports only"); return CSIM_ERR_CONFIG; }
+    AcSolveFront fr;
+    if (const int rc = acSolveFront("csim_spnoise_solve_batch", device, n, B, G, Cm, nullptr, omega, F, kernel, work, fr)) return rc;
+    if (!work) return CSIM_OK;
+    std::vector<double> psdT((size_t)S * B);                 // [B][S] -> [S][B]
+    for (int b = 0; b < B; ++b)
+        for (int s = 0; s < S; ++s) psdT[(size_t)s * B + b] = psd[(size_t)b * S + s];
+    const size_t FB = (size_t)F * (size_t)B, ppDoubles = 2 * FB * (size_t)(P * P);
+    DevBuf dA, dB, dPsd, dY, dCy, dNf, dFmin, dRn, dYopt, dX;
+    HIPCHK(dA.alloc(sizeof(int32_t) * (size_t)S));
+    HIPCHK(dB.alloc(sizeof(int32_t) * (size_t)S));
+    HIPCHK(dPsd.alloc(sizeof(double) * psdT.size()));
+    HIPCHK(dCy.alloc(sizeof(double) * ppDoubles));
+    if (y) HIPCHK(dY.alloc(sizeof(double) * ppDoubles));
+    if (nf) HIPCHK(dNf.alloc(sizeof(double) * FB));
+    if (fmin) HIPCHK(dFmin.alloc(sizeof(double) * FB));
+    if (rn) HIPCHK(dRn.alloc(sizeof(double) * FB));
+    if (yopt) HIPCHK(dYopt.alloc(sizeof(double) * 2 * FB));
+    if (x) HIPCHK(dX.alloc(sizeof(double) * 2 * FB * (size_t)P * (size_t)n));
+    if (S > 0) {
+        HIPCHK(hipMemcpy(dA.p, src_a, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dB.p, src_b, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dPsd.p, psdT.data(), sizeof(double) * psdT.size(), hipMemcpyHostToDevice));
+    }
+    csim::SpNoiseArgs a{};
+    a.N = n; a.P = P; a.F = F; a.S = S; a.B = B; a.b0 = 0; a.Bc = B;
+    for (int i = 0; i < P; ++i) a.portEq[i] = port_eq[i];
+    a.eps = 1e-15;
+    a.kT40 = 4.0 * 1.380649e-23 * 290.0;
+    a.gs = 1.0 / z0[0];
+    a.sys = fr.dSys.as<double>();
+    a.omega = fr.dOmega.as<double>();
+    a.srcA = dA.as<int32_t>();
+    a.srcB = dB.as<int32_t>();
+    a.psd = dPsd.as<double>();
+    a.psdStride = (size_t)B;
+    a.psdOff = 0;
+    a.y = y ? dY.as<double>() : nullptr;
+    a.cy = dCy.as<double>();
+    a.nf = nf ? dNf.as<double>() : nullptr;
+    a.fmin = fmin ? dFmin.as<double>() : nullptr;
+    a.rn = rn ? dRn.as<double>() : nullptr;
+    a.yopt = yopt ? dYopt.as<double>() : nullptr;
+    a.x = x ? dX.as<double>() : nullptr;
+    a.status = fr.dF.as<uint32_t>();
+    HIPCHK(csim::launchSpNoiseSweep(fr.which, a, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    int rc = toHost(dCy.as<double>(), F, P * P, B, 2, cy);
+    if (!rc && y) rc = toHost(dY.as<double>(), F, P * P, B, 2, y);
+    if (!rc && nf) rc = toHost(dNf.as<double>(), F, 1, B, 1, nf);
+    if (!rc && fmin) rc = toHost(dFmin.as<double>(), F, 1, B, 1, fmin);
+    if (!rc && rn) rc = toHost(dRn.as<double>(), F, 1, B, 1, rn);
+    if (!rc && yopt) rc = toHost(dYopt.as<double>(), F, 1, B, 2, yopt);
+    if (!rc && x) rc = toHost(dX.as<double>(), F, P * n, B, 2, x);           // [F][P][n][B] -> [B][F][P][n]
     if (rc) return rc;
     if (flags) HIPCHK(hipMemcpy(flags, fr.dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
     return CSIM_OK;

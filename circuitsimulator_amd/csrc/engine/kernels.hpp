@@ -128,6 +128,28 @@ struct SpArgs {
 };
 hipError_t launchSpSweep(int which, const SpArgs& a, hipStream_t stream);
 
+// Two-port noise analysis (kernels_spnoise.hip) on the systems launchAcAssemble leaves: one factorisation of A^T with
+// one adjoint right-hand side per port and (instance, frequency), Y and Cy from its solutions.  Generators and their
+// PSDs as NoiseArgs.  Port equations are checked by the launcher, generator terminals by the callers: they index LDS.
+struct SpNoiseArgs {
+    int N, P, F, S, B, b0, Bc;
+    int32_t portEq[4];                  // branch equations of the ports
+    double eps;
+    double kT40, gs;                    // 4 k 290 and 1 / Z0 of port 1 (noise parameters, P == 2)
+    const double* sys;
+    const double* omega;
+    const int32_t *srcA, *srcB;         // [S] generator terminals (equations, -1 ground)
+    const double* psd;
+    size_t psdStride, psdOff;
+    double* y;                          // [F][P][P][B] complex or null
+    double* cy;                         // [F][P][P][B] complex
+    double *nf, *fmin, *rn;             // [F][B] or null (P == 2)
+    double* yopt;                       // [F][B] complex or null (P == 2)
+    double* x;                          // [F][P][N][B] complex or null: the adjoint solutions
+    uint32_t* status;                   // [B], OR-ed
+};
+hipError_t launchSpNoiseSweep(int which, const SpNoiseArgs& a, hipStream_t stream);
+
 // layout helpers (transpose.hip): [rows][cols] <-> [cols][rows] of doubles
 hipError_t launchTranspose(const double* dIn, double* dOut, int rows, int cols, hipStream_t stream);
 

@@ -233,6 +233,13 @@ int csim_netlist_sp(const csim_netlist* nl, int32_t* enabled, int32_t* sweep, in
     return CSIM_OK;
 }
 
+int csim_netlist_sp_noise(const csim_netlist* nl, int32_t* donoise)
+{
+    if (!nl) return CSIM_ERR_ARG;
+    if (donoise) *donoise = (nl->sim.sp.enabled && nl->sim.sp.doNoise) ? 1 : 0;
+    return CSIM_OK;
+}
+
 // SPICE frequency grid of an .AC card (DEC / OCT: n points per decade / octave from fstart, up to fstop;
 // LIN: n points from fstart to fstop inclusive)
 int64_t csim_ac_num_freqs(int32_t sweep, int32_t n_points, double fstart, double fstop)

@@ -110,6 +110,13 @@ class Netlist:
         capi.check(capi.lib().csim_netlist_sp(self._h, C.byref(en), C.byref(sw), C.byref(npt), C.byref(f0), C.byref(f1)))
         return (AC_SWEEPS[sw.value], npt.value, f0.value, f1.value) if en.value else None
 
+    @property
+    def sp_noise(self):
+        """True when the .SP card carries the trailing 1 (ngspice's donoise): two-port noise wanted with the sweep."""
+        v = C.c_int32()
+        capi.check(capi.lib().csim_netlist_sp_noise(self._h, C.byref(v)))
+        return bool(v.value)
+
     def sp_freqs(self):
         """Frequency grid of the .SP card (numpy, Hz)."""
         card = self.sp
@@ -459,6 +466,58 @@ class Engine:
                                             st.ctypes.data))
         return dict(freqs=f, y=y, s=s, status=st)
 
+    def sp_noise(self, params, x_op, freqs=None, temp=300.15, status=None, noise_params=None):
+        """Two-port noise sweep of the batch around the operating points x_op (device [N][B], from dc());
+        csim_spnoise_batch_dev.  freqs: Hz, None = the .SP card; temp in kelvin (the generators' temperature; NF is
+        referred to 290 K).  noise_params: None = for two ports; True with any other port count is a ValueError.
+        -> dict(freqs, y, cy complex [F][P][P][B], status [B]) and, for two ports, nf, fmin, rn [F][B] (linear) and
+        yopt complex [F][B]; device tensors; status is OR-ed into `status` when given."""
+        torch = _torch()
+        B = params.shape[1]
+        f = self.netlist.sp_freqs() if freqs is None else np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        P = len(self.netlist.ports)
+        if noise_params and P != 2:
+            raise ValueError("NF, Fmin, Rn and Yopt exist for two ports only (the netlist has %d)" % P)
+        two = P == 2 if noise_params is None else bool(noise_params)
+        dev = self._dev()
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)     # noqa: E731
+        y, cy = z(len(f), P, P, B, 2), z(len(f), P, P, B, 2)
+        nf, fmin, rn, yopt = (z(len(f), B), z(len(f), B), z(len(f), B), z(len(f), B, 2)) if two else (None,) * 4
+        st = status if status is not None else torch.zeros(B, dtype=torch.int32, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None     # noqa: E731
+        capi.check(capi.lib().csim_spnoise_batch_dev(self._h, params.data_ptr(), B, x_op.data_ptr(), f.ctypes.data, len(f),
+                                                     float(temp), y.data_ptr(), cy.data_ptr(), ptr(nf), ptr(fmin), ptr(rn),
+                                                     ptr(yopt), st.data_ptr(), self._stream()))
+        r = dict(freqs=f, y=torch.view_as_complex(y), cy=torch.view_as_complex(cy), status=st)
+        if two:
+            r.update(nf=nf, fmin=fmin, rn=rn, yopt=torch.view_as_complex(yopt))
+        return r
+
+    def sp_noise_host(self, params=None, B=1, freqs=None, temp=300.15, noise_params=None):
+        """DC operating point + two-port noise sweep (csim_spnoise_batch): numpy, instance-major.
+        -> dict(freqs, y, cy complex [B][F][P][P], status [B]) and, for two ports, nf, fmin, rn [B][F], yopt complex
+        [B][F]"""
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=np.float64)
+            B = params.shape[0]
+        f = self.netlist.sp_freqs() if freqs is None else np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        P = len(self.netlist.ports)
+        if noise_params and P != 2:
+            raise ValueError("NF, Fmin, Rn and Yopt exist for two ports only (the netlist has %d)" % P)
+        two = P == 2 if noise_params is None else bool(noise_params)
+        y = np.zeros((B, len(f), P, P), dtype=np.complex128)
+        cy = np.zeros((B, len(f), P, P), dtype=np.complex128)
+        nf, fmin, rn = (np.zeros((B, len(f))) for _ in range(3)) if two else (None,) * 3
+        yopt = np.zeros((B, len(f)), dtype=np.complex128) if two else None
+        st = np.zeros(B, dtype=np.uint32)
+        ptr = lambda a: a.ctypes.data if a is not None else None    # noqa: E731
+        capi.check(capi.lib().csim_spnoise_batch(self._h, ptr(params), B, f.ctypes.data, len(f), float(temp), y.ctypes.data,
+                                                 cy.ctypes.data, ptr(nf), ptr(fmin), ptr(rn), ptr(yopt), st.ctypes.data))
+        r = dict(freqs=f, y=y, cy=cy, status=st)
+        if two:
+            r.update(nf=nf, fmin=fmin, rn=rn, yopt=yopt)
+        return r
+
     def dc_host(self, params=None, B=1):
         if params is not None:
             params = np.ascontiguousarray(params, dtype=np.float64)
@@ -737,6 +796,45 @@ def sp_solve_batch(G, Cm, J, omega, kernel="auto", device=0, port_eq=None, z0=No
                                      x.ctypes.data, flags.ctypes.data, pe.ctypes.data, z.ctypes.data, y.ctypes.data,
                                      s.ctypes.data if s is not None else None))
     return dict(x=x, y=y, s=s, flags=flags)
+
+
+def sp_noise_solve_batch(G, Cm, port_eq, z0, src_a, src_b, psd, omega, kernel="auto", device=0, noise_params=None,
+                         want_x=True):
+    """The two-port noise kernels on systems given directly (csim_spnoise_solve_batch): (G + j w C)^T L = unit vectors
+    at port_eq.  G, Cm [B][n][n] real; port_eq, z0 [P]; generators src_a, src_b [S] (-1 = ground) with psd [B][S];
+    omega [F] rad/s; kernel auto | wave | packed.  noise_params: None = for two ports; True with any other port count
+    is a ValueError.
+    -> dict(y, cy complex [B][F][P][P], x complex [B][F][P][n] or None, flags [B]) and, for two ports, nf, fmin, rn
+       [B][F], yopt complex [B][F]."""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    Cm = np.ascontiguousarray(Cm, dtype=np.float64)
+    omega = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
+    pe = np.ascontiguousarray(port_eq, dtype=np.int32).reshape(-1)
+    z = np.ascontiguousarray(z0, dtype=np.float64).reshape(-1)
+    src_a = np.ascontiguousarray(src_a, dtype=np.int32).reshape(-1)
+    src_b = np.ascontiguousarray(src_b, dtype=np.int32).reshape(-1)
+    B, n, F, P, S = G.shape[0], G.shape[1], len(omega), len(pe), len(src_a)
+    if len(z) != P:
+        raise ValueError("port_eq and z0 differ in length")
+    if noise_params and P != 2:
+        raise ValueError("NF, Fmin, Rn and Yopt exist for two ports only (%d given)" % P)
+    two = P == 2 if noise_params is None else bool(noise_params)
+    psd = np.ascontiguousarray(psd, dtype=np.float64).reshape(B, S)
+    y = np.zeros((B, F, P, P), dtype=np.complex128)
+    cy = np.zeros((B, F, P, P), dtype=np.complex128)
+    nf, fmin, rn = (np.zeros((B, F)) for _ in range(3)) if two else (None,) * 3
+    yopt = np.zeros((B, F), dtype=np.complex128) if two else None
+    x = np.zeros((B, F, P, n), dtype=np.complex128) if want_x else None
+    flags = np.zeros(B, dtype=np.uint32)
+    ptr = lambda a: a.ctypes.data if a is not None else None    # noqa: E731
+    capi.check(capi.lib().csim_spnoise_solve_batch(
+        device, n, B, P, G.ctypes.data, Cm.ctypes.data, pe.ctypes.data, z.ctypes.data, S, src_a.ctypes.data,
+        src_b.ctypes.data, psd.ctypes.data, omega.ctypes.data, F, ("auto", "wave", "packed").index(kernel), y.ctypes.data,
+        cy.ctypes.data, ptr(nf), ptr(fmin), ptr(rn), ptr(yopt), ptr(x), flags.ctypes.data))
+    r = dict(y=y, cy=cy, x=x, flags=flags)
+    if two:
+        r.update(nf=nf, fmin=fmin, rn=rn, yopt=yopt)
+    return r
 
 
 def gs_solve_batch(A, b, x0=None, max_iters=1000, tol=1e-10, device=0):

@@ -148,6 +148,9 @@ int  csim_netlist_port(const csim_netlist* nl, int32_t i, int32_t* elem, int32_t
 /* .SP DEC|OCT|LIN n fstart fstop: the sweep as for .AC */
 int  csim_netlist_sp(const csim_netlist* nl, int32_t* enabled, int32_t* sweep, int32_t* n_points, double* fstart,
                      double* fstop);
+/* .SP ... 1: the card's trailing donoise token ("Two-port noise analysis" below); 0 without a card, without the
+ * token, or with any other sixth token.                                                                         */
+int  csim_netlist_sp_noise(const csim_netlist* nl, int32_t* donoise);
 /* Monte-Carlo recipe per parameter slot: 0 fixed, 1 scaled by (1+sigma z),
  * 2 MOS K rebuilt from a MU draw: K = (MU(1+sigma z))*COX*(W/L)              */
 int  csim_netlist_mc_kinds(const csim_netlist* nl, int32_t* kinds);
@@ -395,6 +398,59 @@ int  csim_sp_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int3
 int  csim_sp_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F, double* y,
                    double* s, uint32_t* status);
 
+/* ---- Two-port noise analysis (.SP ... 1; Y, the port noise-current correlation matrix Cy and, for two ports, NF,
+ *      NFmin, Rn and Yopt by one adjoint factorisation per frequency) ----
+ * Card: `.SP DEC|OCT|LIN n fstart fstop 1`, ngspice's donoise; the token only records the wish
+ *   (csim_netlist_sp_noise), the entry points below work with or without it.
+ * System.  For instance b and angular frequency w, A = G + j w C is exactly the matrix of "AC analysis": the same
+ *   assembly, the same elements left out.  Ports are those of "S-parameter analysis", k_i the branch equation of port
+ *   i; generators those of "Noise analysis": the same elements, the same PSD formulas at temp_k.
+ * Adjoint multi-RHS solve.  A^T L = [e_{k_1} ... e_{k_P}], real unit vectors, with the transposed load of "Noise
+ *   analysis" (A^T(i,j) = G(j,i) + j (w C(j,i)), w C one product) and the multi-RHS algorithm of "S-parameter
+ *   analysis"; pivoting never looks at a right-hand side.  lambda_i is column i.  A column maximum below lu_eps^2:
+ *   every output of that (instance, frequency) is +0.0, CSIM_ST_LU_TINY_PIVOT is OR-ed into the status, the sweep
+ *   goes on.
+ * Y(i,j) = -lambda_i[k_j], both parts negated.  Mathematically the Y of csim_sp_batch; numerically it comes from the
+ *   factorisation of the transposed matrix, so its low bits may differ from csim_sp_batch's.
+ * Cy.  Per generator s between equations (a_s, b_s): t_i = lambda_i[a_s] - lambda_i[b_s] (ground = (0, 0)).  For
+ *   i <= j:  q.re = (t_i.re t_j.re + t_i.im t_j.im) psd_s,  q.im = (t_i.im t_j.re - t_i.re t_j.im) psd_s.
+ *   Cy(i,j) = 0.0 + q(0) + q(1) + ... in ascending s, re and im separately; Cy(j,i) = conj(Cy(i,j)) (im negated).
+ *   The diagonal sums the real part alone and its imaginary part is +0.0: Cy(i,i).re is bit for bit the onoise of
+ *   "Noise analysis" taken with the output at k_i.  A^2/Hz, one-sided.
+ * Noise parameters, P == 2 only, port 1 the input and port 2 the output; all linear (decibels are the caller's).
+ *   kT4_0 = 4.0 * 1.380649e-23 * 290.0 (the IEEE reference temperature, whatever temp_k) and Gs = 1.0 / Z0_1 are
+ *   computed once on the host.  Every real division below is x * (1.0 / y), complex ones the AC division:
+ *     d = Y21.re Y21.re + Y21.im Y21.im     r = Y11 / Y21     Cvv = Cy22.re * (1 / d)
+ *     Cii = (Cy11.re - 2.0 * (r.re Cy12.re + r.im Cy12.im)) + (r.re r.re + r.im r.im) * Cy22.re
+ *     q = (Cy12.re - r.re Cy22.re,  r.im Cy22.re - Cy12.im) / Y21        (Cvi = -q)
+ *     Gcor = (-q.re) * (1 / Cvv)    Bcor = q.im * (1 / Cvv)              (Ycor = conj(Cvi) / Cvv)
+ *     Rn = Cvv * (1 / kT4_0)        Gu = (Cii - (Gcor Gcor + Bcor Bcor) * Cvv) * (1 / kT4_0)
+ *     Gopt = sqrt(max0(Gu * (1 / Rn) + Gcor Gcor)), max0(x) = x < 0.0 ? 0.0 : x (a NaN passes through)
+ *     Yopt = (Gopt, -Bcor)          Fmin = 1.0 + (2.0 * Rn) * (Gcor + Gopt)
+ *     NF = 1.0 + (Gu + Rn * ((Gs + Gcor) (Gs + Gcor) + Bcor Bcor)) * (1 / Gs)
+ *   Cvv not > 0.0 (a noiseless or purely current-noisy two-port): Rn = +0.0, Yopt = (+0.0, +0.0), Fmin = 1.0,
+ *   NF = 1.0 + (Cii * (1 / kT4_0)) * (1 / Gs).  Y21 == 0 gets no special case: the outputs are what IEEE arithmetic
+ *   gives.  The exact order of every operation: engine/ac_port_noise.hpp, written once for host and device.
+ * No FMA contraction anywhere.  Circuits of up to 63 unknowns (CSIM_ERR_UNSUPPORTED beyond); no port or a bad port
+ * numbering: CSIM_ERR_CONFIG; temp_k <= 0 or not finite: CSIM_ERR_CONFIG; a non-NULL noise-parameter pointer with
+ * P != 2: CSIM_ERR_CONFIG.  S == 0 is legal: Cy = 0.
+ *
+ * Enqueues the sweep; never waits for it; frequency lists as csim_ac_batch_dev (same buffers, same discipline).
+ *   d_y, d_cy [F][P][P][B] complex (re, im), row i then column j, instance fastest
+ *   d_nf, d_fmin, d_rn [F][B]    d_yopt [F][B] complex    d_status [B], OR-ed
+ * Every output but d_cy may be NULL (the Python binding's noise_params=False passes NULL for the four noise
+ * parameters).  The engine option ac_kernel picks the kernel as for AC; both give bit-identical
+ * results.                                                                                                        */
+int  csim_spnoise_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int32_t B, const double* d_xop,
+                            const double* freqs, int32_t F, double temp_k, double* d_y, double* d_cy, double* d_nf,
+                            double* d_fmin, double* d_rn, double* d_yopt, uint32_t* d_status, void* stream);
+/* DC operating point, then the sweep.  params [B][P] or NULL (nominal); freqs NULL = the grid of the netlist's .SP
+ * card (F ignored; no card: CSIM_ERR_CONFIG).  y, cy [B][F][P][P] complex; nf, fmin, rn [B][F]; yopt [B][F] complex;
+ * every output but cy may be NULL.                                                                                */
+int  csim_spnoise_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F,
+                        double temp_k, double* y, double* cy, double* nf, double* fmin, double* rn, double* yopt,
+                        uint32_t* status);
+
 /* Batched dense solve A x = b with the engine's pivoted LU
  * (Solver::solveLinearSystemLU semantics: first-maximum partial pivoting,
  * tiny pivot -> zero vector).  A [B][n][n] row-major, b/x [B][n], host
@@ -433,6 +489,19 @@ int  csim_noise_solve_batch(int32_t device, int32_t n, int32_t B, const double* 
 int  csim_sp_solve_batch(int32_t device, int32_t n, int32_t B, int32_t K, const double* G, const double* C,
                          const double* J, const double* omega, int32_t F, int32_t kernel, double* x, uint32_t* flags,
                          const int32_t* port_eq, const double* z0, double* y, double* s);
+
+/* The two-port noise kernels on systems, ports and generator tables given directly (host pointers; lu_eps = 1e-15),
+ * the counterpart of csim_ac_solve_batch for "Two-port noise analysis".  G, C [B][n][n] row-major; port_eq [P],
+ * z0 [P] (Gs = 1 / z0[0]), 1 <= P <= 4; generators src_a, src_b [S] (equations, -1 ground) with psd [B][S]; omega [F]
+ * rad/s.  cy [B][F][P][P] complex; y the same, nf, fmin, rn [B][F], yopt [B][F] complex, x [B][F][P][n] complex (the
+ * adjoint solutions, zeros where the factorisation fails) and flags [B] are optional.  kernel and sizes as
+ * csim_ac_solve_batch; P outside 1 .. 4, an equation index out of range or a Z0 that is not finite and > 0:
+ * CSIM_ERR_ARG; a noise parameter asked for with P != 2: CSIM_ERR_CONFIG.                                          */
+int  csim_spnoise_solve_batch(int32_t device, int32_t n, int32_t B, int32_t P, const double* G, const double* C,
+                              const int32_t* port_eq, const double* z0, int32_t S, const int32_t* src_a,
+                              const int32_t* src_b, const double* psd, const double* omega, int32_t F, int32_t kernel,
+                              double* y, double* cy, double* nf, double* fmin, double* rn, double* yopt, double* x,
+                              uint32_t* flags);
 
 /* ---- Gauss-Seidel variant of the reference (never reached from its main(), kept as public API) ----
  * Batched Solver::solveLinearSystemGaussSeidel (include/solver.hpp:139-204): sweeps in row order with the
