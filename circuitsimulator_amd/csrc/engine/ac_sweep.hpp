@@ -3,12 +3,14 @@
 // right-hand sides -- ac_lu.hpp's primitives applied in the order of ac_lu_solve_multi(), by one wavefront on a system
 // in LDS, or by 32 lanes on a system in registers -- and the scaffolding around it (LDS carve-up, the G + jwC load,
 // instance indexing, launch dispatch).  AC and noise are K = 1.  Included by those four files only.
+// A third shape, one 256-thread workgroup per system for N <= 1024 (AC and noise only), is ac_block.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
+#include "ac_block.hpp"
 #include "ac_lu.hpp"
 #include "device_common.hpp"
 #include "kernels.hpp"
@@ -231,8 +233,28 @@ __device__ __forceinline__ void acp_back(const double (&ar)[NP + KP], const doub
     }
 }
 
-// ---- launch: the sizes the two kernel shapes cover, and the packed kernel's NP = N rounded up to 8
-inline bool ac_sweep_covers(int which, int N) { return N >= 1 && N <= 63 && !(which == AC_KERNEL_PACKED && N > 32); }
+// ---- launch: the sizes the kernel shapes cover, and the packed kernel's NP = N rounded up to 8
+inline bool ac_sweep_covers(int which, int N)
+{
+    if (which == AC_KERNEL_BLOCK) return N >= 1 && N <= ACB_MAX_N;
+    return N >= 1 && N <= 63 && !(which == AC_KERNEL_PACKED && N > 32);
+}
+
+// A = G + jwC (or A^T) into the block shape's planes, the workgroup walking the words in address order
+template <bool TRANSPOSED>
+__device__ __forceinline__ void acb_load(int N, int LD, const double* Gt, const double* Ct, double w, double* Ar, double* Ai,
+                                         int tid)
+{
+    for (int idx = tid; idx < N * N; idx += ACB_THREADS) {
+        const int q = idx / N, m = idx - q * N;
+        const int i = TRANSPOSED ? q : m, j = TRANSPOSED ? m : q;
+        Ar[i * LD + j] = Gt[idx];
+        Ai[i * LD + j] = w * Ct[idx];
+    }
+}
+
+// the planes of chunk instance c in the block shape's scratch: acBlockWorkDoubles(N) doubles per instance
+__device__ __forceinline__ double* acb_work_at(double* work, int c, int N, int LD) { return work + (size_t)c * 2 * N * LD; }
 
 // launch(std::integral_constant<int, NP>)
 template <class Launch>

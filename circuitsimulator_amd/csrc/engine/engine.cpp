@@ -357,6 +357,7 @@ void csim_engine_destroy(csim_engine* eng)
             if (s.d) (void)hipFree(s.d);
         }
     if (eng->dAcSys) (void)hipFree(eng->dAcSys);
+    if (eng->dAcWork) (void)hipFree(eng->dAcWork);
     if (eng->dNoisePsd) (void)hipFree(eng->dNoisePsd);
     if (eng->schedLib) dlclose(eng->schedLib);
     delete eng;
@@ -424,7 +425,8 @@ int csim_engine_set_option(csim_engine* eng, const char* key, const char* value)
         if (v == "auto") c.acKernel = csim::AC_KERNEL_AUTO;
         else if (v == "wave") c.acKernel = csim::AC_KERNEL_WAVE;
         else if (v == "packed") c.acKernel = csim::AC_KERNEL_PACKED;
-        else { setError("ac_kernel must be auto, wave or packed"); return CSIM_ERR_ARG; }
+        else if (v == "block") c.acKernel = csim::AC_KERNEL_BLOCK;
+        else { setError("ac_kernel must be auto, wave, packed or block"); return CSIM_ERR_ARG; }
     }
     else { setError("csim_engine_set_option: unknown option '" + k + "'"); return CSIM_ERR_ARG; }
     return CSIM_OK;
@@ -826,11 +828,15 @@ int csim_dc_batch(csim_engine* eng, const double* params, int32_t B, double* x_o
 // ---- AC small-signal analysis ----------------------------------------------
 
 // the system of every instance lives in device scratch between assembly and sweep; instances are processed in
-// chunks that keep it below 256 MiB
+// chunks that keep it below 256 MiB; under ac_kernel=block the planes of the solve live there too, and a chunk may
+// shrink to 32 instances (the planes of a 1024-unknown system are 16 MiB)
+static bool acBlock(const csim_engine* eng) { return eng->cfg.acKernel == csim::AC_KERNEL_BLOCK; }
+
 static size_t acChunkCap(const csim_engine* eng)
 {
-    const size_t per = sizeof(double) * csim::acSystemDoubles(eng->plan.N);
-    return std::max<size_t>(256, ((size_t)256 << 20) / per);
+    size_t per = sizeof(double) * csim::acSystemDoubles(eng->plan.N);
+    if (acBlock(eng)) per += sizeof(double) * csim::acBlockWorkDoubles(eng->plan.N);
+    return std::max<size_t>(acBlock(eng) ? 32 : 256, ((size_t)256 << 20) / per);
 }
 
 static int acChunk(const csim_engine* eng, int B)
@@ -838,9 +844,23 @@ static int acChunk(const csim_engine* eng, int B)
     return (int)std::min<size_t>((size_t)B, acChunkCap(eng));
 }
 
+// the sizes the frequency-domain analyses cover: 63 unknowns, or with ac_kernel=block (AC and noise) 1024
+static bool acSizeRefused(const csim_engine* eng)
+{
+    return eng->plan.N > (acBlock(eng) ? 1024 : 63);
+}
+
+// the block kernel carries one right-hand side: the port analyses have none for it yet
+static int acBlockRefused(const csim_engine* eng, const char* what)
+{
+    if (!acBlock(eng)) return CSIM_OK;
+    setError(std::string(what) + ": ac_kernel=block covers AC and noise analysis only");
+    return CSIM_ERR_UNSUPPORTED;
+}
+
 static int acCheck(const csim_engine* eng)
 {
-    if (eng->plan.N > 63) { setError("AC analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
+    if (acSizeRefused(eng)) { setError("AC analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
     if (!eng->acAnySource) { setError("AC analysis: no source carries an AC magnitude (V/I ... AC mag [phase])"); return CSIM_ERR_CONFIG; }
     return CSIM_OK;
 }
@@ -908,14 +928,26 @@ static int acSysScratch(csim_engine* eng, int chunk)
     return CSIM_OK;
 }
 
+// the block kernel's planes, grown to `chunk` instances (nothing under the other kernels)
+static int acWorkScratch(csim_engine* eng, int chunk)
+{
+    if (!acBlock(eng) || eng->acWorkCap >= chunk) return CSIM_OK;
+    if (eng->dAcWork) HIPCHK(hipFree(eng->dAcWork));
+    eng->dAcWork = nullptr;
+    eng->acWorkCap = 0;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&eng->dAcWork), sizeof(double) * csim::acBlockWorkDoubles(eng->plan.N) * (size_t)chunk));
+    eng->acWorkCap = chunk;
+    return CSIM_OK;
+}
+
 int csim_ac_system_dev(csim_engine* eng, const double* d_params, int32_t B, const double* d_xop, double* d_sys, void* stream)
 {
     if (!eng || B < 0 || (B > 0 && (!d_params || !d_xop || !d_sys))) { setError("csim_ac_system_dev: bad argument"); return CSIM_ERR_ARG; }
-    if (eng->plan.N > 63) { setError("AC analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
+    if (acSizeRefused(eng)) { setError("AC analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
     if (B == 0) return CSIM_OK;
     HIPCHK(hipSetDevice(eng->device));
     HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, 0, B, d_xop, d_sys,
-                                  static_cast<hipStream_t>(stream)));
+                                  static_cast<hipStream_t>(stream), eng->cfg.acKernel));
     return CSIM_OK;
 }
 
@@ -935,7 +967,7 @@ int csim_ac_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const
             if (probe_eq[i] < 0 || probe_eq[i] >= N) { setError("probe equation index out of range"); return CSIM_ERR_ARG; }
     }
     int which = eng->cfg.acKernel;
-    if (which == csim::AC_KERNEL_AUTO) which = N <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
+    if (which == csim::AC_KERNEL_AUTO) which = N <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;   // block: as it is
     if (which == csim::AC_KERNEL_PACKED && N > 32) { setError("ac_kernel=packed covers N <= 32"); return CSIM_ERR_UNSUPPORTED; }
     if (B == 0 || F == 0) return CSIM_OK;
     HIPCHK(hipSetDevice(eng->device));
@@ -956,11 +988,12 @@ int csim_ac_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const
     }
     const int chunk = acChunk(eng, B);
     if (const int rc = acSysScratch(eng, chunk)) return rc;
+    if (const int rc = acWorkScratch(eng, chunk)) return rc;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int Bc = std::min(chunk, B - b0);
-        HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, b0, Bc, d_xop, eng->dAcSys, hs));
+        HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, b0, Bc, d_xop, eng->dAcSys, hs, which));
         HIPCHK(csim::launchAcSweep(which, N, eng->dAcSys, dOmega, F, dProbe, nProbe, B, b0, Bc, eng->cir.ir.k.lu_eps,
-                                   d_out, d_status, hs));
+                                   d_out, d_status, hs, eng->dAcWork));
     }
     HIPCHK(hipEventRecord(eng->acOmegaSlots[(size_t)eng->acOmegaCur].done, hs));
     if (dProbe) HIPCHK(hipEventRecord(eng->acProbeSlots[(size_t)eng->acProbeCur].done, hs));
@@ -1038,7 +1071,7 @@ static int noiseCardFreqs(const csim_engine* eng, std::vector<double>& card)
 static int noiseSetup(const csim_engine* eng, int out_p, int out_m, int src_elem, double temp_k, csim::NoiseArgs& a, double& kT4)
 {
     const int N = eng->plan.N;
-    if (N > 63) { setError("noise analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
+    if (acSizeRefused(eng)) { setError("noise analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
     if (out_p < 0 || out_p >= N || out_m < -1 || out_m >= N || out_p == out_m) {
         setError("noise analysis: the output needs two different equations, out_p >= 0 (out_m = -1: ground)");
         return CSIM_ERR_ARG;
@@ -1084,7 +1117,7 @@ int csim_noise_batch_dev(csim_engine* eng, const double* d_params, int32_t B, co
     if (const int rc = noiseSetup(eng, out_p_eq, out_m_eq, src_elem, temp_k, a, kT4)) return rc;
     const int N = a.N, S = a.S;
     int which = eng->cfg.acKernel;
-    if (which == csim::AC_KERNEL_AUTO) which = N <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
+    if (which == csim::AC_KERNEL_AUTO) which = N <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;   // block: as it is
     if (which == csim::AC_KERNEL_PACKED && N > 32) { setError("ac_kernel=packed covers N <= 32"); return CSIM_ERR_UNSUPPORTED; }
     if (B == 0 || F == 0) return CSIM_OK;
     HIPCHK(hipSetDevice(eng->device));
@@ -1094,6 +1127,7 @@ int csim_noise_batch_dev(csim_engine* eng, const double* d_params, int32_t B, co
     if (const int rc = acOmega(eng, freqs, F, &dOmega)) return rc;
     const int chunk = acChunk(eng, B);
     if (const int rc = acSysScratch(eng, chunk)) return rc;
+    if (const int rc = acWorkScratch(eng, chunk)) return rc;
     if (!d_psd && eng->noisePsdCap < (size_t)S * (size_t)chunk) {
         if (eng->dNoisePsd) HIPCHK(hipFree(eng->dNoisePsd));
         eng->dNoisePsd = nullptr;
@@ -1110,6 +1144,7 @@ int csim_noise_batch_dev(csim_engine* eng, const double* d_params, int32_t B, co
     a.contrib = d_contrib;
     a.y = nullptr;
     a.status = d_status;
+    a.work = eng->dAcWork;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int Bc = std::min(chunk, B - b0);
         a.b0 = b0;
@@ -1117,7 +1152,7 @@ int csim_noise_batch_dev(csim_engine* eng, const double* d_params, int32_t B, co
         a.psd = d_psd ? d_psd : eng->dNoisePsd;
         a.psdStride = d_psd ? (size_t)B : (size_t)chunk;
         a.psdOff = d_psd ? (size_t)b0 : 0;
-        HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, b0, Bc, d_xop, eng->dAcSys, hs));
+        HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, b0, Bc, d_xop, eng->dAcSys, hs, which));
         HIPCHK(csim::launchNoisePsd(eng->gpTran, eng->dNoiseElem, S, d_params, B, b0, Bc, d_xop, kT4,
                                     d_psd ? d_psd : eng->dNoisePsd, a.psdStride, a.psdOff, hs));
         HIPCHK(csim::launchNoiseSweep(which, a, hs));
@@ -1131,7 +1166,7 @@ int csim_noise_batch(csim_engine* eng, const double* params, int32_t B, const do
                      double* psd, uint32_t* status)
 {
     if (!eng || B < 0) { setError("csim_noise_batch: bad argument"); return CSIM_ERR_ARG; }
-    if (eng->plan.N > 63) { setError("noise analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
+    if (acSizeRefused(eng)) { setError("noise analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
     std::vector<double> card;
     if (!freqs) {
         if (const int rc = noiseCardFreqs(eng, card)) return rc;
@@ -1186,6 +1221,7 @@ int csim_noise_batch(csim_engine* eng, const double* params, int32_t B, const do
 static int spSetup(const csim_engine* eng, csim::SpArgs& a)
 {
     const int N = eng->plan.N;
+    if (const int rc = acBlockRefused(eng, "S-parameter and two-port noise analysis")) return rc;
     if (!eng->spPortError.empty()) { setError(eng->spPortError); return CSIM_ERR_CONFIG; }
     const int P = (int)eng->spPortEq.size();
     if (P == 0) { setError("S-parameter analysis: the netlist declares no port (V ... PORTNUM k [Z0 r])"); return CSIM_ERR_CONFIG; }
@@ -1213,7 +1249,7 @@ int csim_sp_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const
     }
     const int N = a.N;
     int which = eng->cfg.acKernel;
-    if (which == csim::AC_KERNEL_AUTO) which = N <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
+    if (which == csim::AC_KERNEL_AUTO) which = N <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;   // block: as it is
     if (which == csim::AC_KERNEL_PACKED && N > 32) { setError("ac_kernel=packed covers N <= 32"); return CSIM_ERR_UNSUPPORTED; }
     if (B == 0 || F == 0) return CSIM_OK;
     HIPCHK(hipSetDevice(eng->device));
@@ -1320,7 +1356,7 @@ int csim_spnoise_batch_dev(csim_engine* eng, const double* d_params, int32_t B, 
     }
     const int N = a.N, S = a.S;
     int which = eng->cfg.acKernel;
-    if (which == csim::AC_KERNEL_AUTO) which = N <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
+    if (which == csim::AC_KERNEL_AUTO) which = N <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;   // block: as it is
     if (which == csim::AC_KERNEL_PACKED && N > 32) { setError("ac_kernel=packed covers N <= 32"); return CSIM_ERR_UNSUPPORTED; }
     if (B == 0 || F == 0) return CSIM_OK;
     HIPCHK(hipSetDevice(eng->device));
@@ -1716,14 +1752,20 @@ static std::vector<double> packAcSystems(int n, int B, const double* G, const do
     return sys;
 }
 
+// the selector values of the *_solve_batch entries (3 is none)
+static bool acKernelValid(int kernel)
+{
+    return (kernel >= csim::AC_KERNEL_AUTO && kernel <= csim::AC_KERNEL_PACKED) || kernel == csim::AC_KERNEL_BLOCK;
+}
+
 // The common front of the engine-free *_solve_batch entries: device check, kernel choice and its refusals; then, when
 // there is work, the packed systems, the angular frequencies and zeroed flags on the device.
 struct AcSolveFront {
     int which = csim::AC_KERNEL_AUTO;
-    DevBuf dSys, dOmega, dF;
+    DevBuf dSys, dOmega, dF, dWork;         // dWork: the block kernel's planes
 };
 static int acSolveFront(const char* entry, int device, int n, int B, const double* G, const double* Cm, const double* J,
-                        const double* omega, int F, int kernel, bool work, AcSolveFront& fr)
+                        const double* omega, int F, int kernel, bool work, AcSolveFront& fr, bool blockCovered = false)
 {
     const std::string name(entry);
     int count = 0;
@@ -1731,7 +1773,10 @@ static int acSolveFront(const char* entry, int device, int n, int B, const doubl
         setError(name + ": no usable HIP device (this library has no CPU path)");
         return CSIM_ERR_NO_DEVICE;
     }
-    if (n > 63) { setError(name + " covers n <= 63"); return CSIM_ERR_UNSUPPORTED; }
+    if (kernel == csim::AC_KERNEL_BLOCK) {
+        if (!blockCovered) { setError(name + ": the block kernel covers AC and noise analysis only"); return CSIM_ERR_UNSUPPORTED; }
+        if (n > 1024) { setError(name + ": the block kernel covers n <= 1024"); return CSIM_ERR_UNSUPPORTED; }
+    } else if (n > 63) { setError(name + " covers n <= 63"); return CSIM_ERR_UNSUPPORTED; }
     fr.which = kernel;
     if (fr.which == csim::AC_KERNEL_AUTO) fr.which = n <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
     if (fr.which == csim::AC_KERNEL_PACKED && n > 32) { setError(name + ": the packed kernel covers n <= 32"); return CSIM_ERR_UNSUPPORTED; }
@@ -1741,6 +1786,7 @@ static int acSolveFront(const char* entry, int device, int n, int B, const doubl
     HIPCHK(fr.dSys.alloc(sizeof(double) * sys.size()));
     HIPCHK(fr.dOmega.alloc(sizeof(double) * (size_t)F));
     HIPCHK(fr.dF.alloc(sizeof(uint32_t) * (size_t)B));
+    if (fr.which == csim::AC_KERNEL_BLOCK) HIPCHK(fr.dWork.alloc(sizeof(double) * csim::acBlockWorkDoubles(n) * (size_t)B));
     HIPCHK(hipMemcpy(fr.dSys.p, sys.data(), sizeof(double) * sys.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(fr.dOmega.p, omega, sizeof(double) * (size_t)F, hipMemcpyHostToDevice));
     HIPCHK(hipMemset(fr.dF.p, 0, sizeof(uint32_t) * (size_t)B));
@@ -1751,21 +1797,21 @@ static int acSolveFront(const char* entry, int device, int n, int B, const doubl
 int csim_ac_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* Cm, const double* J,
                         const double* omega, int32_t F, int32_t kernel, double* x, uint32_t* flags)
 {
-    if (n < 0 || B < 0 || F < 0 || kernel < csim::AC_KERNEL_AUTO || kernel > csim::AC_KERNEL_PACKED ||
+    if (n < 0 || B < 0 || F < 0 || !acKernelValid(kernel) ||
         (n > 0 && B > 0 && F > 0 && (!G || !Cm || !J || !omega || !x))) {
         setError("csim_ac_solve_batch: bad argument");
         return CSIM_ERR_ARG;
     }
     const bool work = n > 0 && B > 0 && F > 0;
     AcSolveFront fr;
-    if (const int rc = acSolveFront("csim_ac_solve_batch", device, n, B, G, Cm, J, omega, F, kernel, work, fr)) return rc;
+    if (const int rc = acSolveFront("csim_ac_solve_batch", device, n, B, G, Cm, J, omega, F, kernel, work, fr, true)) return rc;
     if (!work) return CSIM_OK;
     const size_t outDoubles = (size_t)2 * F * n * B;
     DevBuf dOut;
     HIPCHK(dOut.alloc(sizeof(double) * outDoubles));
     HIPCHK(hipMemset(dOut.p, 0, sizeof(double) * outDoubles));
     HIPCHK(csim::launchAcSweep(fr.which, n, fr.dSys.as<double>(), fr.dOmega.as<double>(), F, nullptr, n, B, 0, B, 1e-15,
-                               dOut.as<double>(), fr.dF.as<uint32_t>(), nullptr));
+                               dOut.as<double>(), fr.dF.as<uint32_t>(), nullptr, fr.dWork.as<double>()));
     HIPCHK(hipDeviceSynchronize());
     if (const int rc = toHost(dOut.as<double>(), F, n, B, 2, x)) return rc;
     if (flags) HIPCHK(hipMemcpy(flags, fr.dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
@@ -1779,7 +1825,7 @@ int csim_noise_solve_batch(int32_t device, int32_t n, int32_t B, const double* G
                            double* onoise, double* contrib, double* gain, double* y, uint32_t* flags)
 {
     const bool work = n > 0 && B > 0 && F > 0;
-    if (n < 0 || B < 0 || F < 0 || S < 0 || kernel < csim::AC_KERNEL_AUTO || kernel > csim::AC_KERNEL_PACKED ||
+    if (n < 0 || B < 0 || F < 0 || S < 0 || !acKernelValid(kernel) ||
         in_kind < csim::NOISE_IN_NONE || in_kind > csim::NOISE_IN_I ||
         (work && (!G || !Cm || !omega || !onoise || (S > 0 && (!src_a || !src_b || !psd))))) {
         setError("csim_noise_solve_batch: bad argument");
@@ -1794,7 +1840,7 @@ int csim_noise_solve_batch(int32_t device, int32_t n, int32_t B, const double* G
         if (!ok) { setError("csim_noise_solve_batch: equation index out of range (or out_p == out_m)"); return CSIM_ERR_ARG; }
     }
     AcSolveFront fr;
-    if (const int rc = acSolveFront("csim_noise_solve_batch", device, n, B, G, Cm, nullptr, omega, F, kernel, work, fr)) return rc;
+    if (const int rc = acSolveFront("csim_noise_solve_batch", device, n, B, G, Cm, nullptr, omega, F, kernel, work, fr, true)) return rc;
     if (!work) return CSIM_OK;
     std::vector<double> psdT((size_t)S * B);                 // [B][S] -> [S][B]
     for (int b = 0; b < B; ++b)
@@ -1831,6 +1877,7 @@ int csim_noise_solve_batch(int32_t device, int32_t n, int32_t B, const double* G
     a.contrib = contrib ? dCon.as<double>() : nullptr;
     a.y = y ? dY.as<double>() : nullptr;
     a.status = fr.dF.as<uint32_t>();
+    a.work = fr.dWork.as<double>();
     HIPCHK(csim::launchNoiseSweep(fr.which, a, nullptr));
     HIPCHK(hipDeviceSynchronize());
     int rc = toHost(dOn.as<double>(), F, 1, B, 1, onoise);
@@ -1850,7 +1897,7 @@ int csim_sp_solve_batch(int32_t device, int32_t n, int32_t B, int32_t K, const d
 {
     const bool work = n > 0 && B > 0 && F > 0;
     const bool ports = port_eq != nullptr;
-    if (n < 0 || B < 0 || F < 0 || kernel < csim::AC_KERNEL_AUTO || kernel > csim::AC_KERNEL_PACKED ||
+    if (n < 0 || B < 0 || F < 0 || !acKernelValid(kernel) ||
         (work && (!G || !Cm || !omega || (ports ? (!z0 || !y) : (!J || !x))))) {
         setError("csim_sp_solve_batch: bad argument");
         return CSIM_ERR_ARG;
@@ -1906,7 +1953,7 @@ int csim_spnoise_solve_batch(int32_t device, int32_t n, int32_t B, int32_t P, co
                              double* nf, double* fmin, double* rn, double* yopt, double* x, uint32_t* flags)
 {
     const bool work = n > 0 && B > 0 && F > 0;
-    if (n < 0 || B < 0 || F < 0 || S < 0 || kernel < csim::AC_KERNEL_AUTO || kernel > csim::AC_KERNEL_PACKED || !port_eq || !z0 ||
+    if (n < 0 || B < 0 || F < 0 || S < 0 || !acKernelValid(kernel) || !port_eq || !z0 ||
         (work && (!G || !Cm || !omega || !cy || (S > 0 && (!src_a || !src_b || !psd))))) {
         setError("csim_spnoise_solve_batch: bad argument");
         return CSIM_ERR_ARG;

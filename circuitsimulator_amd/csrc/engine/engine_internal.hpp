@@ -119,6 +119,8 @@ struct csim_engine {
     std::vector<int32_t> acProbeCache;
     double* dAcSys = nullptr;
     int acSysCap = 0;                      // instances
+    double* dAcWork = nullptr;             // ac_kernel=block: the planes of every chunk instance
+    int acWorkCap = 0;                     // instances
 
     // Noise analysis: the netlist's .NOISE card (resolved), the generator list (element, terminals; uploaded once) and
     // the PSD scratch of one chunk, used when the caller does not ask for the PSDs

@@ -80,13 +80,19 @@ hipError_t launchMcParams(int P, int B, long long bFirst, uint64_t seed, double 
 
 // AC small-signal analysis (kernels_ac.hip).  System of one instance (acSystemDoubles(N) doubles): G and C
 // column-major [N][N], J re [N], J im [N].  Instances b0 .. b0+Bc-1 of a batch of B; dSys holds Bc systems.
-enum { AC_KERNEL_AUTO = 0, AC_KERNEL_WAVE = 1, AC_KERNEL_PACKED = 2 };
+// AC_KERNEL_BLOCK is opt-in: one 256-thread workgroup per system, N <= 1024, AC and noise only; its matrix lives in a
+// scratch of acBlockWorkDoubles(N) doubles per chunk instance (dWork).  The value 3 stays an invalid selector.
+enum { AC_KERNEL_AUTO = 0, AC_KERNEL_WAVE = 1, AC_KERNEL_PACKED = 2, AC_KERNEL_BLOCK = 4 };
 size_t acSystemDoubles(int N);
+size_t acBlockWorkDoubles(int N);
+// which == AC_KERNEL_BLOCK: the assembly that scatters straight to global memory (any N the engine accepts)
 hipError_t launchAcAssemble(const GenPlan& pl, const double* dAcRe, const double* dAcIm, const double* dParams, int B,
-                            int b0, int Bc, const double* dXop, double* dSys, hipStream_t stream);
+                            int b0, int Bc, const double* dXop, double* dSys, hipStream_t stream,
+                            int which = AC_KERNEL_AUTO);
 // dOut [F][nProbe][B] complex (re, im), dStatus [B] OR-ed; dProbe null = every unknown (nProbe = N)
 hipError_t launchAcSweep(int which, int N, const double* dSys, const double* dOmega, int F, const int32_t* dProbe,
-                         int nProbe, int B, int b0, int Bc, double eps, double* dOut, uint32_t* dStatus, hipStream_t stream);
+                         int nProbe, int B, int b0, int Bc, double eps, double* dOut, uint32_t* dStatus, hipStream_t stream,
+                         double* dWork = nullptr);
 
 // Noise analysis (kernels_noise.hip) on the systems launchAcAssemble leaves.  Generator s of chunk instance c has
 // its PSD at psd[s * psdStride + psdOff + c].  Equation indices are checked by the callers: they index LDS.
@@ -105,6 +111,7 @@ struct NoiseArgs {
     double* contrib;                    // [F][S][B] or null
     double* y;                          // [F][N][B] complex or null: the adjoint solution
     uint32_t* status;                   // [B], OR-ed
+    double* work;                       // AC_KERNEL_BLOCK: acBlockWorkDoubles(N) doubles per chunk instance
 };
 hipError_t launchNoisePsd(const GenPlan& pl, const int32_t* dSrcElem, int S, const double* dParams, int B, int b0, int Bc,
                           const double* dXop, double kT4, double* dPsd, size_t psdStride, size_t psdOff, hipStream_t stream);

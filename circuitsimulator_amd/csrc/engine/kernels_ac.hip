@@ -18,8 +18,13 @@
 //                        Rows are exchanged logically: every lane carries the row position it holds; the pivot
 //                        row (a run-time lane) reaches the others by a bpermute per register.
 //
-// Both sweep kernels apply ac_lu.hpp's primitives to every entry in the same order: their outputs are
-// bit-identical (tests/test_ac_gpu.py forces each through the engine option ac_kernel).
+//   ac_assemble_big_kernel / ac_sweep_block_kernel  the opt-in block shape (ac_kernel=block), 1 <= N <= 1024: the
+//                        assembly scatters every structural non-zero straight to its column-major word (no dense
+//                        N x LD stage in LDS, impossible from N ~ 140), and one 256-thread workgroup per instance
+//                        solves on planes in a global scratch (ac_block.hpp).
+//
+// All sweep kernels apply ac_lu.hpp's primitives to every entry in the same order: their outputs are
+// bit-identical (tests/test_ac_gpu.py and tests/test_ac_block_gpu.py force each through the engine option ac_kernel).
 #include <hip/hip_runtime.h>
 
 #include "ac_lu.hpp"
@@ -114,6 +119,59 @@ __global__ void __launch_bounds__(64) ac_assemble_kernel(GenPlan pl, const doubl
     ac_store(Gm, N, LD, out + N * N, out + 2 * N * N + N, lane);
 }
 
+// The assembly without the dense LDS stage: T, Pv and x in LDS (they fit whenever the engine was created), the
+// instance's 2 N^2 + 2 N doubles zero-filled, then every structural non-zero accumulated in gCon order as assemble()
+// does and stored to its column-major word, the right-hand side rows from iPtr / iRow.  One accumulation and one
+// store per entry: the system is bit for bit ac_assemble_kernel's.
+__device__ void ac_scatter(const GenPlan& pl, const double* T, double* mat, double* rhs, int lane)
+{
+    const int N = pl.N, LD = pl.LD;
+    for (int n = lane; n < pl.nnzG; n += 64) {
+        double acc = 0.0;
+        for (int c = pl.gPtr[n]; c < pl.gPtr[n + 1]; ++c) {
+            const int con = pl.gCon[c];
+            const double v = T[con >> 1];
+            acc = (con & 1) ? acc - v : acc + v;
+        }
+        const int pos = pl.gPos[n], i = pos / LD, j = pos - i * LD;
+        mat[(size_t)j * N + i] = acc;
+    }
+    for (int n = lane; n < pl.nnzI; n += 64) {
+        double acc = 0.0;
+        for (int c = pl.iPtr[n]; c < pl.iPtr[n + 1]; ++c) {
+            const int con = pl.iCon[c];
+            const double v = T[con >> 1];
+            acc = (con & 1) ? acc - v : acc + v;
+        }
+        rhs[pl.iRow[n]] = acc;
+    }
+    wave_sync();
+}
+
+__global__ void __launch_bounds__(64) ac_assemble_big_kernel(GenPlan pl, const double* __restrict__ acRe,
+                                                             const double* __restrict__ acIm, const double* __restrict__ params,
+                                                             int B, int b0, const double* __restrict__ xop, double* __restrict__ sys)
+{
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x;
+    const int c = blockIdx.x, b = b0 + c;
+    const int N = pl.N;
+    double* T = lds;
+    double* Pv = T + pl.nTerms;
+    double* x = Pv + pl.P;
+    for (int p = lane; p < pl.P; p += 64) Pv[p] = params[(size_t)p * B + b];
+    for (int i = lane; i < N; i += 64) x[i] = xop[(size_t)i * B + b];
+    const size_t per = (size_t)2 * N * N + (size_t)2 * N;
+    double* out = sys + (size_t)c * per;
+    for (size_t i = lane; i < per; i += 64) out[i] = 0.0;
+    __threadfence_block();
+    wave_sync();
+    ac_terms<false>(pl, Pv, x, acRe, T, lane);
+    ac_scatter(pl, T, out, out + (size_t)2 * N * N, lane);
+    ac_terms<true>(pl, Pv, x, acIm, T, lane);
+    ac_scatter(pl, T, out + (size_t)N * N, out + (size_t)2 * N * N + N, lane);
+}
+
 // output offset of (frequency f, probe p, instance b), complex pairs: 64-bit
 __device__ __forceinline__ size_t ac_out_at(int f, int p, int nProbe, int B, int b)
 {
@@ -155,6 +213,46 @@ __global__ void __launch_bounds__(64) ac_sweep_wave_kernel(int N, const double* 
     }
     if (lane == 0 && flags) status[b] |= flags;
 }
+
+// ---- 256-thread workgroup per system (N <= 1024): the planes in the instance's slice of a global scratch
+__global__ void __launch_bounds__(ACB_THREADS) ac_sweep_block_kernel(int N, const double* __restrict__ sys,
+                                                                     const double* __restrict__ omega, int F,
+                                                                     const int32_t* __restrict__ probe, int nProbe, int B, int b0,
+                                                                     double eps, double* __restrict__ out,
+                                                                     uint32_t* __restrict__ status, double* work)
+{
+    extern __shared__ double lds[];
+    const int tid = threadIdx.x;
+    const int c = blockIdx.x, b = b0 + c;
+    const int LD = acw_ld(N, 1);
+    const AcbLds m = acb_carve(lds, N, 1);
+    double* const Ar = acb_work_at(work, c, N, LD);
+    double* const Ai = Ar + N * LD;
+    const double* Gt = ac_system_at(sys, c, N);
+    const double* Ct = Gt + N * N;
+    const double* Jr = Ct + N * N;
+    const double* Ji = Jr + N;
+    const double eps2 = eps * eps;
+    unsigned flags = 0u;
+
+    for (int f = 0; f < F; ++f) {
+        const double w = omega[f];
+        acb_load<false>(N, LD, Gt, Ct, w, Ar, Ai, tid);
+        for (int i = tid; i < N; i += ACB_THREADS) { Ar[i * LD + N] = Jr[i]; Ai[i * LD + N] = Ji[i]; }
+        acb_sync();
+
+        if (acb_solve(N, 1, LD, Ar, Ai, m.Lr, m.Li, m.rows, m.Xr, m.Xi, eps2, tid)) flags |= CSIM_ST_LU_TINY_PIVOT;
+        for (int p = tid; p < nProbe; p += ACB_THREADS) {
+            const int eq = probe ? probe[p] : p;
+            const size_t at = ac_out_at(f, p, nProbe, B, b);
+            out[at] = m.Xr[eq];
+            out[at + 1] = m.Xi[eq];
+        }
+        __syncthreads();
+    }
+    if (tid == 0 && flags) status[b] |= flags;
+}
+
 // ---- register-resident, 32 lanes per system (N <= NP <= 32): acp_column / acp_back of ac_sweep.hpp, one RHS
 
 template <int NP>
@@ -208,11 +306,20 @@ __global__ void __launch_bounds__(64) ac_sweep_packed_kernel(int N, const double
 } // namespace
 
 size_t acSystemDoubles(int N) { return (size_t)2 * N * N + (size_t)2 * N; }
+size_t acBlockWorkDoubles(int N) { return (size_t)2 * N * (size_t)acw_ld(N, 1); }
 
 hipError_t launchAcAssemble(const GenPlan& pl, const double* dAcRe, const double* dAcIm, const double* dParams, int B,
-                            int b0, int Bc, const double* dXop, double* dSys, hipStream_t stream)
+                            int b0, int Bc, const double* dXop, double* dSys, hipStream_t stream, int which)
 {
     if (Bc <= 0) return hipSuccess;
+    if (which == AC_KERNEL_BLOCK) {
+        const size_t lds = sizeof(double) * ((size_t)pl.nTerms + pl.P + pl.N);
+        if (lds > 160 * 1024) return hipErrorInvalidValue;
+        if (lds > 64 * 1024)
+            (void)hipFuncSetAttribute((const void*)ac_assemble_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(ac_assemble_big_kernel, dim3(Bc), dim3(64), lds, stream, pl, dAcRe, dAcIm, dParams, B, b0, dXop, dSys);
+        return hipGetLastError();
+    }
     const size_t lds = sizeof(double) * ((size_t)pl.nTerms + pl.P + pl.N + (size_t)pl.N * pl.LD);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     if (lds > 64 * 1024)
@@ -222,11 +329,16 @@ hipError_t launchAcAssemble(const GenPlan& pl, const double* dAcRe, const double
 }
 
 hipError_t launchAcSweep(int which, int N, const double* dSys, const double* dOmega, int F, const int32_t* dProbe,
-                         int nProbe, int B, int b0, int Bc, double eps, double* dOut, uint32_t* dStatus, hipStream_t stream)
+                         int nProbe, int B, int b0, int Bc, double eps, double* dOut, uint32_t* dStatus, hipStream_t stream,
+                         double* dWork)
 {
     if (Bc <= 0 || F <= 0) return hipSuccess;
     if (!ac_sweep_covers(which, N)) return hipErrorInvalidValue;
-    if (which == AC_KERNEL_PACKED) {
+    if (which == AC_KERNEL_BLOCK) {
+        if (!dWork) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(ac_sweep_block_kernel, dim3(Bc), dim3(ACB_THREADS), acb_lds_bytes(N, 1), stream, N, dSys, dOmega, F,
+                           dProbe, nProbe, B, b0, eps, dOut, dStatus, dWork);
+    } else if (which == AC_KERNEL_PACKED) {
         acp_dispatch(N, [&](auto np) {
             hipLaunchKernelGGL(ac_sweep_packed_kernel<decltype(np)::value>, dim3((Bc + 1) / 2), dim3(64), 0, stream, N, dSys,
                                dOmega, F, dProbe, nProbe, B, b0, Bc, eps, dOut, dStatus);

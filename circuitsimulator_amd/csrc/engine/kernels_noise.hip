@@ -7,6 +7,9 @@
 //                           (kT4 / R) and MOSFET channel (kT4 2/3 |gg|, mos_eval at x_op as in the G pass).
 //   ac_noise_wave_kernel    one wavefront per instance, N <= 63: A^T in LDS, acw_solve() of ac_sweep.hpp, epilogue.
 //   ac_noise_packed_kernel  N <= 32: 32 lanes per instance, lane r owns row r of A^T, acp_column / acp_back.
+//   ac_noise_block_kernel   opt-in (ac_kernel=block), N <= 1024: a 256-thread workgroup per instance, A^T in a global
+//                           scratch, acb_solve() of ac_block.hpp; the contributions go through LDS, 256 at a time,
+//                           and one thread adds them in ascending order.
 //
 // The transposed load.  Entry (i, j) of A^T is word i * N + j of the column-major G and C.  The wave kernel walks
 // those words in order and scatters them into LDS: consecutive lanes read consecutive addresses, nothing to
@@ -125,6 +128,63 @@ __global__ void __launch_bounds__(64) ac_noise_wave_kernel(NoiseArgs a)
     if (lane == 0 && flags) a.status[b] |= flags;
 }
 
+// ---- 256-thread workgroup per system (N <= 1024)
+__global__ void __launch_bounds__(ACB_THREADS) ac_noise_block_kernel(NoiseArgs a)
+{
+    extern __shared__ double lds[];
+    __shared__ double cbuf[ACB_THREADS];
+    const int tid = threadIdx.x;
+    const int N = a.N, S = a.S;
+    const int c = blockIdx.x, b = a.b0 + c;
+    const int LD = acw_ld(N, 1);
+    const AcbLds m = acb_carve(lds, N, 1);
+    double *const Xr = m.Xr, *const Xi = m.Xi;
+    double* const Ar = acb_work_at(a.work, c, N, LD);
+    double* const Ai = Ar + N * LD;
+    const double* Gt = ac_system_at(a.sys, c, N);
+    const double* Ct = Gt + N * N;
+    const double eps2 = a.eps * a.eps;
+    unsigned flags = 0u;
+
+    for (int f = 0; f < a.F; ++f) {
+        const double w = a.omega[f];
+        acb_load<true>(N, LD, Gt, Ct, w, Ar, Ai, tid);
+        for (int i = tid; i < N; i += ACB_THREADS) {
+            Ar[i * LD + N] = i == a.outP ? 1.0 : (i == a.outM ? -1.0 : 0.0);
+            Ai[i * LD + N] = 0.0;
+        }
+        acb_sync();
+
+        const bool failed = acb_solve(N, 1, LD, Ar, Ai, m.Lr, m.Li, m.rows, Xr, Xi, eps2, tid);
+        if (failed) flags |= CSIM_ST_LU_TINY_PIVOT;
+        if (a.y)
+            for (int p = tid; p < N; p += ACB_THREADS) {
+                const size_t at = (((size_t)f * (size_t)N + (size_t)p) * (size_t)a.B + (size_t)b) * 2;
+                a.y[at] = Xr[p];                             // zeros when the factorisation failed
+                a.y[at + 1] = Xi[p];
+            }
+        double total = 0.0;
+        for (int s0 = 0; s0 < S; s0 += ACB_THREADS) {
+            const int s = s0 + tid;
+            double cv = 0.0;
+            if (s < S) {
+                if (!failed) cv = noise_contrib(noise_transfer(Xr, Xi, a.srcA[s], a.srcB[s]), psd_at(a, s, c));
+                if (a.contrib) a.contrib[((size_t)f * (size_t)S + (size_t)s) * (size_t)a.B + (size_t)b] = cv;
+            }
+            cbuf[tid] = cv;
+            __syncthreads();
+            if (tid == 0) {
+                const int cnt = min(ACB_THREADS, S - s0);
+                for (int t = 0; t < cnt; ++t) total = total + cbuf[t];
+            }
+            __syncthreads();
+        }
+        if (tid == 0) noise_store(a, f, b, failed, total, Xr, Xi);
+        __syncthreads();
+    }
+    if (tid == 0 && flags) a.status[b] |= flags;
+}
+
 // ---- register-resident, 32 lanes per system (N <= NP <= 32)
 template <int NP>
 __global__ void __launch_bounds__(64) ac_noise_packed_kernel(NoiseArgs a)
@@ -220,7 +280,10 @@ hipError_t launchNoiseSweep(int which, const NoiseArgs& a, hipStream_t stream)
     const int N = a.N;
     if (!ac_sweep_covers(which, N)) return hipErrorInvalidValue;
     if (a.outP < 0 || a.outP >= N || a.outM < -1 || a.outM >= N || a.S < 0) return hipErrorInvalidValue;
-    if (which == AC_KERNEL_PACKED) {
+    if (which == AC_KERNEL_BLOCK) {
+        if (!a.work) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(ac_noise_block_kernel, dim3(a.Bc), dim3(ACB_THREADS), acb_lds_bytes(N, 1), stream, a);
+    } else if (which == AC_KERNEL_PACKED) {
         acp_dispatch(N, [&](auto np) {
             hipLaunchKernelGGL(ac_noise_packed_kernel<decltype(np)::value>, dim3((a.Bc + 1) / 2), dim3(64), 0, stream, a);
         });

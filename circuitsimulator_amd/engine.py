@@ -716,9 +716,13 @@ def lu_solve_batch(A, b, device=0):
     return x, flags
 
 
+# the kernel selector of the *_solve_batch entries (include/csim.h); "block" covers AC and noise, n <= 1024
+_AC_KERNELS = {"auto": 0, "wave": 1, "packed": 2, "block": 4}
+
+
 def ac_solve_batch(G, Cm, J, omega, kernel="auto", device=0):
     """Batched complex solve (G + j w C) x = J through the AC sweep kernels (csim_ac_solve_batch).
-    G, Cm [B][n][n] real, J [B][n] complex, omega [F] rad/s; kernel auto | wave | packed.
+    G, Cm [B][n][n] real, J [B][n] complex, omega [F] rad/s; kernel auto | wave | packed | block (n <= 1024).
     -> (x complex128 [B][F][n], flags [B])"""
     G = np.ascontiguousarray(G, dtype=np.float64)
     Cm = np.ascontiguousarray(Cm, dtype=np.float64)
@@ -728,7 +732,7 @@ def ac_solve_batch(G, Cm, J, omega, kernel="auto", device=0):
     x = np.zeros((B, len(omega), n), dtype=np.complex128)
     flags = np.zeros(B, dtype=np.uint32)
     capi.check(capi.lib().csim_ac_solve_batch(device, n, B, G.ctypes.data, Cm.ctypes.data, J.ctypes.data,
-                                              omega.ctypes.data, len(omega), ("auto", "wave", "packed").index(kernel),
+                                              omega.ctypes.data, len(omega), _AC_KERNELS[kernel],
                                               x.ctypes.data, flags.ctypes.data))
     return x, flags
 
@@ -736,7 +740,8 @@ def ac_solve_batch(G, Cm, J, omega, kernel="auto", device=0):
 def noise_solve_batch(G, Cm, out, src_a, src_b, psd, omega, gain_in=None, kernel="auto", device=0, want_y=True):
     """Batched noise solve through the noise kernels (csim_noise_solve_batch): A^T y = d with A = G + j w C.
     G, Cm [B][n][n] real; out = (out_p, out_m), -1 = ground; generators src_a, src_b [S] with psd [B][S];
-    omega [F] rad/s; gain_in None | ("v", k) | ("i", a, b): H = y[k] | y[a] - y[b]; kernel auto | wave | packed.
+    omega [F] rad/s; gain_in None | ("v", k) | ("i", a, b): H = y[k] | y[a] - y[b]; kernel auto | wave | packed | block
+    (n <= 1024).
     -> dict(onoise [B][F], contrib [B][F][S], gain complex [B][F] or None, y complex [B][F][n] or None, flags [B])"""
     G = np.ascontiguousarray(G, dtype=np.float64)
     Cm = np.ascontiguousarray(Cm, dtype=np.float64)
@@ -758,7 +763,7 @@ def noise_solve_batch(G, Cm, out, src_a, src_b, psd, omega, gain_in=None, kernel
     flags = np.zeros(B, dtype=np.uint32)
     capi.check(capi.lib().csim_noise_solve_batch(
         device, n, B, G.ctypes.data, Cm.ctypes.data, int(out[0]), int(out[1]), S, src_a.ctypes.data, src_b.ctypes.data,
-        psd.ctypes.data, kind, in_a, in_b, omega.ctypes.data, F, ("auto", "wave", "packed").index(kernel),
+        psd.ctypes.data, kind, in_a, in_b, omega.ctypes.data, F, _AC_KERNELS[kernel],
         onoise.ctypes.data, contrib.ctypes.data, gain.ctypes.data if gain is not None else None,
         y.ctypes.data if y is not None else None, flags.ctypes.data))
     return dict(onoise=onoise, contrib=contrib, gain=gain, y=y, flags=flags)
@@ -766,7 +771,8 @@ def noise_solve_batch(G, Cm, out, src_a, src_b, psd, omega, gain_in=None, kernel
 
 def sp_solve_batch(G, Cm, J, omega, kernel="auto", device=0, port_eq=None, z0=None, want_s=True):
     """The S-parameter kernels on systems given directly (csim_sp_solve_batch): (G + j w C) X = J with K = 1 .. 4
-    right-hand sides.  G, Cm [B][n][n] real; omega [F] rad/s; kernel auto | wave | packed.
+    right-hand sides.  G, Cm [B][n][n] real; omega [F] rad/s; kernel auto | wave | packed (block is refused:
+    CSIM_ERR_UNSUPPORTED).
     J [B][K][n] complex -> (x complex [B][F][K][n], flags [B]).
     With port_eq [P] and z0 [P] (J is ignored, may be None) the right-hand sides are the unit vectors at port_eq
     -> dict(x [B][F][P][n], y [B][F][P][P], s the same or None, flags [B])."""
@@ -774,7 +780,7 @@ def sp_solve_batch(G, Cm, J, omega, kernel="auto", device=0, port_eq=None, z0=No
     Cm = np.ascontiguousarray(Cm, dtype=np.float64)
     omega = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
     B, n, F = G.shape[0], G.shape[1], len(omega)
-    which = ("auto", "wave", "packed").index(kernel)
+    which = _AC_KERNELS[kernel]
     flags = np.zeros(B, dtype=np.uint32)
     L = capi.lib()
     if port_eq is None:
@@ -802,7 +808,7 @@ def sp_noise_solve_batch(G, Cm, port_eq, z0, src_a, src_b, psd, omega, kernel="a
                          want_x=True):
     """The two-port noise kernels on systems given directly (csim_spnoise_solve_batch): (G + j w C)^T L = unit vectors
     at port_eq.  G, Cm [B][n][n] real; port_eq, z0 [P]; generators src_a, src_b [S] (-1 = ground) with psd [B][S];
-    omega [F] rad/s; kernel auto | wave | packed.  noise_params: None = for two ports; True with any other port count
+    omega [F] rad/s; kernel auto | wave | packed (block is refused: CSIM_ERR_UNSUPPORTED).  noise_params: None = for two ports; True with any other port count
     is a ValueError.
     -> dict(y, cy complex [B][F][P][P], x complex [B][F][P][n] or None, flags [B]) and, for two ports, nf, fmin, rn
        [B][F], yopt complex [B][F]."""
@@ -829,7 +835,7 @@ def sp_noise_solve_batch(G, Cm, port_eq, z0, src_a, src_b, psd, omega, kernel="a
     ptr = lambda a: a.ctypes.data if a is not None else None    # noqa: E731
     capi.check(capi.lib().csim_spnoise_solve_batch(
         device, n, B, P, G.ctypes.data, Cm.ctypes.data, pe.ctypes.data, z.ctypes.data, S, src_a.ctypes.data,
-        src_b.ctypes.data, psd.ctypes.data, omega.ctypes.data, F, ("auto", "wave", "packed").index(kernel), y.ctypes.data,
+        src_b.ctypes.data, psd.ctypes.data, omega.ctypes.data, F, _AC_KERNELS[kernel], y.ctypes.data,
         cy.ctypes.data, ptr(nf), ptr(fmin), ptr(rn), ptr(yopt), ptr(x), flags.ctypes.data))
     r = dict(y=y, cy=cy, x=x, flags=flags)
     if two:

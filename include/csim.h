@@ -202,7 +202,8 @@ int  csim_engine_set_kernel(csim_engine* eng, int32_t which);
  *   near_test_rollback (0)                  test aid: every verified near-threshold decision is treated as a
  *                                           mismatch, so the roll-back path runs (results must not change)
  *   hybrid_sync (CSIM_HYBRID_SYNC, 1)       see "Streams" above
- *   ac_kernel (auto)                        test aid: AC, noise and S-parameter sweep kernel, auto | wave | packed (see csim_ac_batch_dev)
+ *   ac_kernel (auto)                        AC, noise and S-parameter sweep kernel, auto | wave | packed (test aid) | block
+ *                                           (opt-in: AC and noise of up to 1024 unknowns; see csim_ac_batch_dev)
  *   dc_fast (CSIM_DC_FAST, 0)               DC operating points start on the fast generated kernel (FMA
  *                                           contraction, reciprocal pivots; controller decisions within
  *                                           its rounding noise are replayed) instead of the faithful one
@@ -294,7 +295,8 @@ int64_t csim_tran_num_steps(double tstep, double tstop);
  * re^2 + im^2 (strict '>'); a maximum below lu_eps^2 gives the zero vector for that (instance, frequency) and
  * sets CSIM_ST_LU_TINY_PIVOT in the instance's status; the rest of the sweep goes on.  Multiplier
  * a conj(p) (1 / |p|^2), back substitution in ascending column order, no FMA contraction.  Circuits of up to
- * 63 unknowns (CSIM_ERR_UNSUPPORTED beyond); no source with mag != 0: CSIM_ERR_CONFIG.
+ * 63 unknowns, of up to 1024 with the engine option ac_kernel=block (CSIM_ERR_UNSUPPORTED beyond); no source with
+ * mag != 0: CSIM_ERR_CONFIG.
  *
  * Frequency grid (SPICE): DEC fstart 10^(k/n), OCT fstart 2^(k/n), k = 0 .. floor(n log_b(fstop/fstart) + 1e-9);
  * LIN n points from fstart to fstop inclusive (n == 1: fstart).  n <= 0, fstart <= 0 (DEC/OCT) or fstop < fstart:
@@ -309,7 +311,11 @@ int  csim_ac_freqs(int32_t sweep, int32_t n_points, double fstart, double fstop,
  *   d_status [B], OR-ed
  * The engine option ac_kernel (test aid) forces the sweep kernel: "wave" (one wavefront per system, N <= 63) or
  * "packed" (registers, 32 lanes per system, N <= 32); "auto" picks packed for N <= 32.  Both give bit-identical
- * results.                                                                                                      */
+ * results.
+ * ac_kernel=block is opt-in and never picked by "auto": one 256-thread workgroup per system with the matrix in a
+ * device scratch, 1 <= N <= 1024, for AC and noise analysis (csim_ac_*, csim_noise_*); the same arithmetic in the
+ * same order, so bit-identical to the other two where they run.  With it the S-parameter and two-port noise entry
+ * points return CSIM_ERR_UNSUPPORTED, and csim_engine_stat("ac_chunk") counts its scratch.                      */
 int  csim_ac_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int32_t B, const double* d_xop,
                        const double* freqs, int32_t F, const int32_t* probe_eq, int32_t n_probe,
                        double* d_out, uint32_t* d_status, void* stream);
@@ -344,7 +350,7 @@ int  csim_ac_system_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int
  *      the caller.
  *   Failed factorisation  a column maximum below lu_eps^2 at some frequency: onoise, every contrib and the gain are
  *      +0.0 there, CSIM_ST_LU_TINY_PIVOT is OR-ed into the instance's status, the sweep goes on.
- * Circuits of up to 63 unknowns (CSIM_ERR_UNSUPPORTED beyond).  S == 0 is legal: onoise = 0.  temp_k <= 0 or not
+ * Circuits of up to 63 unknowns, 1024 with ac_kernel=block (CSIM_ERR_UNSUPPORTED beyond).  S == 0 is legal: onoise = 0.  temp_k <= 0 or not
  * finite: CSIM_ERR_CONFIG.  No AC source is needed.
  *
  * Enqueues the sweep; never waits for it; frequency lists as csim_ac_batch_dev (same buffers, same discipline).
@@ -462,8 +468,10 @@ int  csim_lu_solve_batch(int32_t device, int32_t n, int32_t B, const double* A,
  * "AC analysis" above (same pivot rule, multiplier, order; lu_eps = 1e-15), without an engine or a netlist.
  * Host pointers.  G, C [B][n][n] row-major; J [B][n] complex (re, im) pairs; omega [F] rad/s, used as given;
  * x [B][F][n] complex pairs (the zero vector where the factorisation fails); flags [B] optional (CSIM_ST_LU_*).
- * kernel: 0 auto (packed for n <= 32), 1 wave (n <= 63), 2 packed (n <= 32); a size beyond the kernel:
- * CSIM_ERR_UNSUPPORTED.  n, B or F == 0: nothing to do.                                                        */
+ * kernel: 0 auto (packed for n <= 32), 1 wave (n <= 63), 2 packed (n <= 32), 4 block (n <= 1024; never picked by
+ * auto; AC and noise only: csim_sp_solve_batch and csim_spnoise_solve_batch answer it with CSIM_ERR_UNSUPPORTED);
+ * any other value, 3 included: CSIM_ERR_ARG; a size beyond the kernel: CSIM_ERR_UNSUPPORTED.  n, B or F == 0:
+ * nothing to do.                                                                                                */
 int  csim_ac_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* C,
                          const double* J, const double* omega, int32_t F, int32_t kernel,
                          double* x, uint32_t* flags);

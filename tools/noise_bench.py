@@ -9,6 +9,9 @@ from a profiler run of its own:
 
     python tools/noise_bench.py --netlist tests/golden/dbmixer.sp --ac-source "Vrf1+ 112 212 SIN" \\
         --card ".NOISE V(102,103) Vrf1+ DEC 10 1k 10g" --B 4096
+
+The opt-in block kernel (ac_kernel=block, up to 1024 unknowns) on the generated mid-size circuits (their own card):
+    python tools/noise_bench.py --circuit amp65 --kernel block --B 4096
 """
 import argparse
 import json
@@ -20,6 +23,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from bench_circuits import CIRCUITS  # noqa: E402
 
 
 def main():
@@ -32,17 +37,26 @@ def main():
     ap.add_argument("--B", type=int, default=4096)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--contrib", action="store_true", help="also write the per-generator contributions")
+    ap.add_argument("--circuit", choices=sorted(CIRCUITS), help="a generated netlist (with its card) instead of --netlist")
+    ap.add_argument("--kernel", choices=["block"], help="time this sweep kernel instead of wave / packed")
+    ap.add_argument("--points", type=int, default=0, help="with --circuit: points per decade of its card (0 = 10)")
     a = ap.parse_args()
 
     import torch
     from circuitsimulator_amd import Engine, Netlist
 
-    text = open(a.netlist).read()
-    if a.ac_source:
-        assert a.ac_source in text, "source line not found: %s" % a.ac_source
-        text = text.replace(a.ac_source, a.ac_source.replace(" SIN", " AC 1 SIN"), 1)
-    if a.card:
-        text = text.rstrip("\n") + "\n" + a.card + "\n"
+    if a.circuit:
+        text = CIRCUITS[a.circuit]()
+        if a.points:
+            text = text.replace(" dec 10 ", " dec %d " % a.points)
+        a.card = [ln for ln in text.splitlines() if ln.startswith(".noise")][0]
+    else:
+        text = open(a.netlist).read()
+        if a.ac_source:
+            assert a.ac_source in text, "source line not found: %s" % a.ac_source
+            text = text.replace(a.ac_source, a.ac_source.replace(" SIN", " AC 1 SIN"), 1)
+        if a.card:
+            text = text.rstrip("\n") + "\n" + a.card + "\n"
     nl = Netlist.from_text(text)
     assert nl.noise is not None, "no .NOISE card"
     eng = Engine(nl, 0)
@@ -66,10 +80,10 @@ def main():
             ms.append(e0.elapsed_time(e1))
         return float(np.median(ms)), ms
 
-    res = {"netlist": os.path.basename(a.netlist), "card": a.card, "B": B, "N": N, "F": F, "S": S, "systems": B * F,
+    res = {"netlist": a.circuit or os.path.basename(a.netlist), "card": a.card, "B": B, "N": N, "F": F, "S": S, "systems": B * F,
            "contrib": bool(a.contrib)}
     outs = {}
-    kernels = ["wave", "packed"] if N <= 32 else ["wave"]
+    kernels = [a.kernel] if a.kernel else (["wave", "packed"] if N <= 32 else ["wave"])
     for k in kernels:
         eng.set_option("ac_kernel", k)
 
