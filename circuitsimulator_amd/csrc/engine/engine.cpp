@@ -14,11 +14,9 @@
 #include <utility>
 #include <vector>
 
-#include "ac_noise.hpp"
-#include "ac_port_noise.hpp"
-#include "ac_port.hpp"
 #include "codegen.hpp"
 #include "csim.h"
+#include "engine_host.hpp"
 #include "engine_internal.hpp"
 #include "jit.hpp"
 #include "kernels.hpp"
@@ -26,15 +24,6 @@
 #include "plan.hpp"
 
 using csim::setError;
-
-#define HIPCHK(call)                                                                   \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            setError(std::string(#call) + ": " + hipGetErrorString(e_));               \
-            return CSIM_ERR_HIP;                                                       \
-        }                                                                              \
-    } while (0)
 
 namespace {
 
@@ -80,14 +69,6 @@ int fillGenPlan(csim_engine* eng, const csim::GatherPlan& g, csim::GenPlan& out)
     out.k = ir->k;
     return CSIM_OK;
 }
-
-// scratch allocation that frees itself
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8); }
-    template <class T> T* as() { return static_cast<T*>(p); }
-};
 
 int ensureProbes(csim_engine* eng, const int32_t* probe_eq, int n_probe, const int32_t** dOut)
 {
@@ -228,6 +209,27 @@ void loadScheduledKernel(csim_engine* eng)
 }
 
 } // namespace
+
+int csim::stageParams(csim_engine* eng, const double* params, int B, DevBuf& dParams)
+{
+    const int P = eng->cir.ir.n_params;
+    HIPCHK(dParams.alloc(sizeof(double) * (size_t)P * (size_t)B));
+    if (params) {
+        DevBuf tmp;
+        HIPCHK(tmp.alloc(sizeof(double) * (size_t)P * (size_t)B));
+        HIPCHK(hipMemcpy(tmp.p, params, sizeof(double) * (size_t)P * (size_t)B, hipMemcpyHostToDevice));
+        HIPCHK(csim::launchTranspose(tmp.as<double>(), dParams.as<double>(), B, P, nullptr));   // [B][P] -> [P][B]
+        HIPCHK(hipDeviceSynchronize());
+    } else {
+        std::vector<double> rep((size_t)P * (size_t)B);
+        for (int p = 0; p < P; ++p)
+            for (int b = 0; b < B; ++b) rep[(size_t)p * B + b] = eng->cir.nominal[(size_t)p];
+        HIPCHK(hipMemcpy(dParams.p, rep.data(), sizeof(double) * rep.size(), hipMemcpyHostToDevice));
+    }
+    return CSIM_OK;
+}
+
+using csim::stageParams;
 
 extern "C" {
 
@@ -432,13 +434,11 @@ int csim_engine_set_option(csim_engine* eng, const char* key, const char* value)
     return CSIM_OK;
 }
 
-static size_t acChunkCap(const csim_engine* eng);
-
 int64_t csim_engine_stat(const csim_engine* eng, const char* key)
 {
     if (!eng || !key) return -1;
     const std::string k(key);
-    if (k == "ac_chunk") return (int64_t)acChunkCap(eng);
+    if (k == "ac_chunk") return (int64_t)csim::acChunkCap(eng);
     if (k == "near_verified") return eng->nearVerified;
     if (k == "near_rolled_back") return eng->nearRolledBack;
     return -1;
@@ -782,25 +782,6 @@ int64_t csim_tran_num_rows(double tstep, double tstop, double tstart, int32_t ou
 
 // ---- host-pointer forms ---------------------------------------------------
 
-static int stageParams(csim_engine* eng, const double* params, int B, DevBuf& dParams)
-{
-    const int P = eng->cir.ir.n_params;
-    HIPCHK(dParams.alloc(sizeof(double) * (size_t)P * (size_t)B));
-    if (params) {
-        DevBuf tmp;
-        HIPCHK(tmp.alloc(sizeof(double) * (size_t)P * (size_t)B));
-        HIPCHK(hipMemcpy(tmp.p, params, sizeof(double) * (size_t)P * (size_t)B, hipMemcpyHostToDevice));
-        HIPCHK(csim::launchTranspose(tmp.as<double>(), dParams.as<double>(), B, P, nullptr));   // [B][P] -> [P][B]
-        HIPCHK(hipDeviceSynchronize());
-    } else {
-        std::vector<double> rep((size_t)P * (size_t)B);
-        for (int p = 0; p < P; ++p)
-            for (int b = 0; b < B; ++b) rep[(size_t)p * B + b] = eng->cir.nominal[(size_t)p];
-        HIPCHK(hipMemcpy(dParams.p, rep.data(), sizeof(double) * rep.size(), hipMemcpyHostToDevice));
-    }
-    return CSIM_OK;
-}
-
 int csim_dc_batch(csim_engine* eng, const double* params, int32_t B, double* x_out,
                   int32_t* nr_iters, uint32_t* status)
 {
@@ -822,636 +803,6 @@ int csim_dc_batch(csim_engine* eng, const double* params, int32_t B, double* x_o
     if (x_out)    HIPCHK(hipMemcpy(x_out, dXt.p, sizeof(double) * (size_t)N * B, hipMemcpyDeviceToHost));
     if (nr_iters) HIPCHK(hipMemcpy(nr_iters, dIt.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost));
     if (status)   HIPCHK(hipMemcpy(status, dSt.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    return CSIM_OK;
-}
-
-// ---- AC small-signal analysis ----------------------------------------------
-
-// the system of every instance lives in device scratch between assembly and sweep; instances are processed in
-// chunks that keep it below 256 MiB; under ac_kernel=block the planes of the solve live there too, and a chunk may
-// shrink to 32 instances (the planes of a 1024-unknown system are 16 MiB)
-static bool acBlock(const csim_engine* eng) { return eng->cfg.acKernel == csim::AC_KERNEL_BLOCK; }
-
-static size_t acChunkCap(const csim_engine* eng)
-{
-    size_t per = sizeof(double) * csim::acSystemDoubles(eng->plan.N);
-    if (acBlock(eng)) per += sizeof(double) * csim::acBlockWorkDoubles(eng->plan.N);
-    return std::max<size_t>(acBlock(eng) ? 32 : 256, ((size_t)256 << 20) / per);
-}
-
-static int acChunk(const csim_engine* eng, int B)
-{
-    return (int)std::min<size_t>((size_t)B, acChunkCap(eng));
-}
-
-// the sizes the frequency-domain analyses cover: 63 unknowns, or with ac_kernel=block (AC and noise) 1024
-static bool acSizeRefused(const csim_engine* eng)
-{
-    return eng->plan.N > (acBlock(eng) ? 1024 : 63);
-}
-
-// the block kernel carries one right-hand side: the port analyses have none for it yet
-static int acBlockRefused(const csim_engine* eng, const char* what)
-{
-    if (!acBlock(eng)) return CSIM_OK;
-    setError(std::string(what) + ": ac_kernel=block covers AC and noise analysis only");
-    return CSIM_ERR_UNSUPPORTED;
-}
-
-static int acCheck(const csim_engine* eng)
-{
-    if (acSizeRefused(eng)) { setError("AC analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
-    if (!eng->acAnySource) { setError("AC analysis: no source carries an AC magnitude (V/I ... AC mag [phase])"); return CSIM_ERR_CONFIG; }
-    return CSIM_OK;
-}
-
-// A new frequency or probe list for the sweeps: into a slot no enqueued sweep still reads (never the current one,
-// which the previous call's kernels may be using), with a synchronous copy -- complete before the caller's next
-// launch, whatever its stream.  The ring grows only while more than its size of distinct lists are in flight;
-// at AC_MAX_SLOTS the oldest reader is waited for (that event alone, not the device).
-static constexpr size_t AC_MAX_SLOTS = 8;
-static int acUpload(std::vector<csim_engine::AcList>& ring, int& cur, const void* src, size_t bytes)
-{
-    int slot = -1;
-    for (size_t i = 0; i < ring.size() && slot < 0; ++i) {
-        if ((int)i == cur) continue;
-        const hipError_t q = hipEventQuery(ring[i].done);
-        if (q == hipSuccess) slot = (int)i;
-        else if (q != hipErrorNotReady) HIPCHK(q);
-    }
-    (void)hipGetLastError();                     // "not ready" is an answer here, not an error for the next launch check
-    if (slot < 0 && ring.size() < AC_MAX_SLOTS) {
-        ring.emplace_back();
-        slot = (int)ring.size() - 1;
-        HIPCHK(hipEventCreateWithFlags(&ring[(size_t)slot].done, hipEventDisableTiming));
-    }
-    if (slot < 0) {
-        slot = (cur + 1) % (int)ring.size();
-        HIPCHK(hipEventSynchronize(ring[(size_t)slot].done));
-    }
-    csim_engine::AcList& s = ring[(size_t)slot];
-    if (s.cap < bytes) {
-        if (s.d) HIPCHK(hipFree(s.d));
-        s.d = nullptr;
-        s.cap = 0;
-        HIPCHK(hipMalloc(&s.d, bytes));
-        s.cap = bytes;
-    }
-    HIPCHK(hipMemcpy(s.d, src, bytes, hipMemcpyHostToDevice));
-    cur = slot;
-    return CSIM_OK;
-}
-
-// w = 2 pi f of a sweep's frequency list on the device: uploaded when the list changes, cached otherwise
-static int acOmega(csim_engine* eng, const double* freqs, int F, const double** dOmega)
-{
-    std::vector<double> omega((size_t)F);
-    for (int f = 0; f < F; ++f) omega[(size_t)f] = 2.0 * eng->cir.ir.k.pi * freqs[f];
-    if (eng->acOmegaCur < 0 || omega != eng->acOmegaCache) {
-        eng->acOmegaCache.clear();
-        if (const int rc = acUpload(eng->acOmegaSlots, eng->acOmegaCur, omega.data(), sizeof(double) * (size_t)F)) return rc;
-        eng->acOmegaCache = omega;
-    }
-    *dOmega = static_cast<const double*>(eng->acOmegaSlots[(size_t)eng->acOmegaCur].d);
-    return CSIM_OK;
-}
-
-// the per-chunk system scratch, grown to `chunk` instances
-static int acSysScratch(csim_engine* eng, int chunk)
-{
-    if (eng->acSysCap >= chunk) return CSIM_OK;
-    if (eng->dAcSys) HIPCHK(hipFree(eng->dAcSys));
-    eng->dAcSys = nullptr;
-    eng->acSysCap = 0;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&eng->dAcSys), sizeof(double) * csim::acSystemDoubles(eng->plan.N) * (size_t)chunk));
-    eng->acSysCap = chunk;
-    return CSIM_OK;
-}
-
-// the block kernel's planes, grown to `chunk` instances (nothing under the other kernels)
-static int acWorkScratch(csim_engine* eng, int chunk)
-{
-    if (!acBlock(eng) || eng->acWorkCap >= chunk) return CSIM_OK;
-    if (eng->dAcWork) HIPCHK(hipFree(eng->dAcWork));
-    eng->dAcWork = nullptr;
-    eng->acWorkCap = 0;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&eng->dAcWork), sizeof(double) * csim::acBlockWorkDoubles(eng->plan.N) * (size_t)chunk));
-    eng->acWorkCap = chunk;
-    return CSIM_OK;
-}
-
-int csim_ac_system_dev(csim_engine* eng, const double* d_params, int32_t B, const double* d_xop, double* d_sys, void* stream)
-{
-    if (!eng || B < 0 || (B > 0 && (!d_params || !d_xop || !d_sys))) { setError("csim_ac_system_dev: bad argument"); return CSIM_ERR_ARG; }
-    if (acSizeRefused(eng)) { setError("AC analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
-    if (B == 0) return CSIM_OK;
-    HIPCHK(hipSetDevice(eng->device));
-    HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, 0, B, d_xop, d_sys,
-                                  static_cast<hipStream_t>(stream), eng->cfg.acKernel));
-    return CSIM_OK;
-}
-
-int csim_ac_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const double* d_xop, const double* freqs,
-                      int32_t F, const int32_t* probe_eq, int32_t n_probe, double* d_out, uint32_t* d_status, void* stream)
-{
-    if (!eng || B < 0 || F < 0 || (B > 0 && F > 0 && (!d_params || !d_xop || !freqs || !d_out || !d_status))) {
-        setError("csim_ac_batch_dev: bad argument");
-        return CSIM_ERR_ARG;
-    }
-    if (const int rc = acCheck(eng)) return rc;
-    const int N = eng->plan.N;
-    const int nProbe = probe_eq ? n_probe : N;
-    if (probe_eq) {
-        if (n_probe <= 0) { setError("csim_ac_batch_dev: n_probe must be positive"); return CSIM_ERR_ARG; }
-        for (int i = 0; i < n_probe; ++i)
-            if (probe_eq[i] < 0 || probe_eq[i] >= N) { setError("probe equation index out of range"); return CSIM_ERR_ARG; }
-    }
-    int which = eng->cfg.acKernel;
-    if (which == csim::AC_KERNEL_AUTO) which = N <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;   // block: as it is
-    if (which == csim::AC_KERNEL_PACKED && N > 32) { setError("ac_kernel=packed covers N <= 32"); return CSIM_ERR_UNSUPPORTED; }
-    if (B == 0 || F == 0) return CSIM_OK;
-    HIPCHK(hipSetDevice(eng->device));
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-
-    // angular frequencies and the probe list: uploaded when they change, cached otherwise
-    const double* dOmega = nullptr;
-    if (const int rc = acOmega(eng, freqs, F, &dOmega)) return rc;
-    const int32_t* dProbe = nullptr;
-    if (probe_eq) {
-        std::vector<int32_t> want(probe_eq, probe_eq + n_probe);
-        if (eng->acProbeCur < 0 || want != eng->acProbeCache) {
-            eng->acProbeCache.clear();
-            if (const int rc = acUpload(eng->acProbeSlots, eng->acProbeCur, want.data(), sizeof(int32_t) * want.size())) return rc;
-            eng->acProbeCache = want;
-        }
-        dProbe = static_cast<const int32_t*>(eng->acProbeSlots[(size_t)eng->acProbeCur].d);
-    }
-    const int chunk = acChunk(eng, B);
-    if (const int rc = acSysScratch(eng, chunk)) return rc;
-    if (const int rc = acWorkScratch(eng, chunk)) return rc;
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-        const int Bc = std::min(chunk, B - b0);
-        HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, b0, Bc, d_xop, eng->dAcSys, hs, which));
-        HIPCHK(csim::launchAcSweep(which, N, eng->dAcSys, dOmega, F, dProbe, nProbe, B, b0, Bc, eng->cir.ir.k.lu_eps,
-                                   d_out, d_status, hs, eng->dAcWork));
-    }
-    HIPCHK(hipEventRecord(eng->acOmegaSlots[(size_t)eng->acOmegaCur].done, hs));
-    if (dProbe) HIPCHK(hipEventRecord(eng->acProbeSlots[(size_t)eng->acProbeCur].done, hs));
-    return CSIM_OK;
-}
-
-// [F][X][B] on the device, W doubles per entry (1: real, 2: complex) -> [B][F][X] on the host
-static int toHost(const double* dSrc, int F, int X, int B, int W, double* dst)
-{
-    const size_t n = (size_t)W * F * X * B;
-    if (n == 0) return CSIM_OK;
-    std::vector<double> h(n);
-    HIPCHK(hipMemcpy(h.data(), dSrc, sizeof(double) * n, hipMemcpyDeviceToHost));
-    for (int f = 0; f < F; ++f)
-        for (int t = 0; t < X; ++t)
-            for (int b = 0; b < B; ++b) {
-                const size_t src = (((size_t)f * X + t) * B + b) * W;
-                const size_t at = (((size_t)b * F + f) * X + t) * W;
-                for (int k = 0; k < W; ++k) dst[at + k] = h[src + k];
-            }
-    return CSIM_OK;
-}
-
-int csim_ac_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F,
-                  const int32_t* probe_eq, int32_t n_probe, double* out, uint32_t* status)
-{
-    if (!eng || B < 0) { setError("csim_ac_batch: bad argument"); return CSIM_ERR_ARG; }
-    if (const int rc = acCheck(eng)) return rc;
-    std::vector<double> card;
-    if (!freqs) {
-        if (!eng->acEnabled) { setError("csim_ac_batch: no frequencies given and the netlist has no .AC card"); return CSIM_ERR_CONFIG; }
-        const int64_t n = csim_ac_num_freqs(eng->acSweep, eng->acPoints, eng->acFstart, eng->acFstop);
-        if (n < 0) return static_cast<int>(n);
-        card.resize((size_t)n);
-        if (const int rc = csim_ac_freqs(eng->acSweep, eng->acPoints, eng->acFstart, eng->acFstop, card.data())) return rc;
-        freqs = card.data();
-        F = static_cast<int32_t>(n);
-    }
-    if (F < 0 || (B > 0 && F > 0 && !out)) { setError("csim_ac_batch: bad argument"); return CSIM_ERR_ARG; }
-    if (B == 0) return CSIM_OK;
-    HIPCHK(hipSetDevice(eng->device));
-    const int N = eng->plan.N;
-    const int nProbe = probe_eq ? n_probe : N;
-    DevBuf dParams, dX, dIt, dSt, dOut;
-    int rc = stageParams(eng, params, B, dParams);
-    if (rc) return rc;
-    const size_t outDoubles = (size_t)2 * F * (size_t)std::max(nProbe, 0) * B;
-    HIPCHK(dX.alloc(sizeof(double) * (size_t)N * B));
-    HIPCHK(dIt.alloc(sizeof(int32_t) * (size_t)B));
-    HIPCHK(dSt.alloc(sizeof(uint32_t) * (size_t)B));
-    HIPCHK(dOut.alloc(sizeof(double) * outDoubles));
-    rc = csim_dc_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), dIt.as<int32_t>(), dSt.as<uint32_t>(), nullptr);
-    if (rc) return rc;
-    rc = csim_ac_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), freqs, F, probe_eq, n_probe, dOut.as<double>(),
-                           dSt.as<uint32_t>(), nullptr);
-    if (rc) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    if (status) HIPCHK(hipMemcpy(status, dSt.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    return toHost(dOut.as<double>(), F, std::max(nProbe, 0), B, 2, out);
-}
-
-// ---- noise analysis ---------------------------------------------------------
-
-// the netlist's .NOISE card as a frequency list
-static int noiseCardFreqs(const csim_engine* eng, std::vector<double>& card)
-{
-    if (!eng->noiseEnabled) { setError("noise analysis: no frequencies given and the netlist has no .NOISE card"); return CSIM_ERR_CONFIG; }
-    const int64_t n = csim_ac_num_freqs(eng->noiseSweep, eng->noisePoints, eng->noiseFstart, eng->noiseFstop);
-    if (n < 0) return static_cast<int>(n);
-    card.resize((size_t)n);
-    return csim_ac_freqs(eng->noiseSweep, eng->noisePoints, eng->noiseFstart, eng->noiseFstop, card.data());
-}
-
-// output pair, input source and temperature of a noise call -> the kernels' numbers
-static int noiseSetup(const csim_engine* eng, int out_p, int out_m, int src_elem, double temp_k, csim::NoiseArgs& a, double& kT4)
-{
-    const int N = eng->plan.N;
-    if (acSizeRefused(eng)) { setError("noise analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
-    if (out_p < 0 || out_p >= N || out_m < -1 || out_m >= N || out_p == out_m) {
-        setError("noise analysis: the output needs two different equations, out_p >= 0 (out_m = -1: ground)");
-        return CSIM_ERR_ARG;
-    }
-    a.inKind = csim::NOISE_IN_NONE;
-    a.inA = a.inB = -1;
-    if (src_elem >= 0) {
-        const csim::CircuitIR& c = eng->cir;
-        if (src_elem >= c.ir.n_elems) { setError("noise analysis: bad input source element"); return CSIM_ERR_ARG; }
-        const int kind = c.kind[(size_t)src_elem];
-        if (kind == CSIM_V) {
-            a.inKind = csim::NOISE_IN_V;
-            a.inA = c.branchEq[(size_t)src_elem];
-            if (a.inA < 0 || a.inA >= N) { setError("noise analysis: the input source has no branch equation"); return CSIM_ERR_ARG; }
-        } else if (kind == CSIM_I) {                         // stampAC: J(p) -= I, J(m) += I (element.cpp:68-81)
-            a.inKind = csim::NOISE_IN_I;
-            a.inA = c.eq[4 * (size_t)src_elem + 1];
-            a.inB = c.eq[4 * (size_t)src_elem + 0];
-        } else { setError("noise analysis: the input source must be a V or I element"); return CSIM_ERR_ARG; }
-    }
-    if (!(temp_k > 0.0) || !std::isfinite(temp_k)) { setError("noise analysis: the temperature must be positive and finite (kelvin)"); return CSIM_ERR_CONFIG; }
-    kT4 = 4.0 * 1.380649e-23 * temp_k;
-    a.N = N;
-    a.outP = out_p;
-    a.outM = out_m;
-    a.S = eng->nNoiseSrc;
-    a.srcA = eng->dNoiseA;
-    a.srcB = eng->dNoiseB;
-    a.eps = eng->cir.ir.k.lu_eps;
-    return CSIM_OK;
-}
-
-int csim_noise_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const double* d_xop, const double* freqs,
-                         int32_t F, int32_t out_p_eq, int32_t out_m_eq, int32_t src_elem, double temp_k, double* d_onoise,
-                         double* d_gain, double* d_contrib, double* d_psd, uint32_t* d_status, void* stream)
-{
-    if (!eng || B < 0 || F < 0 || (B > 0 && F > 0 && (!d_params || !d_xop || !freqs || !d_onoise || !d_status))) {
-        setError("csim_noise_batch_dev: bad argument");
-        return CSIM_ERR_ARG;
-    }
-    csim::NoiseArgs a{};
-    double kT4 = 0.0;
-    if (const int rc = noiseSetup(eng, out_p_eq, out_m_eq, src_elem, temp_k, a, kT4)) return rc;
-    const int N = a.N, S = a.S;
-    int which = eng->cfg.acKernel;
-    if (which == csim::AC_KERNEL_AUTO) which = N <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;   // block: as it is
-    if (which == csim::AC_KERNEL_PACKED && N > 32) { setError("ac_kernel=packed covers N <= 32"); return CSIM_ERR_UNSUPPORTED; }
-    if (B == 0 || F == 0) return CSIM_OK;
-    HIPCHK(hipSetDevice(eng->device));
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-
-    const double* dOmega = nullptr;
-    if (const int rc = acOmega(eng, freqs, F, &dOmega)) return rc;
-    const int chunk = acChunk(eng, B);
-    if (const int rc = acSysScratch(eng, chunk)) return rc;
-    if (const int rc = acWorkScratch(eng, chunk)) return rc;
-    if (!d_psd && eng->noisePsdCap < (size_t)S * (size_t)chunk) {
-        if (eng->dNoisePsd) HIPCHK(hipFree(eng->dNoisePsd));
-        eng->dNoisePsd = nullptr;
-        eng->noisePsdCap = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&eng->dNoisePsd), sizeof(double) * (size_t)S * (size_t)chunk));
-        eng->noisePsdCap = (size_t)S * (size_t)chunk;
-    }
-    a.F = F;
-    a.B = B;
-    a.sys = eng->dAcSys;
-    a.omega = dOmega;
-    a.onoise = d_onoise;
-    a.gain = d_gain;
-    a.contrib = d_contrib;
-    a.y = nullptr;
-    a.status = d_status;
-    a.work = eng->dAcWork;
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-        const int Bc = std::min(chunk, B - b0);
-        a.b0 = b0;
-        a.Bc = Bc;
-        a.psd = d_psd ? d_psd : eng->dNoisePsd;
-        a.psdStride = d_psd ? (size_t)B : (size_t)chunk;
-        a.psdOff = d_psd ? (size_t)b0 : 0;
-        HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, b0, Bc, d_xop, eng->dAcSys, hs, which));
-        HIPCHK(csim::launchNoisePsd(eng->gpTran, eng->dNoiseElem, S, d_params, B, b0, Bc, d_xop, kT4,
-                                    d_psd ? d_psd : eng->dNoisePsd, a.psdStride, a.psdOff, hs));
-        HIPCHK(csim::launchNoiseSweep(which, a, hs));
-    }
-    HIPCHK(hipEventRecord(eng->acOmegaSlots[(size_t)eng->acOmegaCur].done, hs));
-    return CSIM_OK;
-}
-
-int csim_noise_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F, int32_t out_p_eq,
-                     int32_t out_m_eq, int32_t src_elem, double temp_k, double* onoise, double* gain, double* contrib,
-                     double* psd, uint32_t* status)
-{
-    if (!eng || B < 0) { setError("csim_noise_batch: bad argument"); return CSIM_ERR_ARG; }
-    if (acSizeRefused(eng)) { setError("noise analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
-    std::vector<double> card;
-    if (!freqs) {
-        if (const int rc = noiseCardFreqs(eng, card)) return rc;
-        freqs = card.data();
-        F = static_cast<int32_t>(card.size());
-    }
-    if (out_p_eq == -2) {
-        if (!eng->noiseEnabled) { setError("csim_noise_batch: no output given and the netlist has no .NOISE card"); return CSIM_ERR_CONFIG; }
-        out_p_eq = eng->noiseOutP;
-        out_m_eq = eng->noiseOutM;
-        src_elem = eng->noiseSrcElem;
-    }
-    if (F < 0 || (B > 0 && F > 0 && !onoise)) { setError("csim_noise_batch: bad argument"); return CSIM_ERR_ARG; }
-    {
-        csim::NoiseArgs probe{};
-        double kT4 = 0.0;
-        if (const int rc = noiseSetup(eng, out_p_eq, out_m_eq, src_elem, temp_k, probe, kT4)) return rc;
-    }
-    if (B == 0) return CSIM_OK;
-    HIPCHK(hipSetDevice(eng->device));
-    const int N = eng->plan.N, S = eng->nNoiseSrc;
-    const bool wantGain = gain && src_elem >= 0;
-    DevBuf dParams, dX, dIt, dSt, dOn, dGain, dCon, dPsd;
-    int rc = stageParams(eng, params, B, dParams);
-    if (rc) return rc;
-    const size_t FB = (size_t)F * (size_t)B;
-    HIPCHK(dX.alloc(sizeof(double) * (size_t)N * B));
-    HIPCHK(dIt.alloc(sizeof(int32_t) * (size_t)B));
-    HIPCHK(dSt.alloc(sizeof(uint32_t) * (size_t)B));
-    HIPCHK(dOn.alloc(sizeof(double) * FB));
-    if (wantGain) HIPCHK(dGain.alloc(sizeof(double) * 2 * FB));
-    if (contrib) HIPCHK(dCon.alloc(sizeof(double) * FB * (size_t)S));
-    if (psd) HIPCHK(dPsd.alloc(sizeof(double) * (size_t)S * (size_t)B));
-    rc = csim_dc_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), dIt.as<int32_t>(), dSt.as<uint32_t>(), nullptr);
-    if (rc) return rc;
-    rc = csim_noise_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), freqs, F, out_p_eq, out_m_eq, src_elem, temp_k,
-                              dOn.as<double>(), wantGain ? dGain.as<double>() : nullptr, contrib ? dCon.as<double>() : nullptr,
-                              psd ? dPsd.as<double>() : nullptr, dSt.as<uint32_t>(), nullptr);
-    if (rc) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    if (status) HIPCHK(hipMemcpy(status, dSt.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    if ((rc = toHost(dOn.as<double>(), F, 1, B, 1, onoise))) return rc;
-    if (wantGain && (rc = toHost(dGain.as<double>(), F, 1, B, 2, gain))) return rc;
-    if (contrib && (rc = toHost(dCon.as<double>(), F, S, B, 1, contrib))) return rc;
-    if (psd && F) return toHost(dPsd.as<double>(), 1, S, B, 1, psd);           // [S][B] -> [B][S]
-    return CSIM_OK;
-}
-
-// ---- S-parameter analysis ---------------------------------------------------
-
-// the engine's ports -> the kernels' numbers (include/csim.h "S-parameter analysis")
-static int spSetup(const csim_engine* eng, csim::SpArgs& a)
-{
-    const int N = eng->plan.N;
-    if (const int rc = acBlockRefused(eng, "S-parameter and two-port noise analysis")) return rc;
-    if (!eng->spPortError.empty()) { setError(eng->spPortError); return CSIM_ERR_CONFIG; }
-    const int P = (int)eng->spPortEq.size();
-    if (P == 0) { setError("S-parameter analysis: the netlist declares no port (V ... PORTNUM k [Z0 r])"); return CSIM_ERR_CONFIG; }
-    if (N > 63) { setError("S-parameter analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
-    a.N = N;
-    a.K = a.P = P;
-    for (int i = 0; i < P; ++i) {
-        a.portEq[i] = eng->spPortEq[(size_t)i];
-        a.sz[i] = std::sqrt(eng->spZ0[(size_t)i]);
-        if (a.portEq[i] < 0 || a.portEq[i] >= N) { setError("S-parameter analysis: a port has no branch equation"); return CSIM_ERR_ARG; }
-    }
-    a.eps = eng->cir.ir.k.lu_eps;
-    return CSIM_OK;
-}
-
-int csim_sp_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const double* d_xop, const double* freqs,
-                      int32_t F, double* d_y, double* d_s, uint32_t* d_status, void* stream)
-{
-    if (!eng || B < 0 || F < 0) { setError("csim_sp_batch_dev: bad argument"); return CSIM_ERR_ARG; }
-    csim::SpArgs a{};
-    if (const int rc = spSetup(eng, a)) return rc;          // no port: CSIM_ERR_CONFIG, whatever the buffers
-    if (B > 0 && F > 0 && (!d_params || !d_xop || !freqs || !d_y || !d_status)) {
-        setError("csim_sp_batch_dev: bad argument");
-        return CSIM_ERR_ARG;
-    }
-    const int N = a.N;
-    int which = eng->cfg.acKernel;
-    if (which == csim::AC_KERNEL_AUTO) which = N <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;   // block: as it is
-    if (which == csim::AC_KERNEL_PACKED && N > 32) { setError("ac_kernel=packed covers N <= 32"); return CSIM_ERR_UNSUPPORTED; }
-    if (B == 0 || F == 0) return CSIM_OK;
-    HIPCHK(hipSetDevice(eng->device));
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-
-    const double* dOmega = nullptr;
-    if (const int rc = acOmega(eng, freqs, F, &dOmega)) return rc;
-    const int chunk = acChunk(eng, B);
-    if (const int rc = acSysScratch(eng, chunk)) return rc;
-    a.F = F;
-    a.B = B;
-    a.sys = eng->dAcSys;
-    a.omega = dOmega;
-    a.y = d_y;
-    a.s = d_s;
-    a.status = d_status;
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-        a.b0 = b0;
-        a.Bc = std::min(chunk, B - b0);
-        HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, b0, a.Bc, d_xop, eng->dAcSys, hs));
-        HIPCHK(csim::launchSpSweep(which, a, hs));
-    }
-    HIPCHK(hipEventRecord(eng->acOmegaSlots[(size_t)eng->acOmegaCur].done, hs));
-    return CSIM_OK;
-}
-
-int csim_sp_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F, double* y, double* s,
-                  uint32_t* status)
-{
-    if (!eng || B < 0) { setError("csim_sp_batch: bad argument"); return CSIM_ERR_ARG; }
-    {
-        csim::SpArgs probe{};
-        if (const int rc = spSetup(eng, probe)) return rc;
-    }
-    std::vector<double> card;
-    if (!freqs) {
-        if (!eng->spEnabled) { setError("csim_sp_batch: no frequencies given and the netlist has no .SP card"); return CSIM_ERR_CONFIG; }
-        const int64_t n = csim_ac_num_freqs(eng->spSweep, eng->spPoints, eng->spFstart, eng->spFstop);
-        if (n < 0) return static_cast<int>(n);
-        card.resize((size_t)n);
-        if (const int rc = csim_ac_freqs(eng->spSweep, eng->spPoints, eng->spFstart, eng->spFstop, card.data())) return rc;
-        freqs = card.data();
-        F = static_cast<int32_t>(n);
-    }
-    if (F < 0 || (B > 0 && F > 0 && !y)) { setError("csim_sp_batch: bad argument"); return CSIM_ERR_ARG; }
-    if (B == 0) return CSIM_OK;
-    HIPCHK(hipSetDevice(eng->device));
-    const int N = eng->plan.N, PP = (int)(eng->spPortEq.size() * eng->spPortEq.size());
-    const size_t outDoubles = (size_t)2 * F * PP * B;
-    DevBuf dParams, dX, dIt, dSt, dY, dS;
-    int rc = stageParams(eng, params, B, dParams);
-    if (rc) return rc;
-    HIPCHK(dX.alloc(sizeof(double) * (size_t)N * B));
-    HIPCHK(dIt.alloc(sizeof(int32_t) * (size_t)B));
-    HIPCHK(dSt.alloc(sizeof(uint32_t) * (size_t)B));
-    HIPCHK(dY.alloc(sizeof(double) * outDoubles));
-    if (s) HIPCHK(dS.alloc(sizeof(double) * outDoubles));
-    rc = csim_dc_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), dIt.as<int32_t>(), dSt.as<uint32_t>(), nullptr);
-    if (rc) return rc;
-    rc = csim_sp_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), freqs, F, dY.as<double>(),
-                           s ? dS.as<double>() : nullptr, dSt.as<uint32_t>(), nullptr);
-    if (rc) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    if (status) HIPCHK(hipMemcpy(status, dSt.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    if ((rc = toHost(dY.as<double>(), F, PP, B, 2, y))) return rc;
-    if (s) return toHost(dS.as<double>(), F, PP, B, 2, s);
-    return CSIM_OK;
-}
-
-// ---- two-port noise analysis ------------------------------------------------
-
-// the engine's ports, the temperature and the wish for noise parameters -> the kernels' numbers (include/csim.h
-// "Two-port noise analysis"); port and size errors are those of the S-parameter analysis
-static int spNoiseSetup(const csim_engine* eng, double temp_k, bool wantParams, csim::SpNoiseArgs& a, double& kT4)
-{
-    csim::SpArgs sp{};
-    if (const int rc = spSetup(eng, sp)) return rc;
-    if (wantParams && sp.P != 2) { setError("two-port noise analysis: NF, Fmin, Rn and Yopt exist for two ports only"); return CSIM_ERR_CONFIG; }
-    if (!(temp_k > 0.0) || !std::isfinite(temp_k)) { setError("two-port noise analysis: the temperature must be positive and finite (kelvin)"); return CSIM_ERR_CONFIG; }
-    kT4 = 4.0 * 1.380649e-23 * temp_k;
-    a.N = sp.N;
-    a.P = sp.P;
-    for (int i = 0; i < sp.P; ++i) a.portEq[i] = sp.portEq[i];
-    a.eps = sp.eps;
-    a.kT40 = 4.0 * 1.380649e-23 * 290.0;
-    a.gs = 1.0 / eng->spZ0[0];
-    a.S = eng->nNoiseSrc;
-    a.srcA = eng->dNoiseA;
-    a.srcB = eng->dNoiseB;
-    return CSIM_OK;
-}
-
-int csim_spnoise_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const double* d_xop, const double* freqs,
-                           int32_t F, double temp_k, double* d_y, double* d_cy, double* d_nf, double* d_fmin, double* d_rn,
-                           double* d_yopt, uint32_t* d_status, void* stream)
-{
-    if (!eng || B < 0 || F < 0) { setError("csim_spnoise_batch_dev: bad argument"); return CSIM_ERR_ARG; }
-    csim::SpNoiseArgs a{};
-    double kT4 = 0.0;
-    if (const int rc = spNoiseSetup(eng, temp_k, d_nf || d_fmin || d_rn || d_yopt, a, kT4)) return rc;
-    if (B > 0 && F > 0 && (!d_params || !d_xop || !freqs || !d_cy || !d_status)) {
-        setError("csim_spnoise_batch_dev: bad argument");
-        return CSIM_ERR_ARG;
-    }
-    const int N = a.N, S = a.S;
-    int which = eng->cfg.acKernel;
-    if (which == csim::AC_KERNEL_AUTO) which = N <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;   // block: as it is
-    if (which == csim::AC_KERNEL_PACKED && N > 32) { setError("ac_kernel=packed covers N <= 32"); return CSIM_ERR_UNSUPPORTED; }
-    if (B == 0 || F == 0) return CSIM_OK;
-    HIPCHK(hipSetDevice(eng->device));
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-
-    const double* dOmega = nullptr;
-    if (const int rc = acOmega(eng, freqs, F, &dOmega)) return rc;
-    const int chunk = acChunk(eng, B);
-    if (const int rc = acSysScratch(eng, chunk)) return rc;
-    if (eng->noisePsdCap < (size_t)S * (size_t)chunk) {
-        if (eng->dNoisePsd) HIPCHK(hipFree(eng->dNoisePsd));
-        eng->dNoisePsd = nullptr;
-        eng->noisePsdCap = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&eng->dNoisePsd), sizeof(double) * (size_t)S * (size_t)chunk));
-        eng->noisePsdCap = (size_t)S * (size_t)chunk;
-    }
-    a.F = F;
-    a.B = B;
-    a.sys = eng->dAcSys;
-    a.omega = dOmega;
-    a.psd = eng->dNoisePsd;
-    a.psdStride = (size_t)chunk;
-    a.psdOff = 0;
-    a.y = d_y;
-    a.cy = d_cy;
-    a.nf = d_nf;
-    a.fmin = d_fmin;
-    a.rn = d_rn;
-    a.yopt = d_yopt;
-    a.x = nullptr;
-    a.status = d_status;
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-        a.b0 = b0;
-        a.Bc = std::min(chunk, B - b0);
-        HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, b0, a.Bc, d_xop, eng->dAcSys, hs));
-        HIPCHK(csim::launchNoisePsd(eng->gpTran, eng->dNoiseElem, S, d_params, B, b0, a.Bc, d_xop, kT4, eng->dNoisePsd,
-                                    a.psdStride, a.psdOff, hs));
-        HIPCHK(csim::launchSpNoiseSweep(which, a, hs));
-    }
-    HIPCHK(hipEventRecord(eng->acOmegaSlots[(size_t)eng->acOmegaCur].done, hs));
-    return CSIM_OK;
-}
-
-int csim_spnoise_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F, double temp_k,
-                       double* y, double* cy, double* nf, double* fmin, double* rn, double* yopt, uint32_t* status)
-{
-    if (!eng || B < 0) { setError("csim_spnoise_batch: bad argument"); return CSIM_ERR_ARG; }
-    const bool wantParams = nf || fmin || rn || yopt;
-    {
-        csim::SpNoiseArgs probe{};
-        double kT4 = 0.0;
-        if (const int rc = spNoiseSetup(eng, temp_k, wantParams, probe, kT4)) return rc;
-    }
-    std::vector<double> card;
-    if (!freqs) {
-        if (!eng->spEnabled) { setError("csim_spnoise_batch: no frequencies given and the netlist has no .SP card"); return CSIM_ERR_CONFIG; }
-        const int64_t n = csim_ac_num_freqs(eng->spSweep, eng->spPoints, eng->spFstart, eng->spFstop);
-        if (n < 0) return static_cast<int>(n);
-        card.resize((size_t)n);
-        if (const int rc = csim_ac_freqs(eng->spSweep, eng->spPoints, eng->spFstart, eng->spFstop, card.data())) return rc;
-        freqs = card.data();
-        F = static_cast<int32_t>(n);
-    }
-    if (F < 0 || (B > 0 && F > 0 && !cy)) { setError("csim_spnoise_batch: bad argument"); return CSIM_ERR_ARG; }
-    if (B == 0) return CSIM_OK;
-    HIPCHK(hipSetDevice(eng->device));
-    const int N = eng->plan.N, PP = (int)(eng->spPortEq.size() * eng->spPortEq.size());
-    const size_t FB = (size_t)F * (size_t)B, ppDoubles = 2 * FB * (size_t)PP;
-    DevBuf dParams, dX, dIt, dSt, dY, dCy, dNf, dFmin, dRn, dYopt;
-    int rc = stageParams(eng, params, B, dParams);
-    if (rc) return rc;
-    HIPCHK(dX.alloc(sizeof(double) * (size_t)N * B));
-    HIPCHK(dIt.alloc(sizeof(int32_t) * (size_t)B));
-    HIPCHK(dSt.alloc(sizeof(uint32_t) * (size_t)B));
-    HIPCHK(dCy.alloc(sizeof(double) * ppDoubles));
-    if (y) HIPCHK(dY.alloc(sizeof(double) * ppDoubles));
-    if (nf) HIPCHK(dNf.alloc(sizeof(double) * FB));
-    if (fmin) HIPCHK(dFmin.alloc(sizeof(double) * FB));
-    if (rn) HIPCHK(dRn.alloc(sizeof(double) * FB));
-    if (yopt) HIPCHK(dYopt.alloc(sizeof(double) * 2 * FB));
-    rc = csim_dc_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), dIt.as<int32_t>(), dSt.as<uint32_t>(), nullptr);
-    if (rc) return rc;
-    rc = csim_spnoise_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), freqs, F, temp_k, y ? dY.as<double>() : nullptr,
-                                dCy.as<double>(), nf ? dNf.as<double>() : nullptr, fmin ? dFmin.as<double>() : nullptr,
-                                rn ? dRn.as<double>() : nullptr, yopt ? dYopt.as<double>() : nullptr, dSt.as<uint32_t>(),
-                                nullptr);
-    if (rc) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    if (status) HIPCHK(hipMemcpy(status, dSt.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    if ((rc = toHost(dCy.as<double>(), F, PP, B, 2, cy))) return rc;
-    if (y && (rc = toHost(dY.as<double>(), F, PP, B, 2, y))) return rc;
-    if (nf && (rc = toHost(dNf.as<double>(), F, 1, B, 1, nf))) return rc;
-    if (fmin && (rc = toHost(dFmin.as<double>(), F, 1, B, 1, fmin))) return rc;
-    if (rn && (rc = toHost(dRn.as<double>(), F, 1, B, 1, rn))) return rc;
-    if (yopt && (rc = toHost(dYopt.as<double>(), F, 1, B, 2, yopt))) return rc;
     return CSIM_OK;
 }
 
@@ -1730,300 +1081,6 @@ int csim_lu_solve_batch(int32_t device, int32_t n, int32_t B, const double* A, c
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(x, dX.p, sizeof(double) * (size_t)n * B, hipMemcpyDeviceToHost));
     if (flags) HIPCHK(hipMemcpy(flags, dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    return CSIM_OK;
-}
-
-// [B][n][n] row-major -> the layout the sweep kernels read: G, C column-major, J re, J im (zeros without a J)
-static std::vector<double> packAcSystems(int n, int B, const double* G, const double* Cm, const double* J)
-{
-    const size_t nn = (size_t)n * n, per = csim::acSystemDoubles(n);
-    std::vector<double> sys(per * (size_t)B);
-    for (int b = 0; b < B; ++b) {
-        double* s = sys.data() + per * (size_t)b;
-        for (int i = 0; i < n; ++i) {
-            for (int j = 0; j < n; ++j) {
-                s[(size_t)j * n + i] = G[nn * b + (size_t)i * n + j];
-                s[nn + (size_t)j * n + i] = Cm[nn * b + (size_t)i * n + j];
-            }
-            s[2 * nn + i] = J ? J[((size_t)b * n + i) * 2] : 0.0;
-            s[2 * nn + n + i] = J ? J[((size_t)b * n + i) * 2 + 1] : 0.0;
-        }
-    }
-    return sys;
-}
-
-// the selector values of the *_solve_batch entries (3 is none)
-static bool acKernelValid(int kernel)
-{
-    return (kernel >= csim::AC_KERNEL_AUTO && kernel <= csim::AC_KERNEL_PACKED) || kernel == csim::AC_KERNEL_BLOCK;
-}
-
-// The common front of the engine-free *_solve_batch entries: device check, kernel choice and its refusals; then, when
-// there is work, the packed systems, the angular frequencies and zeroed flags on the device.
-struct AcSolveFront {
-    int which = csim::AC_KERNEL_AUTO;
-    DevBuf dSys, dOmega, dF, dWork;         // dWork: the block kernel's planes
-};
-static int acSolveFront(const char* entry, int device, int n, int B, const double* G, const double* Cm, const double* J,
-                        const double* omega, int F, int kernel, bool work, AcSolveFront& fr, bool blockCovered = false)
-{
-    const std::string name(entry);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
-        setError(name + ": no usable HIP device (this library has no CPU path)");
-        return CSIM_ERR_NO_DEVICE;
-    }
-    if (kernel == csim::AC_KERNEL_BLOCK) {
-        if (!blockCovered) { setError(name + ": the block kernel covers AC and noise analysis only"); return CSIM_ERR_UNSUPPORTED; }
-        if (n > 1024) { setError(name + ": the block kernel covers n <= 1024"); return CSIM_ERR_UNSUPPORTED; }
-    } else if (n > 63) { setError(name + " covers n <= 63"); return CSIM_ERR_UNSUPPORTED; }
-    fr.which = kernel;
-    if (fr.which == csim::AC_KERNEL_AUTO) fr.which = n <= 32 ? csim::AC_KERNEL_PACKED : csim::AC_KERNEL_WAVE;
-    if (fr.which == csim::AC_KERNEL_PACKED && n > 32) { setError(name + ": the packed kernel covers n <= 32"); return CSIM_ERR_UNSUPPORTED; }
-    if (!work) return CSIM_OK;
-    HIPCHK(hipSetDevice(device));
-    const std::vector<double> sys = packAcSystems(n, B, G, Cm, J);
-    HIPCHK(fr.dSys.alloc(sizeof(double) * sys.size()));
-    HIPCHK(fr.dOmega.alloc(sizeof(double) * (size_t)F));
-    HIPCHK(fr.dF.alloc(sizeof(uint32_t) * (size_t)B));
-    if (fr.which == csim::AC_KERNEL_BLOCK) HIPCHK(fr.dWork.alloc(sizeof(double) * csim::acBlockWorkDoubles(n) * (size_t)B));
-    HIPCHK(hipMemcpy(fr.dSys.p, sys.data(), sizeof(double) * sys.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(fr.dOmega.p, omega, sizeof(double) * (size_t)F, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(fr.dF.p, 0, sizeof(uint32_t) * (size_t)B));
-    return CSIM_OK;
-}
-
-// the complex counterpart: any (G + jwC) x = J through the AC sweep kernels, without an engine or a netlist
-int csim_ac_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* Cm, const double* J,
-                        const double* omega, int32_t F, int32_t kernel, double* x, uint32_t* flags)
-{
-    if (n < 0 || B < 0 || F < 0 || !acKernelValid(kernel) ||
-        (n > 0 && B > 0 && F > 0 && (!G || !Cm || !J || !omega || !x))) {
-        setError("csim_ac_solve_batch: bad argument");
-        return CSIM_ERR_ARG;
-    }
-    const bool work = n > 0 && B > 0 && F > 0;
-    AcSolveFront fr;
-    if (const int rc = acSolveFront("csim_ac_solve_batch", device, n, B, G, Cm, J, omega, F, kernel, work, fr, true)) return rc;
-    if (!work) return CSIM_OK;
-    const size_t outDoubles = (size_t)2 * F * n * B;
-    DevBuf dOut;
-    HIPCHK(dOut.alloc(sizeof(double) * outDoubles));
-    HIPCHK(hipMemset(dOut.p, 0, sizeof(double) * outDoubles));
-    HIPCHK(csim::launchAcSweep(fr.which, n, fr.dSys.as<double>(), fr.dOmega.as<double>(), F, nullptr, n, B, 0, B, 1e-15,
-                               dOut.as<double>(), fr.dF.as<uint32_t>(), nullptr, fr.dWork.as<double>()));
-    HIPCHK(hipDeviceSynchronize());
-    if (const int rc = toHost(dOut.as<double>(), F, n, B, 2, x)) return rc;
-    if (flags) HIPCHK(hipMemcpy(flags, fr.dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    return CSIM_OK;
-}
-
-// the engine-free counterpart for the noise kernels: any system, any generator table
-int csim_noise_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* Cm, int32_t out_p,
-                           int32_t out_m, int32_t S, const int32_t* src_a, const int32_t* src_b, const double* psd,
-                           int32_t in_kind, int32_t in_a, int32_t in_b, const double* omega, int32_t F, int32_t kernel,
-                           double* onoise, double* contrib, double* gain, double* y, uint32_t* flags)
-{
-    const bool work = n > 0 && B > 0 && F > 0;
-    if (n < 0 || B < 0 || F < 0 || S < 0 || !acKernelValid(kernel) ||
-        in_kind < csim::NOISE_IN_NONE || in_kind > csim::NOISE_IN_I ||
-        (work && (!G || !Cm || !omega || !onoise || (S > 0 && (!src_a || !src_b || !psd))))) {
-        setError("csim_noise_solve_batch: bad argument");
-        return CSIM_ERR_ARG;
-    }
-    if (n > 0) {
-        bool ok = out_p >= 0 && out_p < n && out_m >= -1 && out_m < n && out_p != out_m;
-        for (int s = 0; s < S && ok && src_a && src_b; ++s)
-            ok = src_a[s] >= -1 && src_a[s] < n && src_b[s] >= -1 && src_b[s] < n;
-        if (in_kind == csim::NOISE_IN_V) ok = ok && in_a >= 0 && in_a < n;
-        if (in_kind == csim::NOISE_IN_I) ok = ok && in_a >= -1 && in_a < n && in_b >= -1 && in_b < n;
-        if (!ok) { setError("csim_noise_solve_batch: equation index out of range (or out_p == out_m)"); return CSIM_ERR_ARG; }
-    }
-    AcSolveFront fr;
-    if (const int rc = acSolveFront("csim_noise_solve_batch", device, n, B, G, Cm, nullptr, omega, F, kernel, work, fr, true)) return rc;
-    if (!work) return CSIM_OK;
-    std::vector<double> psdT((size_t)S * B);                 // [B][S] -> [S][B]
-    for (int b = 0; b < B; ++b)
-        for (int s = 0; s < S; ++s) psdT[(size_t)s * B + b] = psd[(size_t)b * S + s];
-    const size_t FB = (size_t)F * (size_t)B;
-    const bool wantGain = gain && in_kind != csim::NOISE_IN_NONE;
-    DevBuf dA, dB, dPsd, dOn, dCon, dGain, dY;
-    HIPCHK(dA.alloc(sizeof(int32_t) * (size_t)S));
-    HIPCHK(dB.alloc(sizeof(int32_t) * (size_t)S));
-    HIPCHK(dPsd.alloc(sizeof(double) * psdT.size()));
-    HIPCHK(dOn.alloc(sizeof(double) * FB));
-    if (contrib) HIPCHK(dCon.alloc(sizeof(double) * FB * (size_t)S));
-    if (wantGain) HIPCHK(dGain.alloc(sizeof(double) * 2 * FB));
-    if (y) HIPCHK(dY.alloc(sizeof(double) * 2 * FB * (size_t)n));
-    if (S > 0) {
-        HIPCHK(hipMemcpy(dA.p, src_a, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dB.p, src_b, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dPsd.p, psdT.data(), sizeof(double) * psdT.size(), hipMemcpyHostToDevice));
-    }
-    csim::NoiseArgs a{};
-    a.N = n; a.F = F; a.S = S; a.B = B; a.b0 = 0; a.Bc = B;
-    a.outP = out_p; a.outM = out_m;
-    a.inKind = in_kind; a.inA = in_a; a.inB = in_b;
-    a.eps = 1e-15;
-    a.sys = fr.dSys.as<double>();
-    a.omega = fr.dOmega.as<double>();
-    a.srcA = dA.as<int32_t>();
-    a.srcB = dB.as<int32_t>();
-    a.psd = dPsd.as<double>();
-    a.psdStride = (size_t)B;
-    a.psdOff = 0;
-    a.onoise = dOn.as<double>();
-    a.gain = wantGain ? dGain.as<double>() : nullptr;
-    a.contrib = contrib ? dCon.as<double>() : nullptr;
-    a.y = y ? dY.as<double>() : nullptr;
-    a.status = fr.dF.as<uint32_t>();
-    a.work = fr.dWork.as<double>();
-    HIPCHK(csim::launchNoiseSweep(fr.which, a, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    int rc = toHost(dOn.as<double>(), F, 1, B, 1, onoise);
-    if (!rc && wantGain) rc = toHost(dGain.as<double>(), F, 1, B, 2, gain);
-    if (!rc && contrib) rc = toHost(dCon.as<double>(), F, S, B, 1, contrib);
-    if (!rc && y) rc = toHost(dY.as<double>(), F, n, B, 2, y);
-    if (rc) return rc;
-    if (flags) HIPCHK(hipMemcpy(flags, fr.dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    return CSIM_OK;
-}
-
-// the engine-free counterpart for the S-parameter kernels: K right-hand sides per system, or (port_eq given) the
-// ports' unit vectors with Y and S
-int csim_sp_solve_batch(int32_t device, int32_t n, int32_t B, int32_t K, const double* G, const double* Cm, const double* J,
-                        const double* omega, int32_t F, int32_t kernel, double* x, uint32_t* flags, const int32_t* port_eq,
-                        const double* z0, double* y, double* s)
-{
-    const bool work = n > 0 && B > 0 && F > 0;
-    const bool ports = port_eq != nullptr;
-    if (n < 0 || B < 0 || F < 0 || !acKernelValid(kernel) ||
-        (work && (!G || !Cm || !omega || (ports ? (!z0 || !y) : (!J || !x))))) {
-        setError("csim_sp_solve_batch: bad argument");
-        return CSIM_ERR_ARG;
-    }
-    if (K < 1 || K > csim::SP_MAX_PORTS) { setError("csim_sp_solve_batch: 1 to 4 right-hand sides / ports"); return CSIM_ERR_ARG; }
-    if (ports && n > 0)
-        for (int i = 0; i < K; ++i) {
-            if (port_eq[i] < 0 || port_eq[i] >= n) { setError("csim_sp_solve_batch: port equation out of range"); return CSIM_ERR_ARG; }
-            if (!(z0[i] > 0.0) || !std::isfinite(z0[i])) { setError("csim_sp_solve_batch: Z0 must be finite and > 0"); return CSIM_ERR_ARG; }
-        }
-    AcSolveFront fr;
-    if (const int rc = acSolveFront("csim_sp_solve_batch", device, n, B, G, Cm, nullptr, omega, F, kernel, work, fr)) return rc;
-    if (!work) return CSIM_OK;
-    const size_t xDoubles = (size_t)2 * F * K * n * B, yDoubles = (size_t)2 * F * K * K * B;
-    const bool wantX = x != nullptr;
-    DevBuf dJ, dX, dY, dS;
-    csim::SpArgs a{};
-    a.N = n; a.K = K; a.P = ports ? K : 0; a.F = F; a.B = B; a.b0 = 0; a.Bc = B;
-    a.eps = 1e-15;
-    a.sys = fr.dSys.as<double>();
-    a.omega = fr.dOmega.as<double>();
-    a.status = fr.dF.as<uint32_t>();
-    if (wantX) {
-        HIPCHK(dX.alloc(sizeof(double) * xDoubles));
-        HIPCHK(hipMemset(dX.p, 0, sizeof(double) * xDoubles));
-        a.x = dX.as<double>();
-    }
-    if (ports) {
-        for (int i = 0; i < K; ++i) { a.portEq[i] = port_eq[i]; a.sz[i] = std::sqrt(z0[i]); }
-        HIPCHK(dY.alloc(sizeof(double) * yDoubles));
-        a.y = dY.as<double>();
-        if (s) { HIPCHK(dS.alloc(sizeof(double) * yDoubles)); a.s = dS.as<double>(); }
-    } else {
-        HIPCHK(dJ.alloc(sizeof(double) * (size_t)2 * K * n * B));
-        HIPCHK(hipMemcpy(dJ.p, J, sizeof(double) * (size_t)2 * K * n * B, hipMemcpyHostToDevice));
-        a.rhs = dJ.as<double>();
-    }
-    HIPCHK(csim::launchSpSweep(fr.which, a, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    int rc = CSIM_OK;
-    if (wantX) rc = toHost(dX.as<double>(), F, K * n, B, 2, x);              // [F][K][n][B] -> [B][F][K][n]
-    if (!rc && ports) rc = toHost(dY.as<double>(), F, K * K, B, 2, y);
-    if (!rc && ports && s) rc = toHost(dS.as<double>(), F, K * K, B, 2, s);
-    if (rc) return rc;
-    if (flags) HIPCHK(hipMemcpy(flags, fr.dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    return CSIM_OK;
-}
-
-// the engine-free counterpart for the two-port noise kernels: any system, any ports, any generator table
-int csim_spnoise_solve_batch(int32_t device, int32_t n, int32_t B, int32_t P, const double* G, const double* Cm,
-                             const int32_t* port_eq, const double* z0, int32_t S, const int32_t* src_a, const int32_t* src_b,
-                             const double* psd, const double* omega, int32_t F, int32_t kernel, double* y, double* cy,
-                             double* nf, double* fmin, double* rn, double* yopt, double* x, uint32_t* flags)
-{
-    const bool work = n > 0 && B > 0 && F > 0;
-    if (n < 0 || B < 0 || F < 0 || S < 0 || !acKernelValid(kernel) || !port_eq || !z0 ||
-        (work && (!G || !Cm || !omega || !cy || (S > 0 && (!src_a || !src_b || !psd))))) {
-        setError("csim_spnoise_solve_batch: bad argument");
-        return CSIM_ERR_ARG;
-    }
-    if (P < 1 || P > csim::SP_MAX_PORTS) { setError("csim_spnoise_solve_batch: 1 to 4 ports"); return CSIM_ERR_ARG; }
-    for (int i = 0; i < P; ++i)
-        if (!(z0[i] > 0.0) || !std::isfinite(z0[i])) { setError("csim_spnoise_solve_batch: Z0 must be finite and > 0"); return CSIM_ERR_ARG; }
-    if (n > 0) {
-        bool ok = true;
-        for (int i = 0; i < P; ++i) ok = ok && port_eq[i] >= 0 && port_eq[i] < n;
-        for (int s = 0; s < S && ok && src_a && src_b; ++s)
-            ok = src_a[s] >= -1 && src_a[s] < n && src_b[s] >= -1 && src_b[s] < n;
-        if (!ok) { setError("csim_spnoise_solve_batch: equation index out of range"); return CSIM_ERR_ARG; }
-    }
-    if (P != 2 && (nf || fmin || rn || yopt)) { setError("csim_spnoise_solve_batch: NF, Fmin, Rn and Yopt exist for two ports only"); return CSIM_ERR_CONFIG; }
-    AcSolveFront fr;
-    if (const int rc = acSolveFront("csim_spnoise_solve_batch", device, n, B, G, Cm, nullptr, omega, F, kernel, work, fr)) return rc;
-    if (!work) return CSIM_OK;
-    std::vector<double> psdT((size_t)S * B);                 // [B][S] -> [S][B]
-    for (int b = 0; b < B; ++b)
-        for (int s = 0; s < S; ++s) psdT[(size_t)s * B + b] = psd[(size_t)b * S + s];
-    const size_t FB = (size_t)F * (size_t)B, ppDoubles = 2 * FB * (size_t)(P * P);
-    DevBuf dA, dB, dPsd, dY, dCy, dNf, dFmin, dRn, dYopt, dX;
-    HIPCHK(dA.alloc(sizeof(int32_t) * (size_t)S));
-    HIPCHK(dB.alloc(sizeof(int32_t) * (size_t)S));
-    HIPCHK(dPsd.alloc(sizeof(double) * psdT.size()));
-    HIPCHK(dCy.alloc(sizeof(double) * ppDoubles));
-    if (y) HIPCHK(dY.alloc(sizeof(double) * ppDoubles));
-    if (nf) HIPCHK(dNf.alloc(sizeof(double) * FB));
-    if (fmin) HIPCHK(dFmin.alloc(sizeof(double) * FB));
-    if (rn) HIPCHK(dRn.alloc(sizeof(double) * FB));
-    if (yopt) HIPCHK(dYopt.alloc(sizeof(double) * 2 * FB));
-    if (x) HIPCHK(dX.alloc(sizeof(double) * 2 * FB * (size_t)P * (size_t)n));
-    if (S > 0) {
-        HIPCHK(hipMemcpy(dA.p, src_a, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dB.p, src_b, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dPsd.p, psdT.data(), sizeof(double) * psdT.size(), hipMemcpyHostToDevice));
-    }
-    csim::SpNoiseArgs a{};
-    a.N = n; a.P = P; a.F = F; a.S = S; a.B = B; a.b0 = 0; a.Bc = B;
-    for (int i = 0; i < P; ++i) a.portEq[i] = port_eq[i];
-    a.eps = 1e-15;
-    a.kT40 = 4.0 * 1.380649e-23 * 290.0;
-    a.gs = 1.0 / z0[0];
-    a.sys = fr.dSys.as<double>();
-    a.omega = fr.dOmega.as<double>();
-    a.srcA = dA.as<int32_t>();
-    a.srcB = dB.as<int32_t>();
-    a.psd = dPsd.as<double>();
-    a.psdStride = (size_t)B;
-    a.psdOff = 0;
-    a.y = y ? dY.as<double>() : nullptr;
-    a.cy = dCy.as<double>();
-    a.nf = nf ? dNf.as<double>() : nullptr;
-    a.fmin = fmin ? dFmin.as<double>() : nullptr;
-    a.rn = rn ? dRn.as<double>() : nullptr;
-    a.yopt = yopt ? dYopt.as<double>() : nullptr;
-    a.x = x ? dX.as<double>() : nullptr;
-    a.status = fr.dF.as<uint32_t>();
-    HIPCHK(csim::launchSpNoiseSweep(fr.which, a, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    int rc = toHost(dCy.as<double>(), F, P * P, B, 2, cy);
-    if (!rc && y) rc = toHost(dY.as<double>(), F, P * P, B, 2, y);
-    if (!rc && nf) rc = toHost(dNf.as<double>(), F, 1, B, 1, nf);
-    if (!rc && fmin) rc = toHost(dFmin.as<double>(), F, 1, B, 1, fmin);
-    if (!rc && rn) rc = toHost(dRn.as<double>(), F, 1, B, 1, rn);
-    if (!rc && yopt) rc = toHost(dYopt.as<double>(), F, 1, B, 2, yopt);
-    if (!rc && x) rc = toHost(dX.as<double>(), F, P * n, B, 2, x);           // [F][P][n][B] -> [B][F][P][n]
-    if (rc) return rc;
-    if (flags) HIPCHK(hipMemcpy(flags, fr.dF.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
     return CSIM_OK;
 }
 

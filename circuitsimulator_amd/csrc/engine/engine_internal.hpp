@@ -29,7 +29,8 @@ struct EngineConfig {
     std::string jitGenOpts;      // jit_gen_opts: generator options of this engine's JIT, "key=value,key=value" (codegen.hpp)
     bool nearTestRollback = false;   // near_test_rollback: test aid -- every verified near-threshold decision counts as a
                                  // mismatch, so the roll-back path runs (results must not change)
-    int acKernel = 0;            // ac_kernel: test aid -- 0 auto (register-resident for N <= 32, else wave), 1 wave, 2 packed
+    int acKernel = 0;            // ac_kernel: 0 auto (register-resident for N <= 32, else wave), 1 wave, 2 packed (test aids),
+                                 // 4 block (opt-in: one workgroup per system, AC and noise up to 1024 unknowns)
     bool dcFast = false;         // dc_fast        / CSIM_DC_FAST: 1 = DC operating points start on the fast generated kernel
                                  // (contraction, reciprocal pivots, guarded decisions) instead of the faithful one
 };

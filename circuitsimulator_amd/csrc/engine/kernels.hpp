@@ -89,10 +89,19 @@ size_t acBlockWorkDoubles(int N);
 hipError_t launchAcAssemble(const GenPlan& pl, const double* dAcRe, const double* dAcIm, const double* dParams, int B,
                             int b0, int Bc, const double* dXop, double* dSys, hipStream_t stream,
                             int which = AC_KERNEL_AUTO);
-// dOut [F][nProbe][B] complex (re, im), dStatus [B] OR-ed; dProbe null = every unknown (nProbe = N)
-hipError_t launchAcSweep(int which, int N, const double* dSys, const double* dOmega, int F, const int32_t* dProbe,
-                         int nProbe, int B, int b0, int Bc, double eps, double* dOut, uint32_t* dStatus, hipStream_t stream,
-                         double* dWork = nullptr);
+// the sweep on the systems launchAcAssemble leaves (host side only: the kernels take these one by one)
+struct AcArgs {
+    int N, F, B, b0, Bc;
+    int nProbe;
+    double eps;
+    const double* sys;
+    const double* omega;
+    const int32_t* probe;               // [nProbe] equations, or null = every unknown (nProbe = N)
+    double* out;                        // [F][nProbe][B] complex (re, im)
+    uint32_t* status;                   // [B], OR-ed
+    double* work;                       // AC_KERNEL_BLOCK: acBlockWorkDoubles(N) doubles per chunk instance
+};
+hipError_t launchAcSweep(int which, const AcArgs& a, hipStream_t stream);
 
 // Noise analysis (kernels_noise.hip) on the systems launchAcAssemble leaves.  Generator s of chunk instance c has
 // its PSD at psd[s * psdStride + psdOff + c].  Equation indices are checked by the callers: they index LDS.

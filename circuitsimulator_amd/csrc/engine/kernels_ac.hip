@@ -328,27 +328,25 @@ hipError_t launchAcAssemble(const GenPlan& pl, const double* dAcRe, const double
     return hipGetLastError();
 }
 
-hipError_t launchAcSweep(int which, int N, const double* dSys, const double* dOmega, int F, const int32_t* dProbe,
-                         int nProbe, int B, int b0, int Bc, double eps, double* dOut, uint32_t* dStatus, hipStream_t stream,
-                         double* dWork)
+hipError_t launchAcSweep(int which, const AcArgs& a, hipStream_t stream)
 {
-    if (Bc <= 0 || F <= 0) return hipSuccess;
-    if (!ac_sweep_covers(which, N)) return hipErrorInvalidValue;
+    if (a.Bc <= 0 || a.F <= 0) return hipSuccess;
+    if (!ac_sweep_covers(which, a.N)) return hipErrorInvalidValue;
     if (which == AC_KERNEL_BLOCK) {
-        if (!dWork) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(ac_sweep_block_kernel, dim3(Bc), dim3(ACB_THREADS), acb_lds_bytes(N, 1), stream, N, dSys, dOmega, F,
-                           dProbe, nProbe, B, b0, eps, dOut, dStatus, dWork);
+        if (!a.work) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(ac_sweep_block_kernel, dim3(a.Bc), dim3(ACB_THREADS), acb_lds_bytes(a.N, 1), stream, a.N, a.sys, a.omega,
+                           a.F, a.probe, a.nProbe, a.B, a.b0, a.eps, a.out, a.status, a.work);
     } else if (which == AC_KERNEL_PACKED) {
-        acp_dispatch(N, [&](auto np) {
-            hipLaunchKernelGGL(ac_sweep_packed_kernel<decltype(np)::value>, dim3((Bc + 1) / 2), dim3(64), 0, stream, N, dSys,
-                               dOmega, F, dProbe, nProbe, B, b0, Bc, eps, dOut, dStatus);
+        acp_dispatch(a.N, [&](auto np) {
+            hipLaunchKernelGGL(ac_sweep_packed_kernel<decltype(np)::value>, dim3((a.Bc + 1) / 2), dim3(64), 0, stream, a.N, a.sys,
+                               a.omega, a.F, a.probe, a.nProbe, a.B, a.b0, a.Bc, a.eps, a.out, a.status);
         });
     } else {
-        const size_t lds = acw_lds_bytes(N, 1);
+        const size_t lds = acw_lds_bytes(a.N, 1);
         if (lds > 64 * 1024)
             (void)hipFuncSetAttribute((const void*)ac_sweep_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(ac_sweep_wave_kernel, dim3(Bc), dim3(64), lds, stream, N, dSys, dOmega, F, dProbe, nProbe, B, b0,
-                           eps, dOut, dStatus);
+        hipLaunchKernelGGL(ac_sweep_wave_kernel, dim3(a.Bc), dim3(64), lds, stream, a.N, a.sys, a.omega, a.F, a.probe, a.nProbe,
+                           a.B, a.b0, a.eps, a.out, a.status);
     }
     return hipGetLastError();
 }

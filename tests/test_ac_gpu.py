@@ -256,7 +256,7 @@ def test_singular_instance_flagged_others_unchanged():
 
 # ---- instance chunking, the frequency / probe caches, stream order, excitation, sizes, layout
 def _ac_chunk(N):
-    """instances per chunk of csim_ac_batch_dev: 256 MiB of system scratch (engine.cpp acChunk)"""
+    """instances per chunk of csim_ac_batch_dev: 256 MiB of system scratch (engine_freq.cpp acChunk)"""
     return max(256, (256 << 20) // (8 * (2 * N * N + 2 * N)))
 
 

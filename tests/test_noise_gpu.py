@@ -207,7 +207,7 @@ def test_zero_resistance_has_no_noise():
 
 
 def _ac_chunk(N):
-    """instances per chunk of the sweeps: 256 MiB of system scratch (engine.cpp acChunk)"""
+    """instances per chunk of the sweeps: 256 MiB of system scratch (engine_freq.cpp acChunk)"""
     return max(256, (256 << 20) // (8 * (2 * N * N + 2 * N)))
 
 
