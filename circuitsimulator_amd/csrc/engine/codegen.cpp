@@ -110,6 +110,8 @@ bool GeneratorOptions::set(const std::string& keyval)
     if (key == "barrier_every") { barrierEvery = std::max(0, std::atoi(val.c_str())); return true; }
     if (key == "stage_ahead") { stageAhead = std::max(-1, std::atoi(val.c_str())); return true; }
     if (key == "pipeline_mos") { pipelineMos = std::atoi(val.c_str()) != 0; return true; }
+    if (key == "wait_at_use") { waitAtUse = std::atoi(val.c_str()) != 0 ? 1 : 0; return true; }
+    if (key == "cover_mos") { coverMos = std::max(0, std::min(2, std::atoi(val.c_str()))); return true; }
     if (key == "group_waves") { groupWavesPerEu = std::max(0, std::atoi(val.c_str())); return true; }
     if (key == "near_band") { nearBand = std::max(0.0, std::atof(val.c_str())); return true; }
     if (key == "near_band_dc") { nearBandDc = std::max(0.0, std::atof(val.c_str())); return true; }
@@ -150,6 +152,10 @@ uint64_t scheduleHash(const csim_ir& ir, const ScheduleSet& set, const Generator
     mix(static_cast<uint64_t>(gopt.linChainBarrier + 23) * 0x27D4EB2F165667C5ull);
     mix(static_cast<uint64_t>(gopt.group4 + 29) * 0x9FB21C651E98DF25ull);
     mix(static_cast<uint64_t>(gopt.placeSearch + 31) * 0xD6E8FEB86659FD93ull);
+    // (options added without a change of the default emission enter only when set: the hash of every earlier option
+    // set, which the emitted source carries, stays what it was)
+    if (gopt.waitAtUse) mix(static_cast<uint64_t>(gopt.waitAtUse + 37) * 0xA0761D6478BD642Full);
+    if (gopt.coverMos) mix(static_cast<uint64_t>(gopt.coverMos + 41) * 0xE7037ED1A0B428DBull);
     for (std::size_t a = 1; a < set.alts.size(); ++a) {
         h ^= 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2);
         for (int p : set.alts[a].pivotPos) { h ^= static_cast<uint64_t>(p + 1); h *= 1099511628211ull; }

@@ -68,6 +68,21 @@ struct GeneratorOptions {
                                  // that first needs it (-1: all rows read and added before the elimination)
     int pipelineMos = 1;         // sixteen-lane kernel: 1 = the MOSFET pass and the staging reads of iteration i+1 run at
                                  // the end of iteration i, under its convergence bookkeeping; 0 = at the head of i+1
+    int waitAtUse = 0;           // group kernels, pipelined form: 1 = the staging reads are issued in the order in which a solve first uses
+                                 // the rows and nothing waits for them before the loop's back edge: each wait falls inside the next
+                                 // pass's elimination, with a partial count; 0 = all rows have landed at the back edge.  (The per-step
+                                 // batch of TS / XP reads in front of a step's first pass is not part of it: it is waited for where
+                                 // the step's right-hand side is summed, as before.)  Measured on
+                                 // dbmixer, B = 4096, same box (profiles/r05_group16_b4096_summary.md): 2.540e9 against 2.557e9 alone,
+                                 // 2.557e9 with cover_mos=2 -- the rows are needed within the first 120 instructions of the pass,
+                                 // no later than they were waited for before
+    int coverMos = 0;            // group kernels, pipelined form, what runs with the norm under the gather of the MOSFET inputs (the
+                                 // first LDS round trip of the pipelined pass) instead of under the staging reads (the second):
+                                 // 2 = the ballot of the pivot checks (2.583e9 against 2.557e9), 1 = the ballot and the whole
+                                 // convergence bookkeeping (2.438e9: the staging reads lose their cover), 0 = nothing.
+                                 // The generator's own default is 0 -- its output for an option set that existed before is what
+                                 // it was, hash included, so the recorded md5s (tests/golden/generated_source.json) and the
+                                 // revision stand; the libraries that run are generated from engineDefaults(), which asks for 2
     int groupWavesPerEu = 0;     // sixteen-lane kernel: amdgpu_waves_per_eu(n, n) on the kernel (0 = leave it to the compiler)
     // Near-threshold guard of the FAST kernels (FMA contraction, reciprocal pivots).  A branch-deciding comparison
     // whose two sides agree to within this relative band could fall the other way in the reference's arithmetic:
@@ -98,7 +113,12 @@ struct GeneratorOptions {
     int linSrcLds = 1;           // linear sixteen-lane kernel: 1 = the sources' parameters are copied to LDS once per launch
     int nearForm = 0;            // sixteen-lane kernel, how a pass records a near tie: 0 = running minimum of |err - tol| (two
                                  // VALU instructions, one loop-carried double), 1 = two more compares into a loop-carried lane mask
-    bool set(const std::string& keyval);      // "barrier_every=3", "sweep=0,16,32", "stage_ahead=3", "pipeline_mos=0", "group_waves=2", "near_band=2e-8", "near_band_dc=1e-5"
+    // The options every library that runs is generated from -- the shipped ones (csim_codegen --engine-defaults, csrc/Makefile)
+    // and the engine's JIT, whose jit_gen_opts are set on top: the one place that holds the measured choices which are not
+    // the generator's own defaults.  tests/test_shipped_emission_cpu.py records this emission's md5 next to the revision,
+    // as tests/test_codegen_cpu.py does for the generator's defaults, and checks the shipped libraries against it.
+    static GeneratorOptions engineDefaults() { GeneratorOptions g; g.coverMos = 2; return g; }
+    bool set(const std::string& keyval);      // "barrier_every=3", "sweep=0,16,32", "stage_ahead=3", "pipeline_mos=0", "wait_at_use=1", "cover_mos=2", "group_waves=2", "near_band=2e-8", "near_band_dc=1e-5"
 };
 
 // bumped whenever the emitted code or the launcher ABI of a generated library changes

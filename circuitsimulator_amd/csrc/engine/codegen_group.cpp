@@ -445,6 +445,15 @@ std::string emitGroupKernel(const csim_ir& ir, const AssemblyPlan& ap, const std
       << "    if (stepFirst == 0 && sdone == 0 && wave && inb)\n"
       << "        for (int pq = g; pq < nProbe; pq += " << GS << ") wave[((long long)pq) * SB + b] = XS[probeEq[pq]];\n";
     const bool piped = gopt.pipelineMos != 0 && mosRounds > 0 && nStage > 0;
+    // pipelined form only (codegen.hpp GeneratorOptions::waitAtUse, coverMos): where the pass waits for the staging rows,
+    // and what runs under the gather of the MOSFET inputs.  Neither changes an operation, an operand or their order.
+    const bool waitAtUse = piped && gopt.waitAtUse != 0, coverMos = piped && gopt.coverMos == 1;
+    const bool coverBallot = piped && gopt.coverMos == 2 && !multi;
+    // order in which the pipelined pass issues the staging reads: as they are numbered, or as the first schedule's
+    // solve needs them (the LDS returns a wave's reads in issue order: partial waits, each where a row is first used)
+    std::vector<int> readOrder(static_cast<std::size_t>(nStage));
+    for (int r = 0; r < nStage; ++r) readOrder[static_cast<std::size_t>(r)] = r;
+    if (waitAtUse) readOrder = stageReadOrder(gp);
     // ---- MOSFET evaluation + scatter into the staging rows
     auto emitMos = [&](const std::string& ind) {
         for (int r = 0; r < mosRounds; ++r) {
@@ -470,7 +479,7 @@ std::string emitGroupKernel(const csim_ir& ir, const AssemblyPlan& ap, const std
         for (int r = 0; r < mosRounds; ++r)
             o << "    double vd" << r << " = XS[mD" << r << "], vg" << r << " = XS[mG" << r << "], vs" << r << " = XS[mS" << r << "];\n";
         emitMos("    ");
-        for (int r = 0; r < nStage; ++r) o << "    double sv" << r << " = ST[" << r * G << " + g];\n";
+        for (int r : readOrder) o << "    double sv" << r << " = ST[" << r * G << " + g];\n";
     }
     o << "    int smin = (int)(sdone < nSteps ? sdone + 1 : nSteps + 1);\n"
       << "    for (int m = 32; m >= 1; m >>= 1) { const int ot = __shfl_xor(smin, m); smin = ot < smin ? ot : smin; }\n"
@@ -556,22 +565,7 @@ std::string emitGroupKernel(const csim_ir& ir, const AssemblyPlan& ap, const std
     // there: issued up front, the reads end up one after the other, each waited for (the kernel sits at the
     // 256 architectural registers, so the compiler reuses one landing register: 13 LDS round trips, 28 % of
     // the wave's cycles); spread over the elimination they overlap with it.
-    std::vector<int> firstUse(static_cast<std::size_t>(nStage), N);   // column whose code first reads/writes the class
-    {
-        std::vector<std::vector<int>> fu(static_cast<std::size_t>(S), std::vector<int>(static_cast<std::size_t>(N + 1), N));
-        for (int k = N - 1; k >= 0; --k) {
-            const GroupPlan::Column& col = pl.cols[static_cast<std::size_t>(k)];
-            fu[static_cast<std::size_t>(col.pivSlot)][static_cast<std::size_t>(k)] = k;
-            for (int s : col.lSlots) fu[static_cast<std::size_t>(s)][static_cast<std::size_t>(k)] = k;
-            for (const GroupPlan::Check& c : col.checks) fu[static_cast<std::size_t>(c.slot)][static_cast<std::size_t>(k)] = k;
-            for (const GroupPlan::UEntry& u : col.u) {
-                fu[static_cast<std::size_t>(col.pivSlot)][static_cast<std::size_t>(u.j)] = k;
-                for (int s : col.lSlots) fu[static_cast<std::size_t>(s)][static_cast<std::size_t>(u.j)] = k;
-            }
-        }
-        for (int r = 0; r < nStage; ++r)
-            firstUse[static_cast<std::size_t>(r)] = fu[static_cast<std::size_t>(pl.stageRows[static_cast<std::size_t>(r)].s)][static_cast<std::size_t>(pl.stageRows[static_cast<std::size_t>(r)].j)];
-    }
+    const std::vector<int> firstUse = stageFirstUse(pl);              // column whose code first reads/writes the class
     const int ahead = gopt.stageAhead;
     auto stageReads = [&](int k) {       // reads issued at the head of column k (k = N: before the substitution)
         for (int r = 0; r < nStage; ++r) {
@@ -736,32 +730,48 @@ std::string emitGroupKernel(const csim_ir& ir, const AssemblyPlan& ap, const std
       // guard band, where the faithful kernel (which takes the root) has the last word.  Saves the 22-instruction
       // v_rsq_f64 sequence on the critical path of every pass.
       << (guard ? std::string() : in + "const double err = sqrt(ss);\n");
+    const std::string ballot = in + "const bool pv = (__ballot(GRP_PIVOTS_BAD) & rowBits) != 0ull;\n";
+    auto emitBookkeeping = [&]() {
+        o << (multi || coverBallot ? std::string() : ballot)
+          << in << "// branch-free bookkeeping (everything here is uniform within a group of 16 lanes)\n"
+          << in << "const bool good = active && !pv && (ss < 1.0e300);      // the solve stands: take the damped update\n"
+          << in << (guard ? "const bool conv = ss < " + lit(K.tran_tol * K.tran_tol) : "const bool conv = err < " + lit(K.tran_tol)) << ";\n"
+          << in << "const bool slow = !conv && iter >= " << (slowIters - 1) << ";                 // slow step: plan.hpp slowStepIters\n";
+        if (guard)
+            // near-threshold guard: how close did `err < tol` (tanalisis.cpp:369) come to a tie in this step?  Two
+            // instructions per pass; everything else happens once per step, below.  (Passes after a group has converged
+            // are included: they can only raise a false alarm, which costs a verification and changes nothing.)
+            o << in << (gopt.nearForm == 0
+                        ? "nearMin = fmin(nearMin, fabs(ss - " + lit(K.tran_tol * K.tran_tol) + "));\n"
+                        : "nearAny = nearAny || (ss > " + lit(K.tran_tol * K.tran_tol * (1.0 - 2.0 * gopt.nearBand)) + " && ss < " + lit(K.tran_tol * K.tran_tol * (1.0 + 2.0 * gopt.nearBand)) + ");\n");
+        o << in << "viol = viol || (active && !good) || (good && slow);\n"
+          << in << "it += good ? 1 : 0;\n";
+        for (int s = 0; s < S; ++s) o << in << "xo" << s << " = good ? xn" << s << " : xo" << s << ";\n";
+        o << in << "active = good && !conv && !slow;\n";
+    };
+    // cover_mos: the ballot of the pivot checks (2) or the whole bookkeeping (1) needs neither the MOSFET inputs nor the
+    // stamps, so it can run with the norm under the gather of the MOSFET inputs (one LDS round trip behind the write of
+    // the iterate) instead of under the staging reads.  (With several solve bodies the ballots are part of the bodies.)
+    if (coverMos) emitBookkeeping();
+    if (coverBallot) o << ballot;
     if (piped) {
-        o << in << "__builtin_amdgcn_sched_barrier(0);      // the norm above ran under the reads of the MOSFET inputs\n";
+        o << in << "__builtin_amdgcn_sched_barrier(0);      // the " << (coverMos ? "norm and the bookkeeping" : coverBallot ? "norm and the pivot checks' ballot" : "norm") << " above ran under the reads of the MOSFET inputs\n";
         emitMos(in);
-        for (int r = 0; r < nStage; ++r) o << in << "sv" << r << " = ST[" << r * G << " + g];\n";
-        o << in << "__builtin_amdgcn_sched_barrier(0);      // the bookkeeping below runs under the reads of the staging rows\n";
+        for (int r : readOrder) o << in << "sv" << r << " = ST[" << r * G << " + g];\n";
+        o << in << "__builtin_amdgcn_sched_barrier(0);      // " << (coverMos ? "the staging reads are issued here" : "the bookkeeping below runs under the reads of the staging rows") << "\n";
     }
-    o << (multi ? std::string() : in + "const bool pv = (__ballot(GRP_PIVOTS_BAD) & rowBits) != 0ull;\n")
-      << in << "// branch-free bookkeeping (everything here is uniform within a group of 16 lanes)\n"
-      << in << "const bool good = active && !pv && (ss < 1.0e300);      // the solve stands: take the damped update\n"
-      << in << (guard ? "const bool conv = ss < " + lit(K.tran_tol * K.tran_tol) : "const bool conv = err < " + lit(K.tran_tol)) << ";\n"
-      << in << "const bool slow = !conv && iter >= " << (slowIters - 1) << ";                 // slow step: plan.hpp slowStepIters\n";
-    if (guard)
-        // near-threshold guard: how close did `err < tol` (tanalisis.cpp:369) come to a tie in this step?  Two
-        // instructions per pass; everything else happens once per step, below.  (Passes after a group has converged
-        // are included: they can only raise a false alarm, which costs a verification and changes nothing.)
-        o << in << (gopt.nearForm == 0
-                    ? "nearMin = fmin(nearMin, fabs(ss - " + lit(K.tran_tol * K.tran_tol) + "));\n"
-                    : "nearAny = nearAny || (ss > " + lit(K.tran_tol * K.tran_tol * (1.0 - 2.0 * gopt.nearBand)) + " && ss < " + lit(K.tran_tol * K.tran_tol * (1.0 + 2.0 * gopt.nearBand)) + ");\n");
-    o << in << "viol = viol || (active && !good) || (good && slow);\n"
-      << in << "it += good ? 1 : 0;\n";
-    for (int s = 0; s < S; ++s) o << in << "xo" << s << " = good ? xn" << s << " : xo" << s << ";\n";
-    // the empty asm pins the loads of the next iteration's MOSFET inputs (and staging rows) to this side of the loop's
-    // back edge (the compiler otherwise sinks them to the head of the next iteration, in front of what needs them)
-    o << in << "active = good && !conv && !slow;\n"
-      << in << "__builtin_amdgcn_sched_barrier(0);\n";
-    if (piped) {
+    if (!coverMos) emitBookkeeping();
+    o << in << "__builtin_amdgcn_sched_barrier(0);\n";
+    if (waitAtUse) {
+        // The staging reads stay on this side of the loop's back edge, but nothing here waits for them: the statement
+        // below has no operands, it only keeps the compiler from merging the loads with the prologue's into one load at
+        // the head of the next pass.  Their waits fall where the next pass's elimination first adds each row (partial
+        // lgkmcnt counts, in the order the reads were issued in).
+        o << in << "asm volatile(\"\" ::: \"memory\");\n";
+    } else if (piped) {
+        // the empty asm pins the loads of the next iteration's staging rows to this side of the loop's back edge (the
+        // compiler otherwise sinks them to the head of the next iteration, in front of what needs them); as its operands,
+        // the rows have all landed here
         for (int r0 = 0; r0 < nStage; r0 += 12) {
             o << in << "asm volatile(\"\" :";
             for (int r = r0; r < std::min(nStage, r0 + 12); ++r) o << (r > r0 ? ", " : " ") << "\"+v\"(sv" << r << ")";

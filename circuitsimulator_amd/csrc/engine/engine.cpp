@@ -1231,7 +1231,7 @@ static int buildAndLoadScheduled(csim_engine* eng, const csim::ScheduleSet& sch)
     const int N = ir->n_unknowns;
     const unsigned long long topo = csim::scheduleHash(*ir, csim::PivotSchedule::identity(N));
     // generator options of this engine's JIT (option jit_gen_opts: "key=value,key=value"; part of the library's hash)
-    csim::GeneratorOptions gopt;
+    csim::GeneratorOptions gopt = csim::GeneratorOptions::engineDefaults();
     for (std::size_t i = 0; i < eng->cfg.jitGenOpts.size();) {
         std::size_t e = eng->cfg.jitGenOpts.find(',', i);
         if (e == std::string::npos) e = eng->cfg.jitGenOpts.size();

@@ -465,6 +465,39 @@ bool optimizeGroupPlacement(const csim_ir& ir, const AssemblyPlan& ap, const std
 }
 
 // ---------------------------------------------------------------- interpreter
+std::vector<int> stageFirstUse(const GroupPlan& gp)
+{
+    const int N = gp.N, S = gp.S;
+    std::vector<std::vector<int>> fu(static_cast<std::size_t>(S), std::vector<int>(static_cast<std::size_t>(N + 1), N));
+    for (int k = N - 1; k >= 0; --k) {
+        const GroupPlan::Column& col = gp.cols[static_cast<std::size_t>(k)];
+        fu[static_cast<std::size_t>(col.pivSlot)][static_cast<std::size_t>(k)] = k;
+        for (int s : col.lSlots) fu[static_cast<std::size_t>(s)][static_cast<std::size_t>(k)] = k;
+        for (const GroupPlan::Check& c : col.checks) fu[static_cast<std::size_t>(c.slot)][static_cast<std::size_t>(k)] = k;
+        for (const GroupPlan::UEntry& u : col.u) {
+            fu[static_cast<std::size_t>(col.pivSlot)][static_cast<std::size_t>(u.j)] = k;
+            for (int s : col.lSlots) fu[static_cast<std::size_t>(s)][static_cast<std::size_t>(u.j)] = k;
+        }
+    }
+    std::vector<int> firstUse(gp.stageRows.size(), N);
+    for (std::size_t r = 0; r < gp.stageRows.size(); ++r)
+        firstUse[r] = fu[static_cast<std::size_t>(gp.stageRows[r].s)][static_cast<std::size_t>(gp.stageRows[r].j)];
+    return firstUse;
+}
+
+std::vector<int> stageReadOrder(const GroupPlan& gp)
+{
+    const std::vector<int> firstUse = stageFirstUse(gp);
+    std::vector<int> order(gp.stageRows.size());
+    for (std::size_t i = 0; i < order.size(); ++i) order[i] = static_cast<int>(i);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+        const std::size_t ua = static_cast<std::size_t>(a), ub = static_cast<std::size_t>(b);
+        if (firstUse[ua] != firstUse[ub]) return firstUse[ua] < firstUse[ub];
+        return (gp.stageRows[ua].j == gp.N) > (gp.stageRows[ub].j == gp.N);
+    });
+    return order;
+}
+
 void interpretGroupPlan(const GroupPlan& gp, const AssemblyPlan& ap, const csim_ir& ir, const double* T, double eps,
                         double* x, bool* violated, bool* planError)
 {

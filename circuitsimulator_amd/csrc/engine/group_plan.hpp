@@ -117,6 +117,13 @@ bool buildGroupPlan(const csim_ir& ir, const AssemblyPlan& ap, const PivotSchedu
 bool optimizeGroupPlacement(const csim_ir& ir, const AssemblyPlan& ap, const std::vector<PivotSchedule>& schedules, int lanes,
                             GroupPlan& placement, double* costBefore = nullptr, double* costAfter = nullptr);
 
+// Column of the solve whose code first reads or writes the class of staging row r (N: not before the substitution).
+std::vector<int> stageFirstUse(const GroupPlan& gp);
+// The staging rows in the order in which one solve needs them: by column of first use, the right-hand-side rows of a
+// column first.  The LDS returns a wave's reads in issue order, so reads issued in this order can be waited for one by
+// one, each where the elimination gets to it (generator option wait_at_use).
+std::vector<int> stageReadOrder(const GroupPlan& gp);
+
 // Host interpreter of the plan, lane by lane, for ONE system: T[nTerms] are the term values of
 // plan.hpp.  Writes x[N]; *violated = a pivot check failed; *planError = a lane the kernel's all-lane
 // candidate test would see is neither a candidate, masked, nor an exact zero.  Used by the self test

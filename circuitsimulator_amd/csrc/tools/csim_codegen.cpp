@@ -2,7 +2,8 @@
 //
 //   csim_codegen <netlist.sp> <schedule-file|-> <out.hip>      writes HIP source, prints the hash
 //   csim_codegen --hash <netlist.sp> <schedule-file|->          prints the hash only
-//   csim_codegen --opt key=value ... (before the other arguments): generator options
+//   csim_codegen [--engine-defaults] --opt key=value ... (before the other arguments): generator options, on top of the
+//     generator's own defaults or of those the engine generates with (GeneratorOptions::engineDefaults)
 //     (barrier_every=3, sweep=0,16,32 -- tuning aids, part of the library's hash)
 //
 // The schedule file holds the partial-pivot row swaps of the transient
@@ -126,6 +127,11 @@ static int selftestGroup(const csim_ir* ir, const csim::AssemblyPlan& ap, const 
 int main(int argc, char** argv)
 {
     csim::GeneratorOptions gopt;
+    if (argc >= 2 && std::string(argv[1]) == "--engine-defaults") {      // what the engine and the shipped libraries start from
+        gopt = csim::GeneratorOptions::engineDefaults();
+        ++argv;
+        --argc;
+    }
     while (argc >= 3 && std::string(argv[1]) == "--opt") {
         if (!gopt.set(argv[2])) { std::cerr << "unknown generator option " << argv[2] << "\n"; return 1; }
         argv += 2;
