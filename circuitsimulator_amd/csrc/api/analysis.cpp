@@ -104,6 +104,23 @@ BatchNoiseResult BatchEngine::noise(const std::vector<double>& params, int B, co
     return r;
 }
 
+BatchDistoResult BatchEngine::disto(const std::vector<double>& params, int B, const std::vector<double>& freqs, int outP,
+                                    int outM, bool wantPhasors)
+{
+    BatchDistoResult r;
+    r.freqs = freqs;
+    r.nDevices = csim_netlist_num_disto_devices(nl_);
+    const std::size_t FB = static_cast<std::size_t>(B) * freqs.size();
+    if (wantPhasors) r.h.assign(FB * 3 * static_cast<std::size_t>(numUnknowns()), std::complex<double>());
+    r.hd.assign(FB * 2, 0.0);
+    r.status.assign(static_cast<std::size_t>(B), 0);
+    if (csim_disto_batch(eng_, params.empty() ? nullptr : params.data(), B, freqs.data(), static_cast<int>(freqs.size()),
+                         outP, outM, wantPhasors ? reinterpret_cast<double*>(r.h.data()) : nullptr, r.hd.data(), nullptr,
+                         r.status.data()) != CSIM_OK)
+        fail("csim_disto_batch");
+    return r;
+}
+
 BatchSpResult BatchEngine::sp(const std::vector<double>& params, int B, const std::vector<double>& freqs, bool wantS)
 {
     BatchSpResult r;

@@ -66,6 +66,14 @@ struct BatchSpNoiseResult {
     std::vector<uint32_t> status;                 // DC and LU bits (CSIM_ST_LU_TINY_PIVOT: a singular frequency)
 };
 
+struct BatchDistoResult {
+    std::vector<double> freqs;                    // [F] Hz
+    int nDevices = 0;                             // M non-linear devices (csim_netlist_disto_device order)
+    std::vector<std::complex<double>> h;          // [B][F][3][N]: the phasors of order 1, 2, 3 (empty unless asked for)
+    std::vector<double> hd;                       // [B][F][2]: HD2, HD3 at the output
+    std::vector<uint32_t> status;                 // DC and LU bits (CSIM_ST_LU_TINY_PIVOT: a singular order)
+};
+
 // One engine per (circuit, GPU).  Throws std::runtime_error when no HIP
 // device is usable: there is no CPU path.
 class BatchEngine {
@@ -108,6 +116,11 @@ public:
     // NF / Fmin / Rn / Yopt for two ports.  freqs empty: the .SP card (an error when the netlist has none).
     BatchSpNoiseResult spNoise(const std::vector<double>& params, int B, const std::vector<double>& freqs,
                                double tempK = 300.15);
+
+    // Single-tone harmonic distortion (csim_disto_batch, include/csim.h): DC operating point, then three factorisations
+    // per frequency, at w, 2 w and 3 w.  Output V(outP) - V(outM) (equations; outM = -1: ground).
+    BatchDistoResult disto(const std::vector<double>& params, int B, const std::vector<double>& freqs, int outP,
+                           int outM = -1, bool wantPhasors = false);
 
     // the transient of instance `instance` of params ([B][P], empty = nominal) as the reference's CSV
     // (src/tanalisis.cpp:189-231); probeEq empty: the netlist's .PLOTNV/.PRINT probes when `sim` names any, else

@@ -423,6 +423,7 @@ void NetlistParser::dotCard(const Statement& st)
     else if (head == ".ac")     acCard(st);
     else if (head == ".noise")  noiseCard(st);
     else if (head == ".sp")     spCard(st);
+    else if (head == ".disto")  distoCard(st);
     else if (head == ".print")  printCard(st);
     else if (head == ".model")  modelCard(st);
     else if (head == ".hb")     hbCard(st);
@@ -563,6 +564,44 @@ void NetlistParser::noiseCard(const Statement& st)
     }
     cfg.enabled = true;
     sim.noise = cfg;
+}
+
+// .DISTO V(out[,ref]) {LIN|DEC|OCT} npoints fstart fstop   (single tone: a further token, ngspice's f2overf1, is an error)
+void NetlistParser::distoCard(const Statement& st)
+{
+    // the output may be written with blanks inside its parentheses: join tokens up to the closing one
+    std::vector<std::string> t;
+    for (std::size_t i = 0; i < st.tokens.size(); ++i) {
+        if (i >= 2 && t.size() == 2 && t[1].find('(') != std::string::npos && t[1].find(')') == std::string::npos)
+            t[1] += st.tokens[i];
+        else
+            t.push_back(st.tokens[i]);
+    }
+    const std::string sweep = t.size() > 2 ? toLower(t[2]) : std::string();
+    if (t.size() != 6 || (sweep != "lin" && sweep != "oct" && sweep != "dec")) {
+        std::cerr << "Line " << st.lineNo << ": invalid .DISTO syntax: " << st.raw << "\n";
+        return;
+    }
+    const ProbeSpec out = probeFromToken(t[1]);
+    if ((out.kind != ProbeKind::NodeVoltage && out.kind != ProbeKind::DiffVoltage) || out.node1.empty()) {
+        std::cerr << "Line " << st.lineNo << ": .DISTO output must be V(node) or V(node,ref): " << st.raw << "\n";
+        return;
+    }
+    DistoConfig cfg;
+    cfg.outNode = out.node1;
+    cfg.refNode = out.node2;
+    cfg.sweepType = sweep == "lin" ? AcSweepType::LIN : (sweep == "oct" ? AcSweepType::OCT : AcSweepType::DEC);
+    try {
+        cfg.nPoints = std::stoi(t[3]);
+        cfg.fstart  = parseSpiceNumber(t[4]);
+        cfg.fstop   = parseSpiceNumber(t[5]);
+    } catch (const std::exception& e) {
+        std::cerr << "Line " << st.lineNo << ": cannot parse .DISTO arguments: " << e.what()
+                  << " in '" << st.raw << "'\n";
+        return;
+    }
+    cfg.enabled = true;
+    sim.disto = cfg;
 }
 
 // .HB f0 nharm

@@ -50,6 +50,7 @@ private:
     void dcCard(const Statement& st);
     void acCard(const Statement& st);
     void noiseCard(const Statement& st);
+    void distoCard(const Statement& st);
     void spCard(const Statement& st);
     void hbCard(const Statement& st);
     void printCard(const Statement& st);

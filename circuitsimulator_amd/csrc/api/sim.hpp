@@ -165,6 +165,15 @@ struct SpConfig {
     double fstart = 0.0, fstop = 0.0;
 };
 
+// .DISTO V(out[,ref]) {DEC|OCT|LIN} n fstart fstop -- names as written; netlist_capi.cpp resolves them
+struct DistoConfig {
+    bool enabled = false;
+    std::string outNode, refNode;   // refNode empty or "0": ground
+    AcSweepType sweepType = AcSweepType::DEC;
+    int nPoints = 0;
+    double fstart = 0.0, fstop = 0.0;
+};
+
 struct HbConfig {
     bool enabled = false;
     double f0 = 0.0;
@@ -191,6 +200,7 @@ public:
     AcConfig ac;
     NoiseConfig noise;
     SpConfig sp;
+    DistoConfig disto;
     HbConfig hb;
     std::vector<PrintCommand> printCommands;
 

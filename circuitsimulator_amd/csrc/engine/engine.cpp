@@ -320,6 +320,24 @@ int csim_engine_create(const csim_netlist* nl, int32_t device, csim_engine** out
         eng->noiseFstop = nc.fstop;
     }
     if (!rc) {
+        const std::vector<csim::DistoDevice> dev = csim::distoDevices(c);
+        std::vector<int32_t> el, td, tg, ts;
+        for (const csim::DistoDevice& m : dev) { el.push_back(m.elem); td.push_back(m.d); tg.push_back(m.g); ts.push_back(m.s); }
+        eng->nDistoDev = static_cast<int>(dev.size());
+        rc = upload(eng, el, &eng->dDistoElem);
+        if (!rc) rc = upload(eng, td, &eng->dDistoD);
+        if (!rc) rc = upload(eng, tg, &eng->dDistoG);
+        if (!rc) rc = upload(eng, ts, &eng->dDistoS);
+        const DistoConfig& dc = nl->sim.disto;
+        eng->distoEnabled = dc.enabled ? 1 : 0;
+        eng->distoOutP = nl->distoOutP;
+        eng->distoOutM = nl->distoOutM;
+        eng->distoSweep = dc.sweepType == AcSweepType::DEC ? 0 : (dc.sweepType == AcSweepType::OCT ? 1 : 2);
+        eng->distoPoints = dc.nPoints;
+        eng->distoFstart = dc.fstart;
+        eng->distoFstop = dc.fstop;
+    }
+    if (!rc) {
         for (const csim::Port& p : nl->ports) { eng->spPortEq.push_back(p.branchEq); eng->spZ0.push_back(p.z0); }
         eng->spPortError = nl->portError;
         const SpConfig& sc = nl->sim.sp;
@@ -361,6 +379,7 @@ void csim_engine_destroy(csim_engine* eng)
     if (eng->dAcSys) (void)hipFree(eng->dAcSys);
     if (eng->dAcWork) (void)hipFree(eng->dAcWork);
     if (eng->dNoisePsd) (void)hipFree(eng->dNoisePsd);
+    if (eng->dDistoCoef) (void)hipFree(eng->dDistoCoef);
     if (eng->schedLib) dlclose(eng->schedLib);
     delete eng;
 }

@@ -132,6 +132,15 @@ struct csim_engine {
     double* dNoisePsd = nullptr;
     size_t noisePsdCap = 0;                // doubles
 
+    // Distortion analysis: the netlist's .DISTO card (resolved), the MOSFET list (element, drain, gate, source
+    // equations; uploaded once) and the coefficient scratch of one chunk, used when the caller does not ask for them
+    int distoEnabled = 0, distoOutP = -2, distoOutM = -1, distoSweep = 0, distoPoints = 0;
+    double distoFstart = 0.0, distoFstop = 0.0;
+    int nDistoDev = 0;
+    const int32_t *dDistoElem = nullptr, *dDistoD = nullptr, *dDistoG = nullptr, *dDistoS = nullptr;
+    double* dDistoCoef = nullptr;
+    size_t distoCoefCap = 0;               // doubles
+
     // S-parameter analysis: the netlist's .SP card and its ports in port order (branch equation, Z0); spPortError
     // says what is wrong with the PORTNUM numbering, if anything
     int spEnabled = 0, spSweep = 0, spPoints = 0;

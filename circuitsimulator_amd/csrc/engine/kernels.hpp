@@ -166,6 +166,27 @@ struct SpNoiseArgs {
 };
 hipError_t launchSpNoiseSweep(int which, const SpNoiseArgs& a, hipStream_t stream);
 
+// Distortion analysis (kernels_disto.hip) on the systems launchAcAssemble leaves: three factorisations per (instance,
+// frequency), at w, 2 w and 3 w.  Coefficient k of device m of chunk instance c is at
+// coef[(m * 7 + k) * coefStride + coefOff + c].  Device terminals are checked by the callers, the output pair by the
+// launcher: they index LDS.  Wave and packed shapes only.
+struct DistoArgs {
+    int N, F, M, B, b0, Bc;
+    int outP, outM;                     // v = x[outP] - x[outM] (-1: ground)
+    double eps;
+    const double* sys;
+    const double* omega;
+    const int32_t *devD, *devG, *devS;  // [M] drain, gate, source equations (-1 ground)
+    const double* coef;
+    size_t coefStride, coefOff;
+    double* h;                          // [F][3][N][B] complex or null: x1, x2, x3
+    double* hd;                         // [F][2][B]: HD2, HD3
+    uint32_t* status;                   // [B], OR-ed
+};
+hipError_t launchDistoCoef(const GenPlan& pl, const int32_t* dDevElem, int M, const double* dParams, int B, int b0, int Bc,
+                           const double* dXop, double* dCoef, size_t coefStride, size_t coefOff, hipStream_t stream);
+hipError_t launchDistoSweep(int which, const DistoArgs& a, hipStream_t stream);
+
 // layout helpers (transpose.hip): [rows][cols] <-> [cols][rows] of doubles
 hipError_t launchTranspose(const double* dIn, double* dOut, int rows, int cols, hipStream_t stream);
 

@@ -56,6 +56,18 @@ int finishNetlist(csim_netlist* nl)
             if (toLower(nl->ckt.elements[e]->getName()) == toLower(nc.srcName)) { nl->noiseSrcElem = static_cast<int>(e); break; }
     }
 
+    // .DISTO card: names -> equation indices
+    if (nl->sim.disto.enabled) {
+        const DistoConfig& dc = nl->sim.disto;
+        auto eqOf = [&](const std::string& name) {
+            if (name == "0") return -1;
+            const auto hit = nl->ckt.nodeNameToId.find(name);
+            return hit == nl->ckt.nodeNameToId.end() ? -2 : nl->ckt.nodes[static_cast<std::size_t>(hit->second)].eqIndex;
+        };
+        nl->distoOutP = eqOf(dc.outNode);
+        nl->distoOutM = dc.refNode.empty() ? -1 : eqOf(dc.refNode);
+    }
+
     // PORTNUM tokens: the ports in port order
     nl->portError = csim::portList(nl->cir, nl->ports);
     if (!nl->portError.empty()) std::cerr << nl->portError << "\n";
@@ -201,6 +213,35 @@ int csim_netlist_noise_source(const csim_netlist* nl, int32_t i, int32_t* elem, 
     if (elem) *elem = src[static_cast<std::size_t>(i)].elem;
     if (eq_a) *eq_a = src[static_cast<std::size_t>(i)].a;
     if (eq_b) *eq_b = src[static_cast<std::size_t>(i)].b;
+    return CSIM_OK;
+}
+
+int csim_netlist_disto(const csim_netlist* nl, int32_t* enabled, int32_t* out_p_eq, int32_t* out_m_eq, int32_t* sweep,
+                       int32_t* n_points, double* fstart, double* fstop)
+{
+    if (!nl) return CSIM_ERR_ARG;
+    const DistoConfig& a = nl->sim.disto;
+    if (enabled)  *enabled = a.enabled ? 1 : 0;
+    if (out_p_eq) *out_p_eq = nl->distoOutP;
+    if (out_m_eq) *out_m_eq = nl->distoOutM;
+    if (sweep)    *sweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
+    if (n_points) *n_points = a.nPoints;
+    if (fstart)   *fstart = a.fstart;
+    if (fstop)    *fstop = a.fstop;
+    return CSIM_OK;
+}
+
+int csim_netlist_num_disto_devices(const csim_netlist* nl) { return nl ? static_cast<int>(csim::distoDevices(nl->cir).size()) : 0; }
+
+int csim_netlist_disto_device(const csim_netlist* nl, int32_t i, int32_t* elem, int32_t* eq_d, int32_t* eq_g, int32_t* eq_s)
+{
+    if (!nl) return CSIM_ERR_ARG;
+    const std::vector<csim::DistoDevice> dev = csim::distoDevices(nl->cir);
+    if (i < 0 || i >= static_cast<int32_t>(dev.size())) { csim::setError("csim_netlist_disto_device: bad index"); return CSIM_ERR_ARG; }
+    if (elem) *elem = dev[static_cast<std::size_t>(i)].elem;
+    if (eq_d) *eq_d = dev[static_cast<std::size_t>(i)].d;
+    if (eq_g) *eq_g = dev[static_cast<std::size_t>(i)].g;
+    if (eq_s) *eq_s = dev[static_cast<std::size_t>(i)].s;
     return CSIM_OK;
 }
 

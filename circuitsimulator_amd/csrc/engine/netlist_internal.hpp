@@ -21,6 +21,8 @@ struct csim_netlist {
     std::string csvHeader;
     // .NOISE card resolved to indices: output equations (-1 ground, -2 unknown node), input source element (-1 none)
     int noiseOutP = -2, noiseOutM = -1, noiseSrcElem = -1;
+    // .DISTO card resolved to indices: output equations (-1 ground, -2 unknown node)
+    int distoOutP = -2, distoOutM = -1;
     // the ports (PORTNUM) in port order, or what is wrong with their numbering
     std::vector<csim::Port> ports;
     std::string portError;
@@ -39,6 +41,19 @@ inline std::vector<NoiseSource> noiseSources(const CircuitIR& c)
         const int32_t* q = c.eq.data() + 4 * e;
         if (c.kind[e] == CSIM_R) out.push_back({static_cast<int32_t>(e), q[0], q[1]});
         else if (c.kind[e] == CSIM_NMOS || c.kind[e] == CSIM_PMOS) out.push_back({static_cast<int32_t>(e), q[0], q[2]});
+    }
+    return out;
+}
+
+// Non-linear devices of a circuit, in element order (include/csim.h "Distortion analysis"): every MOSFET with its
+// drain, gate and source equations, -1 for ground.
+struct DistoDevice { int32_t elem, d, g, s; };
+inline std::vector<DistoDevice> distoDevices(const CircuitIR& c)
+{
+    std::vector<DistoDevice> out;
+    for (std::size_t e = 0; e < c.kind.size(); ++e) {
+        const int32_t* q = c.eq.data() + 4 * e;
+        if (c.kind[e] == CSIM_NMOS || c.kind[e] == CSIM_PMOS) out.push_back({static_cast<int32_t>(e), q[0], q[1], q[2]});
     }
     return out;
 }

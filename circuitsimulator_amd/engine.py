@@ -88,6 +88,33 @@ class Netlist:
         return out
 
     @property
+    def disto(self):
+        """The .DISTO card: None, or (out_p_eq, out_m_eq, sweep, n_points, fstart, fstop); out_m_eq -1 = ground."""
+        v = [C.c_int32() for _ in range(5)]
+        f0, f1 = C.c_double(), C.c_double()
+        capi.check(capi.lib().csim_netlist_disto(self._h, *[C.byref(x) for x in v], C.byref(f0), C.byref(f1)))
+        en, op, om, sw, npt = [x.value for x in v]
+        return (op, om, AC_SWEEPS[sw], npt, f0.value, f1.value) if en else None
+
+    def disto_freqs(self):
+        """Frequency grid of the .DISTO card (numpy, Hz)."""
+        card = self.disto
+        if card is None:
+            raise capi.CsimError(capi.CSIM_ERR_CONFIG, "the netlist has no .DISTO card")
+        return ac_freqs(*card[2:])
+
+    @property
+    def disto_devices(self):
+        """The non-linear devices (MOSFETs) in element order: [(element index, eq_d, eq_g, eq_s)], -1 = ground."""
+        L = capi.lib()
+        out = []
+        for i in range(L.csim_netlist_num_disto_devices(self._h)):
+            e, d, g, s = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+            capi.check(L.csim_netlist_disto_device(self._h, i, C.byref(e), C.byref(d), C.byref(g), C.byref(s)))
+            out.append((e.value, d.value, g.value, s.value))
+        return out
+
+    @property
     def ports(self):
         """The ports (V sources with PORTNUM k [Z0 r]) in port order: [(element index, branch equation, Z0)].
         Raises CsimError(CSIM_ERR_CONFIG) when the numbering has a gap or a duplicate or there are more than 4."""
@@ -432,6 +459,61 @@ class Engine:
         return dict(freqs=f, onoise=on, gain=g[..., 0] + 1j * g[..., 1] if g is not None else None, contrib=con, psd=ps,
                     status=st)
 
+    def _disto_args(self, freqs, out):
+        """-> (freqs, out_p, out_m); None takes the .DISTO card's value"""
+        card = self.netlist.disto
+        if freqs is None:
+            f = self.netlist.disto_freqs()
+        else:
+            f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        if out is None:
+            if card is None:
+                raise capi.CsimError(capi.CSIM_ERR_CONFIG, "no output given and the netlist has no .DISTO card")
+            out_p, out_m = card[0], card[1]
+        elif isinstance(out, (tuple, list)):
+            out_p, out_m = int(out[0]), int(out[1])
+        else:
+            out_p, out_m = int(out), -1
+        return f, out_p, out_m
+
+    def disto(self, params, x_op, freqs=None, out=None, want_h=True, coef=False, status=None):
+        """Single-tone distortion sweep of the batch around the operating points x_op (device [N][B], from dc());
+        csim_disto_batch_dev.  freqs: Hz; out: equation or (out_p, out_m), -1 = ground -- None takes each from the
+        .DISTO card.
+        -> dict(freqs, h complex [F][3][N][B] (x1, x2, x3) or None, hd [F][2][B] (HD2, HD3), coef [M][7][B] or None,
+                status [B]); device tensors; status is OR-ed into `status` when given."""
+        torch = _torch()
+        B = params.shape[1]
+        f, out_p, out_m = self._disto_args(freqs, out)
+        M = len(self.netlist.disto_devices)
+        dev = self._dev()
+        h = torch.zeros((len(f), 3, self.N, B, 2), dtype=torch.float64, device=dev) if want_h else None
+        hd = torch.zeros((len(f), 2, B), dtype=torch.float64, device=dev)
+        cf = torch.zeros((M, 7, B), dtype=torch.float64, device=dev) if coef else None
+        st = status if status is not None else torch.zeros(B, dtype=torch.int32, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None     # noqa: E731
+        capi.check(capi.lib().csim_disto_batch_dev(self._h, params.data_ptr(), B, x_op.data_ptr(), f.ctypes.data, len(f),
+                                                   out_p, out_m, ptr(h), hd.data_ptr(), ptr(cf), st.data_ptr(),
+                                                   self._stream()))
+        return dict(freqs=f, h=torch.view_as_complex(h) if h is not None else None, hd=hd, coef=cf, status=st)
+
+    def disto_host(self, params=None, B=1, freqs=None, out=None, want_h=True, coef=False):
+        """DC operating point + distortion sweep (csim_disto_batch): numpy, instance-major.
+        -> dict(freqs, h complex [B][F][3][N] or None, hd [B][F][2], coef [B][M][7] or None, status [B])"""
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=np.float64)
+            B = params.shape[0]
+        f, out_p, out_m = self._disto_args(freqs, out)
+        M = len(self.netlist.disto_devices)
+        h = np.zeros((B, len(f), 3, self.N), dtype=np.complex128) if want_h else None
+        hd = np.zeros((B, len(f), 2))
+        cf = np.zeros((B, M, 7)) if coef else None
+        st = np.zeros(B, dtype=np.uint32)
+        ptr = lambda a: a.ctypes.data if a is not None else None    # noqa: E731
+        capi.check(capi.lib().csim_disto_batch(self._h, ptr(params), B, f.ctypes.data, len(f), out_p, out_m, ptr(h),
+                                               hd.ctypes.data, ptr(cf), st.ctypes.data))
+        return dict(freqs=f, h=h, hd=hd, coef=cf, status=st)
+
     def sp(self, params, x_op, freqs=None, want_s=True, status=None):
         """S-parameter sweep of the batch around the operating points x_op (device [N][B], from dc());
         csim_sp_batch_dev.  freqs: Hz, None = the .SP card.
@@ -767,6 +849,34 @@ def noise_solve_batch(G, Cm, out, src_a, src_b, psd, omega, gain_in=None, kernel
         onoise.ctypes.data, contrib.ctypes.data, gain.ctypes.data if gain is not None else None,
         y.ctypes.data if y is not None else None, flags.ctypes.data))
     return dict(onoise=onoise, contrib=contrib, gain=gain, y=y, flags=flags)
+
+
+def disto_solve_batch(G, Cm, J, dev_d, dev_g, dev_s, coef, out, omega, kernel="auto", device=0, want_h=True):
+    """The distortion kernels on systems and device tables given directly (csim_disto_solve_batch): (G + j k w C) x_k
+    = rhs_k for k = 1, 2, 3.  G, Cm [B][n][n] real; J [B][n] complex; devices dev_d, dev_g, dev_s [M] (equations, -1 =
+    ground) with coef [B][M][7]; out = (out_p, out_m), -1 = ground; omega [F] rad/s; kernel auto | wave | packed
+    (block is refused: CSIM_ERR_UNSUPPORTED).
+    -> dict(h complex [B][F][3][n] or None, hd [B][F][2], flags [B])"""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    Cm = np.ascontiguousarray(Cm, dtype=np.float64)
+    J = np.ascontiguousarray(J, dtype=np.complex128)
+    omega = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
+    dev_d = np.ascontiguousarray(dev_d, dtype=np.int32).reshape(-1)
+    dev_g = np.ascontiguousarray(dev_g, dtype=np.int32).reshape(-1)
+    dev_s = np.ascontiguousarray(dev_s, dtype=np.int32).reshape(-1)
+    B, n = J.shape
+    M, F = len(dev_d), len(omega)
+    if len(dev_g) != M or len(dev_s) != M:
+        raise ValueError("dev_d, dev_g and dev_s differ in length")
+    coef = np.ascontiguousarray(coef, dtype=np.float64).reshape(B, M, 7)
+    h = np.zeros((B, F, 3, n), dtype=np.complex128) if want_h else None
+    hd = np.zeros((B, F, 2))
+    flags = np.zeros(B, dtype=np.uint32)
+    capi.check(capi.lib().csim_disto_solve_batch(
+        device, n, B, G.ctypes.data, Cm.ctypes.data, J.ctypes.data, M, dev_d.ctypes.data, dev_g.ctypes.data,
+        dev_s.ctypes.data, coef.ctypes.data, int(out[0]), int(out[1]), omega.ctypes.data, F, _AC_KERNELS[kernel],
+        h.ctypes.data if h is not None else None, hd.ctypes.data, flags.ctypes.data))
+    return dict(h=h, hd=hd, flags=flags)
 
 
 def sp_solve_batch(G, Cm, J, omega, kernel="auto", device=0, port_eq=None, z0=None, want_s=True):

@@ -78,7 +78,7 @@ extern "C" {
 #define CSIM_ERR_HIP          -4   /* a HIP runtime call failed                    */
 #define CSIM_ERR_UNSUPPORTED  -5   /* circuit outside what the kernels cover       */
 #define CSIM_ERR_EMPTY        -6   /* circuit has no unknowns                      */
-#define CSIM_ERR_CONFIG       -7   /* invalid .TRAN / .AC / .NOISE numbers, no AC source, no port */
+#define CSIM_ERR_CONFIG       -7   /* invalid .TRAN / .AC / .NOISE / .DISTO numbers, no AC source, no port */
 
 typedef struct csim_netlist csim_netlist;
 typedef struct csim_engine  csim_engine;
@@ -203,7 +203,7 @@ int  csim_engine_set_kernel(csim_engine* eng, int32_t which);
  *   near_test_rollback (0)                  test aid: every verified near-threshold decision is treated as a
  *                                           mismatch, so the roll-back path runs (results must not change)
  *   hybrid_sync (CSIM_HYBRID_SYNC, 1)       see "Streams" above
- *   ac_kernel (auto)                        AC, noise and S-parameter sweep kernel, auto | wave | packed (test aid) | block
+ *   ac_kernel (auto)                        AC, noise, S-parameter and distortion sweep kernel, auto | wave | packed (test aid) | block
  *                                           (opt-in: AC and noise of up to 1024 unknowns; see csim_ac_batch_dev)
  *   dc_fast (CSIM_DC_FAST, 0)               DC operating points start on the fast generated kernel (FMA
  *                                           contraction, reciprocal pivots; controller decisions within
@@ -458,6 +458,74 @@ int  csim_spnoise_batch(csim_engine* eng, const double* params, int32_t B, const
                         double temp_k, double* y, double* cy, double* nf, double* fmin, double* rn, double* yopt,
                         uint32_t* status);
 
+/* ---- Distortion analysis (.DISTO; single-tone harmonic distortion HD2, HD3 by a Volterra series at the operating
+ *      point: three factorisations per frequency) ----
+ * Card: `.DISTO V(out[,ref]) DEC|OCT|LIN n fstart fstop`, the output as on .NOISE, the grid of csim_ac_freqs.  Single
+ *   tone only: a further token (ngspice's f2overf1) is a card error, reported, the statement dropped.
+ * System.  For instance b and angular frequency w, A(w) = G + j w C is exactly the matrix of "AC analysis" above: the
+ *   same assembly, the same elements left out, tran_gmin.  J is that section's right-hand side: `AC mag [phase]` of the
+ *   netlist's sources, mag a PEAK amplitude that matters here (x2 ~ mag^2, x3 ~ mag^3).  No source with mag != 0:
+ *   CSIM_ERR_CONFIG.
+ * Non-linearity.  The only one of this simulator is the level-1 MOSFET drain current (the Cj0 capacitances are
+ *   constants).  Inside a region it is a polynomial of degree <= 3 in (Vgs, Vds), so its expansion to third order is
+ *   exact.  Devices are the MOSFETs in element order, M per circuit (csim_netlist_disto_device), each with its drain,
+ *   gate and source equations (d, g, s), -1 for ground.
+ * Coefficients, seven per (device, instance), computed once at x_op.  With mos_eval's own quantities and comparisons
+ *   (p = -1.0 for a PMOS, else 1.0; Vgs = p * (Vg - Vs); Vds = p * (Vd - Vs); on when Vgs > Vth && Vds >= 0.0;
+ *   Vov = Vgs - Vth; triode when Vds < Vov; factor = 1.0 + lambda * Vds), every product and sum below one operation
+ *   in the order written:
+ *     off, or factor < 0.0 (mos_eval clamps it to 0): all seven +0.0
+ *     saturation  gg = K * factor    gd = (K * Vov) * lambda    ggd = K * lambda    dd = ggg = gdd = ddd = 0.0
+ *     triode      gd = K * factor + (K * Vds) * lambda          dd = 2.0 * ((K * (Vov - Vds)) * lambda) - K * factor
+ *                 gdd = 2.0 * (K * lambda)    ddd = -3.0 * (K * lambda)             gg = ggg = ggd = 0.0
+ *   These are the derivatives of the current in the device's effective coordinates.  In physical coordinates
+ *   (Ug = Vg - Vs, Ud = Vd - Vs, current drain -> source) the three second-order ones are multiplied by p
+ *   (c_gg = p * gg, c_gd = p * gd, c_dd = p * dd: a zero among them is -0.0 for a PMOS), the four third-order ones are
+ *   unchanged (p p^3 = 1).  Order in a coefficient table: c_gg, c_gd, c_dd, c_ggg, c_ggd, c_gdd, c_ddd.
+ * Complex arithmetic.  A product of two complex values is four real products, then one difference (re) and one sum
+ *   (im), as in "AC analysis"; a real factor times a complex value scales re and im, one product each; sums of complex
+ *   values add re and im separately, left to right.  No FMA contraction anywhere.
+ * Order 1.  A(w) x1 = J, the AC solve.
+ * Order 2.  Per device m: Ug = x1[g] - x1[s], Ud = x1[d] - x1[s], ground = (0, 0);
+ *     I2 = 0.5 * ( ((0.5 * c_gg) * (Ug Ug) + c_gd * (Ug Ud)) + (0.5 * c_dd) * (Ud Ud) ).
+ *   Right-hand side: every entry starts at +0.0; the devices are taken in ascending order; each subtracts I2 at d, then
+ *   adds it at s (ground: no entry).  A(2.0 * w) x2 = rhs2.
+ * Order 3.  With Ug2, Ud2 taken from x2 the same way, GG = Ug Ug and DD = Ud Ud:
+ *     a = (((c_ggg / 6.0) * (GG Ug) + (0.5 * c_ggd) * (GG Ud)) + (0.5 * c_gdd) * (Ug DD)) + (c_ddd / 6.0) * (DD Ud)
+ *     b = (c_gg * (Ug Ug2) + c_gd * ((Ug Ud2) + (Ud Ug2))) + c_dd * (Ud Ud2)
+ *     I3 = 0.25 * a + 0.5 * b
+ *   accumulated like I2.  A(3.0 * w) x3 = rhs3.
+ * Outputs.  The three phasor vectors, and for the output V(out_p[, out_m]): v_k = x_k[out_p] - x_k[out_m],
+ *   |z| = sqrt(z.re z.re + z.im z.im), HD2 = |v2| / |v1|, HD3 = |v3| / |v1| (true divisions); +0.0 where |v1| == 0.
+ *   out_p == out_m or out_p < 0: CSIM_ERR_ARG.
+ * Failures.  A column maximum below lu_eps^2 at order k makes x_k and every higher order +0.0 (their HD too) and sets
+ *   CSIM_ST_LU_TINY_PIVOT; the sweep goes on.  All three factorisations are attempted whatever M is, so the flags do
+ *   not depend on the device list.  M == 0 is legal: x2 = x3 = 0.
+ * Circuits of up to 63 unknowns (CSIM_ERR_UNSUPPORTED beyond); ac_kernel=block: CSIM_ERR_UNSUPPORTED (the block shape
+ * covers AC and noise analysis only).  The exact order of every operation: engine/ac_disto.hpp, written once for host
+ * and device.
+ *
+ * Enqueues the sweep; never waits for it; frequency lists as csim_ac_batch_dev (same buffers, same discipline).
+ *   d_h [F][3][N][B] complex (re, im): x1, x2, x3, or NULL    d_hd [F][2][B]: HD2, HD3
+ *   d_coef [M][7][B] or NULL: the coefficients                d_status [B], OR-ed
+ * The engine option ac_kernel picks the kernel as for AC (wave, N <= 63; packed, N <= 32); both give bit-identical
+ * results.                                                                                                        */
+/* .DISTO card: output equations (out_m_eq -1: ground; -2: a node the netlist does not have), the sweep as for .AC */
+int  csim_netlist_disto(const csim_netlist* nl, int32_t* enabled, int32_t* out_p_eq, int32_t* out_m_eq, int32_t* sweep,
+                        int32_t* n_points, double* fstart, double* fstop);
+/* The non-linear devices, in element order: element index and the drain, gate and source equations (-1: ground) */
+int  csim_netlist_num_disto_devices(const csim_netlist* nl);
+int  csim_netlist_disto_device(const csim_netlist* nl, int32_t i, int32_t* elem, int32_t* eq_d, int32_t* eq_g,
+                               int32_t* eq_s);
+int  csim_disto_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int32_t B, const double* d_xop,
+                          const double* freqs, int32_t F, int32_t out_p_eq, int32_t out_m_eq, double* d_h, double* d_hd,
+                          double* d_coef, uint32_t* d_status, void* stream);
+/* DC operating point, then the sweep.  params [B][P] or NULL (nominal); freqs NULL = the grid of the netlist's .DISTO
+ * card (F ignored); out_p_eq == -2 = the card's output (out_m_eq ignored); no card: CSIM_ERR_CONFIG.
+ * h [B][F][3][N] complex or NULL; hd [B][F][2]; coef [B][M][7] or NULL.                                             */
+int  csim_disto_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F,
+                      int32_t out_p_eq, int32_t out_m_eq, double* h, double* hd, double* coef, uint32_t* status);
+
 /* Batched dense solve A x = b with the engine's pivoted LU
  * (Solver::solveLinearSystemLU semantics: first-maximum partial pivoting,
  * tiny pivot -> zero vector).  A [B][n][n] row-major, b/x [B][n], host
@@ -511,6 +579,17 @@ int  csim_spnoise_solve_batch(int32_t device, int32_t n, int32_t B, int32_t P, c
                               const int32_t* src_b, const double* psd, const double* omega, int32_t F, int32_t kernel,
                               double* y, double* cy, double* nf, double* fmin, double* rn, double* yopt, double* x,
                               uint32_t* flags);
+
+/* The distortion kernels on systems and device tables given directly (host pointers; lu_eps = 1e-15), the counterpart
+ * of csim_ac_solve_batch for "Distortion analysis".  G, C [B][n][n] row-major; J [B][n] complex (re, im) pairs; devices
+ * dev_d, dev_g, dev_s [M] (equations, -1 ground) with coef [B][M][7] in the order of that section; omega [F] rad/s.
+ * hd [B][F][2]; h [B][F][3][n] complex (zeros from the failed order on) and flags [B] are optional.  kernel 0 auto
+ * (packed for n <= 32), 1 wave (n <= 63), 2 packed (n <= 32); 4 (block): CSIM_ERR_UNSUPPORTED; any other value, 3
+ * included: CSIM_ERR_ARG; an equation index out of range, or out_p == out_m: CSIM_ERR_ARG.                        */
+int  csim_disto_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* C, const double* J,
+                            int32_t M, const int32_t* dev_d, const int32_t* dev_g, const int32_t* dev_s,
+                            const double* coef, int32_t out_p, int32_t out_m, const double* omega, int32_t F,
+                            int32_t kernel, double* h, double* hd, uint32_t* flags);
 
 /* ---- Gauss-Seidel variant of the reference (never reached from its main(), kept as public API) ----
  * Batched Solver::solveLinearSystemGaussSeidel (include/solver.hpp:139-204): sweeps in row order with the
