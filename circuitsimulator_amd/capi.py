@@ -71,6 +71,11 @@ PROTOTYPES = {
     "csim_disto_batch": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "csim_disto_solve_batch": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32,
                                          _i32, _vp, _vp, _vp]),
+    "csim_netlist_stb": (C.c_int, [_vp, _pi32, _pi32, _pi32, _pi32, _pi32, _pi32, _pi32, _pdbl, _pdbl]),
+    "csim_stb_batch_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "csim_stb_batch": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "csim_stb_solve_batch": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                       _vp]),
     "csim_netlist_num_ports": (C.c_int, [_vp]),
     "csim_netlist_port": (C.c_int, [_vp, _i32, _pi32, _pi32, _pdbl]),
     "csim_netlist_sp": (C.c_int, [_vp, _pi32, _pi32, _pi32, _pdbl, _pdbl]),

@@ -121,6 +121,24 @@ BatchDistoResult BatchEngine::disto(const std::vector<double>& params, int B, co
     return r;
 }
 
+BatchStbResult BatchEngine::stb(const std::vector<double>& params, int B, const std::vector<double>& freqs, int probeElem,
+                                bool wantMargins)
+{
+    BatchStbResult r;
+    r.freqs = freqs;
+    r.t.assign(static_cast<std::size_t>(B) * freqs.size(), std::complex<double>());
+    if (wantMargins) {
+        r.margins.assign(static_cast<std::size_t>(B) * 4, 0.0);
+        r.found.assign(static_cast<std::size_t>(B), 0);
+    }
+    r.status.assign(static_cast<std::size_t>(B), 0);
+    if (csim_stb_batch(eng_, params.empty() ? nullptr : params.data(), B, freqs.data(), static_cast<int>(freqs.size()),
+                       probeElem, reinterpret_cast<double*>(r.t.data()), nullptr, wantMargins ? r.margins.data() : nullptr,
+                       wantMargins ? r.found.data() : nullptr, r.status.data()) != CSIM_OK)
+        fail("csim_stb_batch");
+    return r;
+}
+
 BatchSpResult BatchEngine::sp(const std::vector<double>& params, int B, const std::vector<double>& freqs, bool wantS)
 {
     BatchSpResult r;

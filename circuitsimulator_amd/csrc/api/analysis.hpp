@@ -74,6 +74,14 @@ struct BatchDistoResult {
     std::vector<uint32_t> status;                 // DC and LU bits (CSIM_ST_LU_TINY_PIVOT: a singular order)
 };
 
+struct BatchStbResult {
+    std::vector<double> freqs;                    // [F] Hz
+    std::vector<std::complex<double>> t;          // [B][F]: the loop gain
+    std::vector<double> margins;                  // [B][4]: PM (degrees), fc (Hz), GM (dB), f180 (Hz); NaN where not found
+    std::vector<int32_t> found;                   // [B]: bit 0 the unity crossing, bit 1 the phase crossing
+    std::vector<uint32_t> status;                 // DC and LU bits (CSIM_ST_LU_TINY_PIVOT: a singular frequency, or den == 0)
+};
+
 // One engine per (circuit, GPU).  Throws std::runtime_error when no HIP
 // device is usable: there is no CPU path.
 class BatchEngine {
@@ -121,6 +129,12 @@ public:
     // per frequency, at w, 2 w and 3 w.  Output V(outP) - V(outM) (equations; outM = -1: ground).
     BatchDistoResult disto(const std::vector<double>& params, int B, const std::vector<double>& freqs, int outP,
                            int outM = -1, bool wantPhasors = false);
+
+    // Loop gain at a V source in series in the loop (csim_stb_batch, include/csim.h): DC operating point, then one
+    // factorisation with two right-hand sides per frequency.  probeElem -1: the .STB card's probe; margins need
+    // strictly increasing positive frequencies.
+    BatchStbResult stb(const std::vector<double>& params, int B, const std::vector<double>& freqs, int probeElem = -1,
+                       bool wantMargins = true);
 
     // the transient of instance `instance` of params ([B][P], empty = nominal) as the reference's CSV
     // (src/tanalisis.cpp:189-231); probeEq empty: the netlist's .PLOTNV/.PRINT probes when `sim` names any, else

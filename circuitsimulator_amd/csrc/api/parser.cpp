@@ -424,6 +424,7 @@ void NetlistParser::dotCard(const Statement& st)
     else if (head == ".noise")  noiseCard(st);
     else if (head == ".sp")     spCard(st);
     else if (head == ".disto")  distoCard(st);
+    else if (head == ".stb")    stbCard(st);
     else if (head == ".print")  printCard(st);
     else if (head == ".model")  modelCard(st);
     else if (head == ".hb")     hbCard(st);
@@ -602,6 +603,31 @@ void NetlistParser::distoCard(const Statement& st)
     }
     cfg.enabled = true;
     sim.disto = cfg;
+}
+
+// .STB Vprobe {LIN|DEC|OCT} npoints fstart fstop   (any other token count is an error)
+void NetlistParser::stbCard(const Statement& st)
+{
+    const auto& t = st.tokens;
+    const std::string sweep = t.size() > 2 ? toLower(t[2]) : std::string();
+    if (t.size() != 6 || (sweep != "lin" && sweep != "oct" && sweep != "dec")) {
+        std::cerr << "Line " << st.lineNo << ": invalid .STB syntax: " << st.raw << "\n";
+        return;
+    }
+    StbConfig cfg;
+    cfg.probeName = t[1];
+    cfg.sweepType = sweep == "lin" ? AcSweepType::LIN : (sweep == "oct" ? AcSweepType::OCT : AcSweepType::DEC);
+    try {
+        cfg.nPoints = std::stoi(t[3]);
+        cfg.fstart  = parseSpiceNumber(t[4]);
+        cfg.fstop   = parseSpiceNumber(t[5]);
+    } catch (const std::exception& e) {
+        std::cerr << "Line " << st.lineNo << ": cannot parse .STB arguments: " << e.what()
+                  << " in '" << st.raw << "'\n";
+        return;
+    }
+    cfg.enabled = true;
+    sim.stb = cfg;
 }
 
 // .HB f0 nharm

@@ -174,6 +174,15 @@ struct DistoConfig {
     double fstart = 0.0, fstop = 0.0;
 };
 
+// .STB Vprobe {DEC|OCT|LIN} n fstart fstop -- the probe's name as written; netlist_capi.cpp resolves it
+struct StbConfig {
+    bool enabled = false;
+    std::string probeName;          // a V source in series in the loop, + on the driving side
+    AcSweepType sweepType = AcSweepType::DEC;
+    int nPoints = 0;
+    double fstart = 0.0, fstop = 0.0;
+};
+
 struct HbConfig {
     bool enabled = false;
     double f0 = 0.0;
@@ -201,6 +210,7 @@ public:
     NoiseConfig noise;
     SpConfig sp;
     DistoConfig disto;
+    StbConfig stb;
     HbConfig hb;
     std::vector<PrintCommand> printCommands;
 

@@ -338,6 +338,15 @@ int csim_engine_create(const csim_netlist* nl, int32_t device, csim_engine** out
         eng->distoFstop = dc.fstop;
     }
     if (!rc) {
+        const StbConfig& tc = nl->sim.stb;
+        eng->stbEnabled = tc.enabled ? 1 : 0;
+        eng->stbElem = nl->stbElem;
+        eng->stbSweep = tc.sweepType == AcSweepType::DEC ? 0 : (tc.sweepType == AcSweepType::OCT ? 1 : 2);
+        eng->stbPoints = tc.nPoints;
+        eng->stbFstart = tc.fstart;
+        eng->stbFstop = tc.fstop;
+    }
+    if (!rc) {
         for (const csim::Port& p : nl->ports) { eng->spPortEq.push_back(p.branchEq); eng->spZ0.push_back(p.z0); }
         eng->spPortError = nl->portError;
         const SpConfig& sc = nl->sim.sp;
@@ -371,7 +380,7 @@ void csim_engine_destroy(csim_engine* eng)
     if (eng->hViolFlag) (void)hipHostFree(eng->hViolFlag);
     if (eng->dKnownAlts) (void)hipFree(eng->dKnownAlts);
     if (eng->dBigScratch) (void)hipFree(eng->dBigScratch);
-    for (auto* ring : {&eng->acOmegaSlots, &eng->acProbeSlots})
+    for (auto* ring : {&eng->acOmegaSlots, &eng->acProbeSlots, &eng->stbFreqSlots})
         for (auto& s : *ring) {
             if (s.done) (void)hipEventDestroy(s.done);
             if (s.d) (void)hipFree(s.d);

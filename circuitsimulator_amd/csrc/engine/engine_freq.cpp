@@ -1,6 +1,6 @@
-// engine_freq.cpp -- C-ABI of the frequency-domain analyses: AC, noise, S-parameters, two-port noise, distortion, each as
-// csim_*_batch_dev (device pointers, enqueue only), csim_*_batch (host pointers, DC operating point included) and
-// csim_*_solve_batch (any system, no engine).  What the four share is written once: kernel choice, the chunk
+// engine_freq.cpp -- C-ABI of the frequency-domain analyses: AC, noise, S-parameters, two-port noise, distortion and loop
+// gain, each as csim_*_batch_dev (device pointers, enqueue only), csim_*_batch (host pointers, DC operating point
+// included) and csim_*_solve_batch (any system, no engine).  What the six share is written once: kernel choice, the chunk
 // driver, scratch growth, the card's frequencies, the operating point and the output list of the host-pointer forms.
 // A new analysis supplies its setup function, its ...Args and its sweep launch.
 #include <hip/hip_runtime.h>
@@ -14,6 +14,7 @@
 #include "ac_disto.hpp"
 #include "ac_noise.hpp"
 #include "ac_port.hpp"
+#include "ac_stb.hpp"
 #include "csim.h"
 #include "engine_host.hpp"
 #include "kernels.hpp"
@@ -376,6 +377,37 @@ int distoSetup(const csim_engine* eng, int out_p, int out_m, csim::DistoArgs& a)
     a.devG = eng->dDistoG;
     a.devS = eng->dDistoS;
     return CSIM_OK;
+}
+
+// the probe of a loop-gain call -> the kernels' numbers (include/csim.h "Loop-gain analysis"); probe_elem -1: the card's
+int stbSetup(const csim_engine* eng, int probe_elem, csim::StbArgs& a)
+{
+    const int N = eng->plan.N;
+    if (const int rc = acBlockRefused(eng, "loop-gain analysis")) return rc;
+    if (N > 63) { setError("loop-gain analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
+    if (probe_elem == -1) {
+        if (!eng->stbEnabled) { setError("loop-gain analysis: no probe given and the netlist has no .STB card"); return CSIM_ERR_CONFIG; }
+        probe_elem = eng->stbElem;
+    }
+    const csim::CircuitIR& c = eng->cir;
+    if (probe_elem < 0 || probe_elem >= c.ir.n_elems) { setError("loop-gain analysis: the probe is not an element of the netlist"); return CSIM_ERR_CONFIG; }
+    if (c.kind[(size_t)probe_elem] != CSIM_V) { setError("loop-gain analysis: the probe must be a V source"); return CSIM_ERR_CONFIG; }
+    a.eqP = c.eq[4 * (size_t)probe_elem + 0];
+    a.eqM = c.eq[4 * (size_t)probe_elem + 1];
+    a.eqBr = c.branchEq[(size_t)probe_elem];
+    if (a.eqP < 0 || a.eqP >= N || a.eqM < 0 || a.eqM >= N || a.eqBr < 0 || a.eqBr >= N || a.eqP == a.eqM) {
+        setError("loop-gain analysis: the probe needs two different nodes off ground");
+        return CSIM_ERR_CONFIG;
+    }
+    return CSIM_OK;
+}
+
+// margins need strictly increasing positive frequencies
+bool stbFreqsIncrease(const double* freqs, int F)
+{
+    for (int f = 0; f < F; ++f)
+        if (!(freqs[f] > (f ? freqs[f - 1] : 0.0)) || !std::isfinite(freqs[f])) return false;
+    return true;
 }
 
 // ---- engine-free forms -----------------------------------------------------------
@@ -796,6 +828,85 @@ int csim_disto_batch(csim_engine* eng, const double* params, int32_t B, const do
     return rc ? rc : outs.finish(op.status, status);
 }
 
+// ---- loop-gain analysis -----------------------------------------------------
+
+int csim_stb_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const double* d_xop, const double* freqs,
+                       int32_t F, int32_t probe_elem, double* d_t, double* d_x, double* d_margins, int32_t* d_found,
+                       uint32_t* d_status, void* stream)
+{
+    if (!eng || B < 0 || F < 0 || (B > 0 && F > 0 && (!d_params || !d_xop || !freqs || !d_t || !d_status)) ||
+        (d_found && !d_margins)) {
+        setError("csim_stb_batch_dev: bad argument");
+        return CSIM_ERR_ARG;
+    }
+    if (d_margins && B > 0 && !stbFreqsIncrease(freqs, F)) {
+        setError("csim_stb_batch_dev: margins need strictly increasing positive frequencies");
+        return CSIM_ERR_ARG;
+    }
+    csim::StbArgs a{};
+    if (const int rc = stbSetup(eng, probe_elem, a)) return rc;
+    int which;
+    if (const int rc = acPickKernel(eng->cfg.acKernel, eng->plan.N, nullptr, &which)) return rc;
+    if (B == 0 || (F == 0 && !d_margins)) return CSIM_OK;
+    HIPCHK(hipSetDevice(eng->device));
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    // the frequencies in Hz for the margins kernel: uploaded when the list changes, cached otherwise
+    const double* dFreqs = nullptr;
+    if (d_margins && F > 0) {
+        std::vector<double> want(freqs, freqs + F);
+        if (eng->stbFreqCur < 0 || want != eng->stbFreqCache) {
+            eng->stbFreqCache.clear();
+            if (const int rc = acUpload(eng->stbFreqSlots, eng->stbFreqCur, want.data(), sizeof(double) * want.size())) return rc;
+            eng->stbFreqCache = want;
+        }
+        dFreqs = static_cast<const double*>(eng->stbFreqSlots[(size_t)eng->stbFreqCur].d);
+    }
+    a.t = d_t;
+    a.x = d_x;
+    if (F > 0)
+        if (const int rc = acSweepChunks(eng, d_params, B, d_xop, freqs, F, which, hs, nullptr, d_status, a,
+                                         [&](const double*, size_t, size_t) { return csim::launchStbSweep(which, a, hs); })) return rc;
+    if (d_margins) {
+        HIPCHK(csim::launchStbMargins(F, B, dFreqs, d_t, d_margins, d_found, hs));
+        if (dFreqs) HIPCHK(hipEventRecord(eng->stbFreqSlots[(size_t)eng->stbFreqCur].done, hs));
+    }
+    return CSIM_OK;
+}
+
+int csim_stb_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F, int32_t probe_elem,
+                   double* t, double* x, double* margins, int32_t* found, uint32_t* status)
+{
+    if (!eng || B < 0 || (found && !margins)) { setError("csim_stb_batch: bad argument"); return CSIM_ERR_ARG; }
+    std::vector<double> card;
+    if (!freqs)
+        if (const int rc = cardFreqs(eng->stbEnabled, eng->stbSweep, eng->stbPoints, eng->stbFstart, eng->stbFstop,
+                                     "loop-gain analysis", ".STB", card, &freqs, &F)) return rc;
+    if (F < 0 || (B > 0 && F > 0 && !t)) { setError("csim_stb_batch: bad argument"); return CSIM_ERR_ARG; }
+    if (margins && B > 0 && !stbFreqsIncrease(freqs, F)) {
+        setError("csim_stb_batch: margins need strictly increasing positive frequencies");
+        return CSIM_ERR_ARG;
+    }
+    {
+        csim::StbArgs probe{};
+        if (const int rc = stbSetup(eng, probe_elem, probe)) return rc;
+    }
+    if (B == 0) return CSIM_OK;
+    HIPCHK(hipSetDevice(eng->device));
+    OpPoint op;
+    HostOutputs outs(F, B);
+    double* dT = outs.add(t, 1, 2);
+    double* dX = outs.add(x, 2 * eng->plan.N, 2);
+    double* dMargins = outs.add(margins, 4, 1, false, true);
+    DevBuf dFound;
+    if (found) HIPCHK(dFound.alloc(sizeof(int32_t) * (size_t)B));
+    int rc = opPointSolve(eng, params, B, outs, op);
+    if (!rc) rc = csim_stb_batch_dev(eng, op.params.as<double>(), B, op.x.as<double>(), freqs, F, probe_elem, dT, dX, dMargins,
+                                     found ? dFound.as<int32_t>() : nullptr, op.status.as<uint32_t>(), nullptr);
+    if (!rc) rc = outs.finish(op.status, status);
+    if (!rc && found) HIPCHK(hipMemcpy(found, dFound.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    return rc;
+}
+
 // ---- engine-free forms: any system through the sweep kernels, without an engine or a netlist ----------------
 
 // the complex counterpart of csim_lu_solve_batch: any (G + jwC) x = J through the AC sweep kernels
@@ -1014,6 +1125,50 @@ int csim_disto_solve_batch(int32_t device, int32_t n, int32_t B, const double* G
     if (outs.rc) return outs.rc;
     HIPCHK(csim::launchDistoSweep(fr.which, a, nullptr));
     return outs.finish(fr.dF, flags);
+}
+
+// the loop-gain kernels: any system, any probe; the margins kernel on their T
+int csim_stb_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* Cm, int32_t eq_p, int32_t eq_m,
+                         int32_t eq_br, const double* omega, int32_t F, int32_t kernel, double* T, double* x, uint32_t* flags,
+                         const double* freqs_hz, double* margins, int32_t* found)
+{
+    const bool work = n > 0 && B > 0 && F > 0;
+    if (n < 0 || B < 0 || F < 0 || !acKernelValid(kernel) || (found && !margins) ||
+        (work && (!G || !Cm || !omega || !T || (margins && !freqs_hz)))) {
+        setError("csim_stb_solve_batch: bad argument");
+        return CSIM_ERR_ARG;
+    }
+    if (work && margins && !stbFreqsIncrease(freqs_hz, F)) {
+        setError("csim_stb_solve_batch: margins need strictly increasing positive frequencies");
+        return CSIM_ERR_ARG;
+    }
+    if (n > 0 && (eq_p < 0 || eq_p >= n || eq_m < 0 || eq_m >= n || eq_br < 0 || eq_br >= n || eq_p == eq_m || eq_p == eq_br ||
+                  eq_m == eq_br)) {
+        setError("csim_stb_solve_batch: the probe needs three different equations in range");
+        return CSIM_ERR_ARG;
+    }
+    AcSolveFront fr;
+    if (const int rc = acSolveFront("csim_stb_solve_batch", device, n, B, G, Cm, nullptr, omega, F, kernel, work, fr)) return rc;
+    if (!work) return CSIM_OK;
+    HostOutputs outs(F, B);
+    csim::StbArgs a{};
+    fr.fill(a, n, F, B);
+    a.eqP = eq_p; a.eqM = eq_m; a.eqBr = eq_br;
+    a.t = outs.add(T, 1, 2);
+    a.x = outs.add(x, 2 * n, 2);                                                // [F][2][n][B] -> [B][F][2][n]
+    double* dMargins = outs.add(margins, 4, 1, false, true);                    // [4][B] -> [B][4]
+    if (outs.rc) return outs.rc;
+    DevBuf dFreqs, dFound;
+    HIPCHK(csim::launchStbSweep(fr.which, a, nullptr));
+    if (margins) {
+        HIPCHK(dFreqs.alloc(sizeof(double) * (size_t)F));
+        HIPCHK(hipMemcpy(dFreqs.p, freqs_hz, sizeof(double) * (size_t)F, hipMemcpyHostToDevice));
+        if (found) HIPCHK(dFound.alloc(sizeof(int32_t) * (size_t)B));
+        HIPCHK(csim::launchStbMargins(F, B, dFreqs.as<double>(), a.t, dMargins, found ? dFound.as<int32_t>() : nullptr, nullptr));
+    }
+    if (const int rc = outs.finish(fr.dF, flags)) return rc;
+    if (margins && found) HIPCHK(hipMemcpy(found, dFound.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    return CSIM_OK;
 }
 
 } // extern "C"

@@ -114,9 +114,10 @@ struct csim_engine {
     // current one: it goes to a slot whose last reader has finished (`done`, recorded on the caller's stream
     // after every sweep that uses the slot), or to a new one.
     struct AcList { void* d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; };
-    std::vector<AcList> acOmegaSlots, acProbeSlots;
+    std::vector<AcList> acOmegaSlots, acProbeSlots, stbFreqSlots;
     int acOmegaCur = -1, acProbeCur = -1;  // slot holding acOmegaCache / acProbeCache
-    std::vector<double> acOmegaCache;
+    int stbFreqCur = -1;                   // slot holding stbFreqCache: the frequencies in Hz, read by the margins kernel
+    std::vector<double> acOmegaCache, stbFreqCache;
     std::vector<int32_t> acProbeCache;
     double* dAcSys = nullptr;
     int acSysCap = 0;                      // instances
@@ -140,6 +141,10 @@ struct csim_engine {
     const int32_t *dDistoElem = nullptr, *dDistoD = nullptr, *dDistoG = nullptr, *dDistoS = nullptr;
     double* dDistoCoef = nullptr;
     size_t distoCoefCap = 0;               // doubles
+
+    // Loop-gain analysis: the netlist's .STB card; stbElem is its probe element (-2: a name the netlist does not have)
+    int stbEnabled = 0, stbElem = -2, stbSweep = 0, stbPoints = 0;
+    double stbFstart = 0.0, stbFstop = 0.0;
 
     // S-parameter analysis: the netlist's .SP card and its ports in port order (branch equation, Z0); spPortError
     // says what is wrong with the PORTNUM numbering, if anything

@@ -187,6 +187,25 @@ hipError_t launchDistoCoef(const GenPlan& pl, const int32_t* dDevElem, int M, co
                            const double* dXop, double* dCoef, size_t coefStride, size_t coefOff, hipStream_t stream);
 hipError_t launchDistoSweep(int which, const DistoArgs& a, hipStream_t stream);
 
+// Loop-gain analysis (kernels_stb.hip) on the systems launchAcAssemble leaves (their J is not read): one factorisation
+// with two right-hand sides per (instance, frequency), T formed on the device.  The probe's equations are checked by
+// the launcher: they index LDS.  Wave and packed shapes only.
+struct StbArgs {
+    int N, F, B, b0, Bc;
+    int eqP, eqM, eqBr;                 // the probe: + node (drives), - node (receives), branch equation
+    double eps;
+    const double* sys;
+    const double* omega;
+    double* t;                          // [F][B] complex: the loop gain
+    double* x;                          // [F][2][N][B] complex or null: the two solutions
+    uint32_t* status;                   // [B], OR-ed
+};
+hipError_t launchStbSweep(int which, const StbArgs& a, hipStream_t stream);
+// the margins of B instances from t [F][B] complex at freqs [F] (Hz, on the device): margins [4][B] = PM, fc, GM, f180;
+// found [B] or null
+hipError_t launchStbMargins(int F, int B, const double* dFreqs, const double* dT, double* dMargins, int32_t* dFound,
+                            hipStream_t stream);
+
 // layout helpers (transpose.hip): [rows][cols] <-> [cols][rows] of doubles
 hipError_t launchTranspose(const double* dIn, double* dOut, int rows, int cols, hipStream_t stream);
 

@@ -68,6 +68,11 @@ int finishNetlist(csim_netlist* nl)
         nl->distoOutM = dc.refNode.empty() ? -1 : eqOf(dc.refNode);
     }
 
+    // .STB card: the probe's name -> element index
+    if (nl->sim.stb.enabled)
+        for (std::size_t e = 0; e < nl->ckt.elements.size(); ++e)
+            if (toLower(nl->ckt.elements[e]->getName()) == toLower(nl->sim.stb.probeName)) { nl->stbElem = static_cast<int>(e); break; }
+
     // PORTNUM tokens: the ports in port order
     nl->portError = csim::portList(nl->cir, nl->ports);
     if (!nl->portError.empty()) std::cerr << nl->portError << "\n";
@@ -242,6 +247,25 @@ int csim_netlist_disto_device(const csim_netlist* nl, int32_t i, int32_t* elem, 
     if (eq_d) *eq_d = dev[static_cast<std::size_t>(i)].d;
     if (eq_g) *eq_g = dev[static_cast<std::size_t>(i)].g;
     if (eq_s) *eq_s = dev[static_cast<std::size_t>(i)].s;
+    return CSIM_OK;
+}
+
+int csim_netlist_stb(const csim_netlist* nl, int32_t* enabled, int32_t* elem, int32_t* eq_p, int32_t* eq_m, int32_t* eq_br,
+                     int32_t* sweep, int32_t* n_points, double* fstart, double* fstop)
+{
+    if (!nl) return CSIM_ERR_ARG;
+    const StbConfig& a = nl->sim.stb;
+    const int e = a.enabled ? nl->stbElem : -2;
+    const bool isV = e >= 0 && nl->cir.kind[static_cast<std::size_t>(e)] == CSIM_V;
+    if (enabled)  *enabled = a.enabled ? 1 : 0;
+    if (elem)     *elem = e;
+    if (eq_p)     *eq_p = isV ? nl->cir.eq[4 * static_cast<std::size_t>(e) + 0] : -2;
+    if (eq_m)     *eq_m = isV ? nl->cir.eq[4 * static_cast<std::size_t>(e) + 1] : -2;
+    if (eq_br)    *eq_br = isV ? nl->cir.branchEq[static_cast<std::size_t>(e)] : -2;
+    if (sweep)    *sweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
+    if (n_points) *n_points = a.nPoints;
+    if (fstart)   *fstart = a.fstart;
+    if (fstop)    *fstop = a.fstop;
     return CSIM_OK;
 }
 

@@ -23,6 +23,8 @@ struct csim_netlist {
     int noiseOutP = -2, noiseOutM = -1, noiseSrcElem = -1;
     // .DISTO card resolved to indices: output equations (-1 ground, -2 unknown node)
     int distoOutP = -2, distoOutM = -1;
+    // .STB card resolved: the probe's element index (-2: a name the netlist does not have)
+    int stbElem = -2;
     // the ports (PORTNUM) in port order, or what is wrong with their numbering
     std::vector<csim::Port> ports;
     std::string portError;

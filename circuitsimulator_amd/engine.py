@@ -115,6 +115,23 @@ class Netlist:
         return out
 
     @property
+    def stb(self):
+        """The .STB card: None, or (probe element, eq_p, eq_m, eq_br, sweep, n_points, fstart, fstop).  The element is -2
+        for a name the netlist does not have; the equations are -2 when the probe is not a V source, -1 = ground."""
+        v = [C.c_int32() for _ in range(7)]
+        f0, f1 = C.c_double(), C.c_double()
+        capi.check(capi.lib().csim_netlist_stb(self._h, *[C.byref(x) for x in v], C.byref(f0), C.byref(f1)))
+        en, el, ep, em, eb, sw, npt = [x.value for x in v]
+        return (el, ep, em, eb, AC_SWEEPS[sw], npt, f0.value, f1.value) if en else None
+
+    def stb_freqs(self):
+        """Frequency grid of the .STB card (numpy, Hz)."""
+        card = self.stb
+        if card is None:
+            raise capi.CsimError(capi.CSIM_ERR_CONFIG, "the netlist has no .STB card")
+        return ac_freqs(*card[4:])
+
+    @property
     def ports(self):
         """The ports (V sources with PORTNUM k [Z0 r]) in port order: [(element index, branch equation, Z0)].
         Raises CsimError(CSIM_ERR_CONFIG) when the numbering has a gap or a duplicate or there are more than 4."""
@@ -514,6 +531,58 @@ class Engine:
                                                hd.ctypes.data, ptr(cf), st.ctypes.data))
         return dict(freqs=f, h=h, hd=hd, coef=cf, status=st)
 
+    def _stb_args(self, freqs, probe):
+        """-> (freqs, probe element); None takes the .STB card's value (-1 tells the library to)"""
+        f = self.netlist.stb_freqs() if freqs is None else np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        return f, -1 if probe is None else int(probe)
+
+    @staticmethod
+    def _stb_dict(f, t, x, mg, fd, st, axis):
+        """margins [4][B] (axis 0) or [B][4] (axis 1) -> the four named entries"""
+        if mg is None:
+            pm = fc = gm = f180 = None
+        else:
+            pm, fc, gm, f180 = (mg[i] if axis == 0 else np.ascontiguousarray(mg[:, i]) for i in range(4))
+        return dict(freqs=f, t=t, x=x, pm=pm, fc=fc, gm=gm, f180=f180, found=fd, status=st)
+
+    def stb(self, params, x_op, freqs=None, probe=None, margins=True, want_x=False, status=None):
+        """Loop-gain sweep of the batch around the operating points x_op (device [N][B], from dc()); csim_stb_batch_dev.
+        freqs: Hz; probe: element index of a V source in series in the loop, + on the driving side -- None takes each
+        from the .STB card.  margins need strictly increasing positive frequencies.
+        -> dict(freqs, t complex [F][B], x complex [F][2][N][B] or None, pm (degrees), fc (Hz), gm (dB), f180 (Hz) [B]
+                (NaN where not found) and found [B] (bit 0 unity, bit 1 phase crossing) or None, status [B]); device
+                tensors; status is OR-ed into `status` when given."""
+        torch = _torch()
+        B = params.shape[1]
+        f, probe = self._stb_args(freqs, probe)
+        dev = self._dev()
+        t = torch.zeros((len(f), B, 2), dtype=torch.float64, device=dev)
+        x = torch.zeros((len(f), 2, self.N, B, 2), dtype=torch.float64, device=dev) if want_x else None
+        mg = torch.zeros((4, B), dtype=torch.float64, device=dev) if margins else None
+        fd = torch.zeros(B, dtype=torch.int32, device=dev) if margins else None
+        st = status if status is not None else torch.zeros(B, dtype=torch.int32, device=dev)
+        ptr = lambda v: v.data_ptr() if v is not None else None     # noqa: E731
+        capi.check(capi.lib().csim_stb_batch_dev(self._h, params.data_ptr(), B, x_op.data_ptr(), f.ctypes.data, len(f), probe,
+                                                 t.data_ptr(), ptr(x), ptr(mg), ptr(fd), st.data_ptr(), self._stream()))
+        return self._stb_dict(f, torch.view_as_complex(t), torch.view_as_complex(x) if x is not None else None, mg, fd, st, 0)
+
+    def stb_host(self, params=None, B=1, freqs=None, probe=None, margins=True, want_x=False):
+        """DC operating point + loop-gain sweep (csim_stb_batch): numpy, instance-major.
+        -> dict(freqs, t complex [B][F], x complex [B][F][2][N] or None, pm, fc, gm, f180, found [B] or None, status [B])"""
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=np.float64)
+            B = params.shape[0]
+        f, probe = self._stb_args(freqs, probe)
+        t = np.zeros((B, len(f)), dtype=np.complex128)
+        x = np.zeros((B, len(f), 2, self.N), dtype=np.complex128) if want_x else None
+        mg = np.zeros((B, 4)) if margins else None
+        fd = np.zeros(B, dtype=np.int32) if margins else None
+        st = np.zeros(B, dtype=np.uint32)
+        ptr = lambda a: a.ctypes.data if a is not None else None    # noqa: E731
+        capi.check(capi.lib().csim_stb_batch(self._h, ptr(params), B, f.ctypes.data, len(f), probe, t.ctypes.data, ptr(x),
+                                             ptr(mg), ptr(fd), st.ctypes.data))
+        return self._stb_dict(f, t, x, mg, fd, st, 1)
+
     def sp(self, params, x_op, freqs=None, want_s=True, status=None):
         """S-parameter sweep of the batch around the operating points x_op (device [N][B], from dc());
         csim_sp_batch_dev.  freqs: Hz, None = the .SP card.
@@ -877,6 +946,36 @@ def disto_solve_batch(G, Cm, J, dev_d, dev_g, dev_s, coef, out, omega, kernel="a
         dev_s.ctypes.data, coef.ctypes.data, int(out[0]), int(out[1]), omega.ctypes.data, F, _AC_KERNELS[kernel],
         h.ctypes.data if h is not None else None, hd.ctypes.data, flags.ctypes.data))
     return dict(h=h, hd=hd, flags=flags)
+
+
+def stb_solve_batch(G, Cm, probe, omega, kernel="auto", device=0, want_x=True, freqs=None):
+    """The loop-gain kernels on systems given directly (csim_stb_solve_batch): (G + j w C) X = [e_k, e_x] and T from the
+    two solutions.  G, Cm [B][n][n] real; probe = (eq_p, eq_m, eq_br), the equations of the probe's + node, - node and
+    branch; omega [F] rad/s; kernel auto | wave | packed (block is refused: CSIM_ERR_UNSUPPORTED); freqs [F] in Hz,
+    strictly increasing and positive: the margins are computed too.
+    -> dict(t complex [B][F], x complex [B][F][2][n] or None, pm, fc, gm, f180, found [B] or None, flags [B])"""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    Cm = np.ascontiguousarray(Cm, dtype=np.float64)
+    omega = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
+    B, n = G.shape[0], G.shape[1]
+    F = len(omega)
+    if freqs is not None:
+        freqs = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        if len(freqs) != F:
+            raise ValueError("freqs and omega differ in length")
+    t = np.zeros((B, F), dtype=np.complex128)
+    x = np.zeros((B, F, 2, n), dtype=np.complex128) if want_x else None
+    mg = np.full((B, 4), np.nan) if freqs is not None else None
+    fd = np.zeros(B, dtype=np.int32) if freqs is not None else None
+    flags = np.zeros(B, dtype=np.uint32)
+    ptr = lambda a: a.ctypes.data if a is not None else None    # noqa: E731
+    capi.check(capi.lib().csim_stb_solve_batch(
+        device, n, B, G.ctypes.data, Cm.ctypes.data, int(probe[0]), int(probe[1]), int(probe[2]), omega.ctypes.data, F,
+        _AC_KERNELS[kernel], t.ctypes.data, ptr(x), flags.ctypes.data, ptr(freqs), ptr(mg), ptr(fd)))
+    r = Engine._stb_dict(None, t, x, mg, fd, None, 1)
+    del r["freqs"], r["status"]
+    r["flags"] = flags
+    return r
 
 
 def sp_solve_batch(G, Cm, J, omega, kernel="auto", device=0, port_eq=None, z0=None, want_s=True):

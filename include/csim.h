@@ -78,7 +78,7 @@ extern "C" {
 #define CSIM_ERR_HIP          -4   /* a HIP runtime call failed                    */
 #define CSIM_ERR_UNSUPPORTED  -5   /* circuit outside what the kernels cover       */
 #define CSIM_ERR_EMPTY        -6   /* circuit has no unknowns                      */
-#define CSIM_ERR_CONFIG       -7   /* invalid .TRAN / .AC / .NOISE / .DISTO numbers, no AC source, no port */
+#define CSIM_ERR_CONFIG       -7   /* invalid .TRAN / .AC / .NOISE / .DISTO / .STB numbers, no AC source, no port, no probe */
 
 typedef struct csim_netlist csim_netlist;
 typedef struct csim_engine  csim_engine;
@@ -203,7 +203,7 @@ int  csim_engine_set_kernel(csim_engine* eng, int32_t which);
  *   near_test_rollback (0)                  test aid: every verified near-threshold decision is treated as a
  *                                           mismatch, so the roll-back path runs (results must not change)
  *   hybrid_sync (CSIM_HYBRID_SYNC, 1)       see "Streams" above
- *   ac_kernel (auto)                        AC, noise, S-parameter and distortion sweep kernel, auto | wave | packed (test aid) | block
+ *   ac_kernel (auto)                        AC, noise, S-parameter, distortion and loop-gain sweep kernel, auto | wave | packed (test aid) | block
  *                                           (opt-in: AC and noise of up to 1024 unknowns; see csim_ac_batch_dev)
  *   dc_fast (CSIM_DC_FAST, 0)               DC operating points start on the fast generated kernel (FMA
  *                                           contraction, reciprocal pivots; controller decisions within
@@ -526,6 +526,72 @@ int  csim_disto_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, i
 int  csim_disto_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F,
                       int32_t out_p_eq, int32_t out_m_eq, double* h, double* hd, double* coef, uint32_t* status);
 
+/* ---- Loop-gain analysis (.STB; the loop gain T of a feedback loop by Middlebrook's double injection at a V source in
+ *      series in the loop, one factorisation with two right-hand sides per frequency; phase and gain margins) ----
+ * Card: `.STB Vprobe DEC|OCT|LIN n fstart fstop`, the grid of csim_ac_freqs.  Any other token count is a card error,
+ *   reported, the statement dropped.  The card changes nothing in the IR.  A name the netlist does not have keeps the
+ *   card, with element -2, refused when used (CSIM_ERR_CONFIG).
+ * Probe.  A V source of the netlist in series in the loop, normally DC 0.  Its + node is the side that DRIVES the loop
+ *   (equation x), its - node the side that RECEIVES (equation y); k is its branch equation, the branch current flowing
+ *   from + through the source ("S-parameter analysis").  With reverse transmission T depends on this orientation.
+ *   Not a V source, a node on ground, or + and - on one node: CSIM_ERR_CONFIG.
+ * System.  For instance b and angular frequency w, A(w) = G + j w C is exactly the matrix of "AC analysis" above.  Every
+ *   AC stimulus of the netlist is ignored: J is not read, and no source needs an AC magnitude.
+ * Two columns, one factorisation.
+ *   Column 0, voltage injection: the real unit vector at row k, exactly a port column of "S-parameter analysis".
+ *     vx = X0[x], vy = X0[y].
+ *   Column 1, current injection: +1.0 (im +0.0) at row x, nothing else.  SIGN: this is the column the AC assembly leaves
+ *     for `Iinj 0 <+node> AC 1` beside a probe with AC 0 -- an I source `I n1 n2` stamps J(n1) -= I and J(n2) += I, so
+ *     1 A from ground into the + node is +1.0 at x.  ib = X1[k], the part of that ampere that flows through the probe.
+ * Loop gain.  Tv = -vx / vy, Ti = (1 - ib) / ib, T = (Tv Ti - 1) / (Tv + Ti + 2), evaluated without the intermediate
+ *   divisions, in this order:
+ *     a = 1.0 - ib,  b = 1.0 + ib                 (re: 1.0 -/+ ib.re; im: 0.0 -/+ ib.im)
+ *     num = -(vx a) - (vy ib)                     (each part: the exact negation of the first product minus the second)
+ *     den =  (vy b) - (vx ib)
+ *     T   = num / den                             (as a * conj(p) * (1 / |p|^2), "AC analysis")
+ *   Products of complex values as in "AC analysis" (four real products, one difference, one sum).  No FMA contraction.
+ *   T is positive real at low frequency for negative feedback.
+ * Failures.  A fails its pivot test (a column maximum below lu_eps^2): both solutions +0.0, T = +0.0 + 0.0j,
+ *   CSIM_ST_LU_TINY_PIVOT.  den exactly zero: the same T and flag.  The sweep goes on.
+ * Margins (optional), per instance, from T_0 .. T_{F-1} at strictly increasing positive frequencies f_k in Hz (anything
+ *   else with margins asked for: CSIM_ERR_ARG).  pi = 3.14159265358979323846; atan2, log10, log, exp of the C library
+ *   of the side that runs (the device's on the device), so margins are not bit-exact across implementations.
+ *     m_k = re^2 + im^2 of T_k,  g_k = 10.0 * log10(m_k)
+ *     phi_0 = atan2(im, re);  d_k = atan2 of T_k * conj(T_{k-1});  phi_k = phi_{k-1} + d_k  (unwrapped by increments)
+ *     unity crossing: the smallest k >= 1 with m_{k-1} >= 1.0 > m_k:
+ *       t = g_{k-1} / (g_{k-1} - g_k);  fc = f_{k-1} * exp(t * log(f_k / f_{k-1}));
+ *       PM = 180.0 + ((phi_{k-1} + t * d_k) * 180.0) / pi
+ *     phase crossing: the smallest k >= 1 with phi_{k-1} > -pi >= phi_k:
+ *       t = (phi_{k-1} + pi) / (phi_{k-1} - phi_k);  f180 by the same interpolation;
+ *       GM = -(g_{k-1} + t * (g_k - g_{k-1}))
+ *   The walk ends at the first T_k that is exactly zero or not finite; what was found before it stays.
+ *   margins = PM (degrees), fc (Hz), GM (dB), f180 (Hz); a pair that is not found is NaN.  found: bit 0 the unity
+ *   crossing, bit 1 the phase crossing.
+ * Circuits of up to 63 unknowns (CSIM_ERR_UNSUPPORTED beyond); ac_kernel=block: CSIM_ERR_UNSUPPORTED.  The exact order
+ * of every operation: engine/ac_stb.hpp, written once for host and device.
+ * Order of the refusals of an engine's call: a bad argument (margins on a grid that does not increase among them);
+ *   ac_kernel=block; more than 63 unknowns; no card where the probe was left to it; the probe (not in the netlist, not a
+ *   V source, a node on ground, + and - on one node -- its branch equation is never a node's, so three different
+ *   equations follow); ac_kernel=packed above 32 unknowns.  csim_stb_batch with freqs NULL asks for the card's grid
+ *   before any of these but its own argument check.
+ *
+ * Enqueues the sweep and (d_margins given) the margins kernel after its last chunk; never waits; frequency lists as
+ * csim_ac_batch_dev.  probe_elem: element index of the probe, -1 = the .STB card's (no card: CSIM_ERR_CONFIG).
+ *   d_t [F][B] complex (re, im)                d_x [F][2][N][B] complex or NULL: the two solutions
+ *   d_margins [4][B] or NULL                   d_found [B] int32 or NULL (needs d_margins)        d_status [B], OR-ed
+ * The engine option ac_kernel picks the kernel as for AC (wave, N <= 63; packed, N <= 32); both give bit-identical T.  */
+/* .STB card: the probe's element index (-2: a name the netlist does not have), the equations of its + node, - node and
+ * branch (-1: ground; all -2 when the probe is not a V source), the sweep as for .AC */
+int  csim_netlist_stb(const csim_netlist* nl, int32_t* enabled, int32_t* elem, int32_t* eq_p, int32_t* eq_m, int32_t* eq_br,
+                      int32_t* sweep, int32_t* n_points, double* fstart, double* fstop);
+int  csim_stb_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int32_t B, const double* d_xop,
+                        const double* freqs, int32_t F, int32_t probe_elem, double* d_t, double* d_x, double* d_margins,
+                        int32_t* d_found, uint32_t* d_status, void* stream);
+/* DC operating point, then the sweep.  params [B][P] or NULL (nominal); freqs NULL = the grid of the netlist's .STB card
+ * (F ignored).  t [B][F] complex; x [B][F][2][N] complex or NULL; margins [B][4] or NULL; found [B] or NULL.          */
+int  csim_stb_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F, int32_t probe_elem,
+                    double* t, double* x, double* margins, int32_t* found, uint32_t* status);
+
 /* Batched dense solve A x = b with the engine's pivoted LU
  * (Solver::solveLinearSystemLU semantics: first-maximum partial pivoting,
  * tiny pivot -> zero vector).  A [B][n][n] row-major, b/x [B][n], host
@@ -590,6 +656,17 @@ int  csim_disto_solve_batch(int32_t device, int32_t n, int32_t B, const double* 
                             int32_t M, const int32_t* dev_d, const int32_t* dev_g, const int32_t* dev_s,
                             const double* coef, int32_t out_p, int32_t out_m, const double* omega, int32_t F,
                             int32_t kernel, double* h, double* hd, uint32_t* flags);
+
+/* The loop-gain kernels on systems given directly (host pointers; lu_eps = 1e-15), the counterpart of
+ * csim_ac_solve_batch for "Loop-gain analysis".  G, C [B][n][n] row-major; eq_p, eq_m, eq_br the probe's + node, - node
+ * and branch equations, three different values in 0 .. n-1 (else CSIM_ERR_ARG); omega [F] rad/s.  T [B][F] complex;
+ * x [B][F][2][n] complex and flags [B] are optional.  margins [B][4] (optional) needs freqs_hz [F], strictly increasing
+ * and positive (else CSIM_ERR_ARG); found [B] int32 (optional) needs margins.  kernel 0 auto (packed for n <= 32), 1 wave
+ * (n <= 63), 2 packed (n <= 32); 4 (block): CSIM_ERR_UNSUPPORTED; any other value, 3 included: CSIM_ERR_ARG.  Nothing
+ * is written when n, B or F is 0.                                                                                   */
+int  csim_stb_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* C, int32_t eq_p, int32_t eq_m,
+                          int32_t eq_br, const double* omega, int32_t F, int32_t kernel, double* T, double* x,
+                          uint32_t* flags, const double* freqs_hz, double* margins, int32_t* found);
 
 /* ---- Gauss-Seidel variant of the reference (never reached from its main(), kept as public API) ----
  * Batched Solver::solveLinearSystemGaussSeidel (include/solver.hpp:139-204): sweeps in row order with the
