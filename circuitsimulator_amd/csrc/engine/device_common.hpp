@@ -59,6 +59,50 @@ __host__ __device__ inline LdsLayout ldsLayout(int N, int LD, int nTerms, int P)
 // worst deviation from the oracle 6.7e-10 -> 4.9e-11 (of a 1e-9 A floor).
 #pragma clang fp contract(off)
 
+// ---- iteration control of the DC and transient kernels (wave, packed, big, Gauss-Seidel), written once
+__device__ __forceinline__ double clampd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__device__ __forceinline__ double base_gmin(const csim_consts& k, double s)
+{
+    s = clampd(s, 0.0, 1.0);
+    return k.gmin_high * (1.0 - s) + k.gmin_low * s;        // dcanalysis.hpp:45-48
+}
+
+__device__ __forceinline__ double dc_alpha(const csim_consts& k) { return clampd(k.dc_alpha, k.dc_alpha_min, k.dc_alpha_max); }   // dcanalysis.cpp:274
+
+// ConvController::update (dcanalysis.cpp:268-307): the gmin of the next pass; gb = base_gmin of this ramp step
+__device__ __forceinline__ double conv_gmin_next(const csim_consts& k, int iter, double err, double prevErr, double gmin, double gb)
+{
+    if (iter == 0 || !isfinite(prevErr)) return gb;                             // :280-282
+    if (err > prevErr * k.slow_ratio) return fmin(gmin * 2.0, k.gmin_abs_max);  // :285-288
+    if (err < prevErr * k.fast_ratio) return 0.5 * gmin + 0.5 * gb;             // :289-293
+    return 0.7 * gmin + 0.3 * gb;                                               // :296
+}
+
+// hybrid stepping: `done` = steps of this launch each instance has completed; a kernel advances an unfinished
+// instance from step d0 by at most maxSteps, to sEnd, and hands it back (done == null: the whole launch)
+struct StepWindow { long long d0, sEnd; };
+__device__ __forceinline__ StepWindow step_window(const int32_t* done, int b, long long nSteps, int maxSteps)
+{
+    StepWindow w;
+    w.d0 = done ? (long long)done[b] : 0;
+    w.sEnd = done ? (w.d0 + maxSteps < nSteps ? w.d0 + maxSteps : nSteps) : nSteps;
+    return w;
+}
+__device__ __forceinline__ void step_window_close(int32_t* done, int b, long long nSteps, bool aborted, long long sLast)
+{
+    if (done) done[b] = aborted ? (int32_t)nSteps : (int32_t)sLast;
+}
+
+__device__ __forceinline__ double tran_time(long long gstep, double dt) { return (double)(int)gstep * dt; }   // tanalisis.cpp:256
+
+// row `row` of the probe waveforms [rows][nProbe][B] from the iterate xs
+__device__ __forceinline__ void store_probe_row(double* wave, long long row, const int32_t* probeEq, int nProbe, int B, int b,
+                                                const double* xs, int lane, int stride)
+{
+    for (int q = lane; q < nProbe; q += stride) wave[(row * nProbe + q) * (int64_t)B + b] = xs[probeEq[q]];
+}
+
 // ---- the plan's index arrays, staged in LDS.  Every Newton iteration walks them (element records in the
 // MOSFET pass, gather lists in the assembly) in short dependent chains: pointer, list entry, term.  Only the
 // packed kernels (kernels_packed.hip) stage them -- they run one wave per SIMD whatever their LDS need, and gain

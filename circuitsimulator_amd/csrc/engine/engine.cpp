@@ -107,6 +107,65 @@ int ensureBigScratch(csim_engine* eng, int B, hipStream_t hs)
     return CSIM_OK;
 }
 
+// a launch of the general kernels (kernels.hpp launchDcGeneral / launchTranGeneral) with the engine's scratch filled in
+template <class Args>
+int launchGeneral(csim_engine* eng, hipError_t (*launch)(const csim::GenPlan&, const Args&, hipStream_t),
+                  const csim::GenPlan& pl, Args a, hipStream_t hs)
+{
+    if (const int rc = ensureBigScratch(eng, a.B, hs)) return rc;
+    a.scratch = eng->dBigScratch;
+    HIPCHK(launch(pl, a, hs));
+    return CSIM_OK;
+}
+
+// planner log (device_common.hpp PIVLOG_*) -> the distinct sequences, most frequent first
+void decodePivotLog(const std::vector<int32_t>& log, int N, int32_t max_alts, int32_t* pivot_pos,
+                           int64_t* counts, int32_t* n_alts, int64_t* n_other)
+{
+    std::vector<int> order;
+    for (int s2 = 0; s2 < log[0]; ++s2) order.push_back(s2);
+    auto cnt = [&](int s2) { return log[(size_t)(3 + s2 * (N + 1) + N)]; };
+    for (size_t i = 0; i < order.size(); ++i)
+        for (size_t j = i + 1; j < order.size(); ++j)
+            if (cnt(order[j]) > cnt(order[i])) std::swap(order[i], order[j]);
+    int64_t other = log[2];
+    int out = 0;
+    for (int s2 : order) {
+        if (out < max_alts) {
+            for (int k = 0; k < N; ++k) pivot_pos[(size_t)out * N + k] = log[(size_t)(3 + s2 * (N + 1) + k)];
+            if (counts) counts[out] = cnt(s2);
+            ++out;
+        } else other += cnt(s2);
+    }
+    *n_alts = out;
+    if (n_other) *n_other = other;
+}
+
+// One planner run of the general kernels: the record `a` with a mask that names `instance` alone and a zeroed pivot
+// log attached; the sequences it logged come back decoded.
+template <class Args>
+int recordOneInstance(csim_engine* eng, hipError_t (*launch)(const csim::GenPlan&, const Args&, hipStream_t),
+                      const csim::GenPlan& pl, Args a, int32_t instance, int32_t max_alts, int32_t* pivot_pos,
+                      int64_t* counts, int32_t* n_alts, int64_t* n_other)
+{
+    const int N = eng->plan.N;
+    const int logInts = csim::pivlog_ints(N);
+    DevBuf dOnly, dLog;
+    HIPCHK(dOnly.alloc((size_t)a.B));
+    HIPCHK(dLog.alloc(sizeof(int32_t) * (size_t)logInts));
+    HIPCHK(hipMemset(dOnly.p, 0, (size_t)a.B));
+    HIPCHK(hipMemset(dLog.p, 0, sizeof(int32_t) * (size_t)logInts));
+    const unsigned char one = 1;
+    HIPCHK(hipMemcpy(dOnly.as<unsigned char>() + instance, &one, 1, hipMemcpyHostToDevice));
+    a.only = dOnly.as<uint8_t>(); a.pivLog = dLog.as<int32_t>(); a.pivInstance = instance;
+    if (const int rc = launchGeneral(eng, launch, pl, a, nullptr)) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<int32_t> log((size_t)logInts);
+    HIPCHK(hipMemcpy(log.data(), dLog.p, sizeof(int32_t) * log.size(), hipMemcpyDeviceToHost));
+    decodePivotLog(log, N, max_alts, pivot_pos, counts, n_alts, n_other);
+    return CSIM_OK;
+}
+
 // directory this shared library was loaded from
 std::string ownDirectory()
 {
@@ -599,14 +658,11 @@ int csim_dc_batch_dev(csim_engine* eng, const double* d_params, int32_t B, doubl
     hipStream_t hs = static_cast<hipStream_t>(stream);
     // the kernels with run-time pivoting: every instance, or the ones a mask names
     auto generalDc = [&](const unsigned char* only) -> int {
-        if (eng->big) {
-            const int rc = ensureBigScratch(eng, B, hs);
-            if (rc) return rc;
-            HIPCHK(csim::launchDcBig(eng->gpDc, d_params, B, eng->dBigScratch, d_x, d_iters, d_status, hs, only));
-        } else {
-            HIPCHK(csim::launchDcGeneral(eng->gpDc, d_params, B, d_x, d_iters, d_status, hs, only));
-        }
-        return CSIM_OK;
+        csim::GenDcArgs a{};
+        a.params = d_params; a.B = B;
+        a.x = d_x; a.iters = d_iters; a.status = d_status;
+        a.only = only;
+        return launchGeneral(eng, csim::launchDcGeneral, eng->gpDc, a, hs);
     };
     if (eng->schedDcLaunch && eng->kernelChoice != 1) {
         // Generated lane-per-instance kernels on the recorded DC pivot sequences, as a chain in which every
@@ -670,19 +726,14 @@ int csim_tran_batch_dev(csim_engine* eng, const double* d_params, int32_t B, dou
     const int np = d_wave ? n_probe : 0, os = d_wave ? out_stride : 1;
     // handBack: stop an instance after the first step that ran on recorded sequences only
     auto general = [&](int32_t* dDone, int maxSteps, bool handBack = false) -> int {
-        if (eng->big) {
-            const int rc = ensureBigScratch(eng, B, hs);
-            if (rc) return rc;
-            HIPCHK(csim::launchTranBig(eng->gpTran, d_params, B, tstep, step_first, n_steps, dProbe, np, os, d_wave, d_x,
-                                       reinterpret_cast<long long*>(d_iters), d_status, d_step_iters, nullptr,
-                                       eng->dBigScratch, nullptr, hs, nullptr, -1, dDone, maxSteps));
-        } else {
-            HIPCHK(csim::launchTranGeneral(eng->gpTran, d_params, B, tstep, step_first, n_steps, dProbe, np, os, d_wave, d_x,
-                                           reinterpret_cast<long long*>(d_iters), d_status, d_step_iters, nullptr, hs,
-                                           nullptr, -1, dDone, maxSteps, handBack ? eng->dKnownAlts : nullptr,
-                                           handBack ? eng->nKnownAlts : 0));
-        }
-        return CSIM_OK;
+        csim::GenTranArgs a{};
+        a.params = d_params; a.B = B; a.dt = tstep;
+        a.stepFirst = step_first; a.nSteps = n_steps;
+        a.probeEq = dProbe; a.nProbe = np; a.outStride = os; a.wave = d_wave;
+        a.x = d_x; a.iters = reinterpret_cast<long long*>(d_iters); a.status = d_status; a.stepIters = d_step_iters;
+        a.done = dDone; a.maxSteps = maxSteps;
+        if (handBack) { a.knownAlts = eng->dKnownAlts; a.nKnown = eng->nKnownAlts; }
+        return launchGeneral(eng, csim::launchTranGeneral, eng->gpTran, a, hs);
     };
     // n_steps == 0 (a run shorter than one step is legal upstream and yields the t = 0 row only): the
     // general kernel writes that row; the hybrid sequence below would return before it
@@ -1112,29 +1163,6 @@ int csim_lu_solve_batch(int32_t device, int32_t n, int32_t B, const double* A, c
     return CSIM_OK;
 }
 
-// planner log (device_common.hpp PIVLOG_*) -> the distinct sequences, most frequent first
-static void decodePivotLog(const std::vector<int32_t>& log, int N, int32_t max_alts, int32_t* pivot_pos,
-                           int64_t* counts, int32_t* n_alts, int64_t* n_other)
-{
-    std::vector<int> order;
-    for (int s2 = 0; s2 < log[0]; ++s2) order.push_back(s2);
-    auto cnt = [&](int s2) { return log[(size_t)(3 + s2 * (N + 1) + N)]; };
-    for (size_t i = 0; i < order.size(); ++i)
-        for (size_t j = i + 1; j < order.size(); ++j)
-            if (cnt(order[j]) > cnt(order[i])) std::swap(order[i], order[j]);
-    int64_t other = log[2];
-    int out = 0;
-    for (int s2 : order) {
-        if (out < max_alts) {
-            for (int k = 0; k < N; ++k) pivot_pos[(size_t)out * N + k] = log[(size_t)(3 + s2 * (N + 1) + k)];
-            if (counts) counts[out] = cnt(s2);
-            ++out;
-        } else other += cnt(s2);
-    }
-    *n_alts = out;
-    if (n_other) *n_other = other;
-}
-
 static int recordPivotSchedulesImpl(csim_engine* eng, const double* d_params, int32_t B, int32_t instance,
                                     double tstep, int64_t n_steps, int32_t max_alts, int32_t* pivot_pos,
                                     int64_t* counts, int32_t* n_alts, int64_t* n_other, uint32_t* inst_status);
@@ -1159,39 +1187,20 @@ static int recordPivotSchedulesImpl(csim_engine* eng, const double* d_params, in
     }
     HIPCHK(hipSetDevice(eng->device));
     const int N = eng->plan.N;
-    const int logInts = csim::pivlog_ints(N);
-    DevBuf dX, dIt32, dIt, dSt, dLog;
+    DevBuf dX, dIt32, dIt, dSt;
     HIPCHK(dX.alloc(sizeof(double) * (size_t)N * B));
     HIPCHK(dIt32.alloc(sizeof(int32_t) * (size_t)B));
     HIPCHK(dIt.alloc(sizeof(int64_t) * (size_t)B));
     HIPCHK(dSt.alloc(sizeof(uint32_t) * (size_t)B));
-    HIPCHK(dLog.alloc(sizeof(int32_t) * (size_t)logInts));
     HIPCHK(hipMemset(dIt.p, 0, sizeof(int64_t) * (size_t)B));
-    HIPCHK(hipMemset(dLog.p, 0, sizeof(int32_t) * (size_t)logInts));
     int rc = csim_dc_batch_dev(eng, d_params, B, dX.as<double>(), dIt32.as<int32_t>(), dSt.as<uint32_t>(), nullptr);
     if (rc) return rc;
-    // only the chosen instance runs (mask), with the pivot log attached
-    DevBuf dOnly;
-    HIPCHK(dOnly.alloc((size_t)B));
-    HIPCHK(hipMemset(dOnly.p, 0, (size_t)B));
-    const unsigned char one = 1;
-    HIPCHK(hipMemcpy(dOnly.as<unsigned char>() + instance, &one, 1, hipMemcpyHostToDevice));
-    if (eng->big) {
-        rc = ensureBigScratch(eng, B, nullptr);
-        if (rc) return rc;
-        HIPCHK(csim::launchTranBig(eng->gpTran, d_params, B, tstep, 0, n_steps, nullptr, 0, 1, nullptr, dX.as<double>(),
-                                   dIt.as<long long>(), dSt.as<uint32_t>(), nullptr, dOnly.as<uint8_t>(),
-                                   eng->dBigScratch, nullptr, nullptr, dLog.as<int32_t>(), instance));
-    } else {
-        HIPCHK(csim::launchTranGeneral(eng->gpTran, d_params, B, tstep, 0, n_steps, nullptr, 0, 1, nullptr, dX.as<double>(),
-                                       dIt.as<long long>(), dSt.as<uint32_t>(), nullptr, dOnly.as<uint8_t>(), nullptr,
-                                       dLog.as<int32_t>(), instance));
-    }
-    HIPCHK(hipDeviceSynchronize());
-    std::vector<int32_t> log((size_t)logInts);
-    HIPCHK(hipMemcpy(log.data(), dLog.p, sizeof(int32_t) * log.size(), hipMemcpyDeviceToHost));
+    csim::GenTranArgs a{};
+    a.params = d_params; a.B = B; a.dt = tstep; a.nSteps = n_steps; a.outStride = 1;
+    a.x = dX.as<double>(); a.iters = dIt.as<long long>(); a.status = dSt.as<uint32_t>();
+    rc = recordOneInstance(eng, csim::launchTranGeneral, eng->gpTran, a, instance, max_alts, pivot_pos, counts, n_alts, n_other);
+    if (rc) return rc;
     if (inst_status) HIPCHK(hipMemcpy(inst_status, dSt.as<uint32_t>() + instance, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    decodePivotLog(log, N, max_alts, pivot_pos, counts, n_alts, n_other);
     return CSIM_OK;
 }
 
@@ -1205,31 +1214,14 @@ int csim_record_dc_pivot_schedules(csim_engine* eng, const double* d_params, int
     }
     HIPCHK(hipSetDevice(eng->device));
     const int N = eng->plan.N;
-    const int logInts = csim::pivlog_ints(N);
-    DevBuf dX, dIt32, dSt, dLog, dOnly;
+    DevBuf dX, dIt32, dSt;
     HIPCHK(dX.alloc(sizeof(double) * (size_t)N * B));
     HIPCHK(dIt32.alloc(sizeof(int32_t) * (size_t)B));
     HIPCHK(dSt.alloc(sizeof(uint32_t) * (size_t)B));
-    HIPCHK(dLog.alloc(sizeof(int32_t) * (size_t)logInts));
-    HIPCHK(dOnly.alloc((size_t)B));
-    HIPCHK(hipMemset(dLog.p, 0, sizeof(int32_t) * (size_t)logInts));
-    HIPCHK(hipMemset(dOnly.p, 0, (size_t)B));
-    const unsigned char one = 1;
-    HIPCHK(hipMemcpy(dOnly.as<unsigned char>() + instance, &one, 1, hipMemcpyHostToDevice));
-    if (eng->big) {
-        const int rc = ensureBigScratch(eng, B, nullptr);
-        if (rc) return rc;
-        HIPCHK(csim::launchDcBig(eng->gpDc, d_params, B, eng->dBigScratch, dX.as<double>(), dIt32.as<int32_t>(), dSt.as<uint32_t>(),
-                                 nullptr, dOnly.as<uint8_t>(), dLog.as<int32_t>(), instance));
-    } else {
-        HIPCHK(csim::launchDcGeneral(eng->gpDc, d_params, B, dX.as<double>(), dIt32.as<int32_t>(), dSt.as<uint32_t>(), nullptr,
-                                     dOnly.as<uint8_t>(), dLog.as<int32_t>(), instance));
-    }
-    HIPCHK(hipDeviceSynchronize());
-    std::vector<int32_t> log((size_t)logInts);
-    HIPCHK(hipMemcpy(log.data(), dLog.p, sizeof(int32_t) * log.size(), hipMemcpyDeviceToHost));
-    decodePivotLog(log, N, max_alts, pivot_pos, counts, n_alts, n_other);
-    return CSIM_OK;
+    csim::GenDcArgs a{};
+    a.params = d_params; a.B = B;
+    a.x = dX.as<double>(); a.iters = dIt32.as<int32_t>(); a.status = dSt.as<uint32_t>();
+    return recordOneInstance(eng, csim::launchDcGeneral, eng->gpDc, a, instance, max_alts, pivot_pos, counts, n_alts, n_other);
 }
 
 int csim_record_pivot_schedule(csim_engine* eng, const double* d_params, int32_t B, int32_t instance,

@@ -8,53 +8,63 @@
 
 namespace csim {
 
-// wave-per-instance kernels (kernels_general.hip)
-hipError_t launchDcGeneral(const GenPlan& pl, const double* dParams, int B, double* dX,
-                           int32_t* dIters, uint32_t* dStatus, hipStream_t stream, const uint8_t* dOnly = nullptr,
-                           int32_t* dPivLog = nullptr, int pivInstance = 0);
-hipError_t launchTranGeneral(const GenPlan& pl, const double* dParams, int B, double dt,
-                             long long stepFirst, long long nSteps, const int32_t* dProbeEq, int nProbe,
-                             int outStride, double* dWave, double* dX, long long* dIters,
-                             uint32_t* dStatus, int32_t* dStepIters, const uint8_t* dOnly,
-                             hipStream_t stream, int32_t* dPivLog = nullptr, int pivInstance = -1,
-                             int32_t* dDone = nullptr, int maxSteps = 0,
-                             const int32_t* dKnownAlts = nullptr, int nKnown = 0);
+// The general DC and transient kernels (run-time pivoting, bit-faithful): one record and one launcher per analysis.
+// The launcher chooses the shape: four instances per wavefront with the matrix in registers (kernels_packed.hip)
+// when no pivot log is asked for and packedLanesFor(pl) == 16, a wavefront per instance with the matrix in LDS up
+// to 63 unknowns (kernels_general.hip), the bit-guided global-memory storage beyond that (kernels_big.hip).
+// Absent parts stay null or zero.
+struct GenDcArgs {
+    const double* params;               // [P][B]
+    int B;
+    double* x;                          // [N][B] operating points
+    int32_t* iters;                     // [B] NR passes
+    uint32_t* status;                   // [B]
+    const uint8_t* only;                // [B] or null: the instances to run (fallback and planner launches)
+    int32_t* pivLog;                    // planner log of instance pivInstance (device_common.hpp PIVLOG_*) or null
+    int pivInstance;
+    double* scratch;                    // N > 63: bigScratchBytesPerInstance(pl) zeroed bytes per instance
+};
+struct GenTranArgs {
+    const double* params;               // [P][B]
+    int B;
+    double dt;
+    long long stepFirst, nSteps;        // steps stepFirst + 1 .. stepFirst + nSteps
+    const int32_t* probeEq;             // [nProbe] equations
+    int nProbe, outStride;
+    double* wave;                       // [rows][nProbe][B] or null
+    double* x;                          // [N][B] state, in and out
+    long long* iters;                   // [B], added to
+    uint32_t* status;                   // [B], OR-ed
+    int32_t* stepIters;                 // [nSteps][B] or null
+    const uint8_t* only;                // [B] or null: the instances to run (planner launches)
+    int32_t* pivLog;                    // planner log of instance pivInstance or null
+    int pivInstance;
+    int32_t* done;                      // [B] hybrid stepping: steps of this launch completed, or null
+    int maxSteps;                       // at most this many further steps per instance (done != null)
+    const int32_t* knownAlts;           // [nKnown][N] recorded pivot sequences: hand an instance back once a whole
+    int nKnown;                         // step ran on them (N <= 63), or null
+    double* scratch;                    // N > 63, as GenDcArgs
+};
+hipError_t launchDcGeneral(const GenPlan& pl, const GenDcArgs& a, hipStream_t stream);
+hipError_t launchTranGeneral(const GenPlan& pl, const GenTranArgs& a, hipStream_t stream);
+int packedLanesFor(const GenPlan& pl);  // 16, or 64: N > 32 or four instances with the staged plan do not fit the LDS
+size_t bigScratchBytesPerInstance(const GenPlan& pl);
+int bigMaxUnknowns();
+bool bigSupports(int N, int nTerms, int P);
+
+// stand-alone batched LU (kernels_general.hip; n <= 32: four systems per wavefront, kernels_packed_lu.hip)
 hipError_t launchLuSolve(int n, int B, const double* dA, const double* dRhs, double* dX,
                          uint32_t* dFlags, double eps, hipStream_t stream);
 hipError_t launchLuFactor(int n, int B, const double* dA, double* dLU, int32_t* dPerm, uint32_t* dFlags,
                           double eps, hipStream_t stream);
-size_t generalLdsBytes(const GenPlan& pl);
-
-// the same kernels with 4 instances per wavefront and the matrix in registers for N <= 32 (kernels_packed.hip);
-// the launchers above use them whenever no pivot log is asked for
-int packedLanesFor(const GenPlan& pl);
 hipError_t launchLuSolvePacked(int n, int B, const double* dA, const double* dRhs, double* dX, uint32_t* dFlags, double eps,
                                hipStream_t stream);
-hipError_t launchDcPacked(const GenPlan& pl, const double* dParams, int B, double* dX, int32_t* dIters,
-                          uint32_t* dStatus, hipStream_t stream, const uint8_t* dOnly);
-hipError_t launchTranPacked(const GenPlan& pl, const double* dParams, int B, double dt, long long stepFirst,
-                            long long nSteps, const int32_t* dProbeEq, int nProbe, int outStride, double* dWave,
-                            double* dX, long long* dIters, uint32_t* dStatus, int32_t* dStepIters, const uint8_t* dOnly,
-                            hipStream_t stream, int32_t* dDone, int maxSteps, const int32_t* dKnownAlts, int nKnown);
 
 // dense stand-alone LU for 64 <= n <= 1024, one workgroup per system, in place (kernels_dense.hip)
 hipError_t launchLuSolveDense(int n, int B, double* dWork, const double* dRhs, double* dX, uint32_t* dFlags,
                               double eps, hipStream_t stream);
 hipError_t launchLuFactorDense(int n, int B, double* dLU, int32_t* dPerm, uint32_t* dFlags, double eps,
                                hipStream_t stream);
-
-// wave-per-instance kernels for 64 <= N <= 320 (kernels_big.hip)
-size_t bigScratchBytesPerInstance(const GenPlan& pl);
-int bigMaxUnknowns();
-bool bigSupports(int N, int nTerms, int P);
-hipError_t launchDcBig(const GenPlan& pl, const double* dParams, int B, double* dScratch, double* dX,
-                       int32_t* dIters, uint32_t* dStatus, hipStream_t stream, const uint8_t* dOnly = nullptr,
-                       int32_t* dPivLog = nullptr, int pivInstance = 0);
-hipError_t launchTranBig(const GenPlan& pl, const double* dParams, int B, double dt, long long stepFirst,
-                         long long nSteps, const int32_t* dProbeEq, int nProbe, int outStride, double* dWave,
-                         double* dX, long long* dIters, uint32_t* dStatus, int32_t* dStepIters,
-                         const uint8_t* dOnly, double* dScratch, const int32_t* dSlotOf, hipStream_t stream,
-                         int32_t* dPivLog = nullptr, int pivInstance = -1, int32_t* dDone = nullptr, int maxSteps = 0);
 
 // Gauss-Seidel solver and the DC operating point built on it (kernels_gs.hip)
 hipError_t launchGsSolve(int n, int B, const double* dAt /*[n*n][B]*/, const double* dRhs /*[n][B]*/,

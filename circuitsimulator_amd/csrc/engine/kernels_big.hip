@@ -21,7 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_common.hpp"
-#include "kernels.hpp"
+#include "general_shapes.hpp"
 
 namespace csim {
 
@@ -29,13 +29,6 @@ namespace {
 
 constexpr int BIG_MAX_N = 1024;          // register arrays below have one entry per 64 columns
 constexpr int BIG_CHUNKS = (BIG_MAX_N + 1 + 63) / 64;       // column chunks of 64 lanes (incl. RHS)
-
-__device__ __forceinline__ double clampd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ double base_gmin(const csim_consts& k, double s)
-{
-    s = clampd(s, 0.0, 1.0);
-    return k.gmin_high * (1.0 - s) + k.gmin_low * s;
-}
 
 struct BigLds {
     double* T; double* Pv; double* xs; double* xp; double* xr;
@@ -274,21 +267,19 @@ __device__ __forceinline__ bool all_finite_big(const double* v, int N, int lane)
 
 // ------------------------------------------------------------------ DC
 __global__ void __launch_bounds__(64)
-k_dc_big(GenPlan pl, const double* __restrict__ params, int B, double* __restrict__ scratch,
-         double* __restrict__ xout, int32_t* __restrict__ iters, uint32_t* __restrict__ status,
-         const uint8_t* __restrict__ only, int32_t* __restrict__ pivLog, int pivInstance)
+k_dc_big(GenPlan pl, GenDcArgs a)
 {
     extern __shared__ unsigned char smraw[];
     const int lane = threadIdx.x;
-    const int b = blockIdx.x;
-    if (only && !only[b]) return;           // fallback / planner launches touch the flagged instances only
-    int32_t* myPivLog = (pivLog && b == pivInstance) ? pivLog : nullptr;
+    const int b = blockIdx.x, B = a.B;
+    if (a.only && !a.only[b]) return;       // fallback / planner launches touch the flagged instances only
+    int32_t* myPivLog = (a.pivLog && b == a.pivInstance) ? a.pivLog : nullptr;
     const int N = pl.N;
     const BigLds L = carve(smraw, N, pl.nTerms, pl.P);
-    double* Gg = scratch + (size_t)b * N * pl.LD;
+    double* Gg = a.scratch + (size_t)b * N * pl.LD;
     const csim_consts& K = pl.k;
 
-    for (int p = lane; p < pl.P; p += 64) L.Pv[p] = params[(int64_t)p * B + b];
+    for (int p = lane; p < pl.P; p += 64) L.Pv[p] = a.params[(int64_t)p * B + b];
     for (int t = lane; t < pl.nTerms; t += 64) L.T[t] = 0.0;
     for (int i = lane; i < N; i += 64) L.xs[i] = 0.0;
     wave_sync();
@@ -326,7 +317,7 @@ k_dc_big(GenPlan pl, const double* __restrict__ params, int B, double* __restric
                     st |= CSIM_ST_DC_NONFINITE;
                     continue;
                 }
-                const double alpha = clampd(K.dc_alpha, K.dc_alpha_min, K.dc_alpha_max);
+                const double alpha = dc_alpha(K);
                 for (int i = lane; i < N; i += 64) {
                     const double xo = L.xs[i];
                     const double xn = xo + alpha * (L.xr[i] - xo);
@@ -334,12 +325,7 @@ k_dc_big(GenPlan pl, const double* __restrict__ params, int B, double* __restric
                     L.xr[i] = xn;
                 }
                 const double err = norm_big(L, L.xp, N, lane);
-                const double gb = base_gmin(K, scale);
-                double gnext = gb;
-                if (iter == 0 || !isfinite(prevErr)) gnext = gb;
-                else if (err > prevErr * K.slow_ratio) gnext = fmin(gmin * 2.0, K.gmin_abs_max);
-                else if (err < prevErr * K.fast_ratio) gnext = 0.5 * gmin + 0.5 * gb;
-                else gnext = 0.7 * gmin + 0.3 * gb;
+                const double gnext = conv_gmin_next(K, iter, err, prevErr, gmin, base_gmin(K, scale));
                 for (int i = lane; i < N; i += 64) L.xs[i] = L.xr[i];
                 wave_sync();
                 gmin = gnext;
@@ -350,54 +336,44 @@ k_dc_big(GenPlan pl, const double* __restrict__ params, int B, double* __restric
         }
     }
     wave_sync();
-    for (int i = lane; i < N; i += 64) xout[(int64_t)i * B + b] = L.xs[i];
-    if (lane == 0) { iters[b] = itTotal; status[b] = (only && !pivLog) ? (st | CSIM_ST_SCHED_FALLBACK_DC) : st; }
+    for (int i = lane; i < N; i += 64) a.x[(int64_t)i * B + b] = L.xs[i];
+    if (lane == 0) { a.iters[b] = itTotal; a.status[b] = (a.only && !a.pivLog) ? (st | CSIM_ST_SCHED_FALLBACK_DC) : st; }
 }
 
 // ------------------------------------------------------------ transient
 __global__ void __launch_bounds__(64)
-k_tran_big(GenPlan pl, const double* __restrict__ params, int B, double dt, long long stepFirst, long long nSteps,
-           const int32_t* __restrict__ probeEq, int nProbe, int outStride, double* __restrict__ wave,
-           double* __restrict__ xio, long long* __restrict__ iters, uint32_t* __restrict__ status,
-           int32_t* __restrict__ stepIters, const uint8_t* __restrict__ only, double* __restrict__ scratch,
-           const int32_t* __restrict__ slotOf, int32_t* __restrict__ pivLog, int pivInstance,
-           int32_t* __restrict__ done, int maxSteps)
+k_tran_big(GenPlan pl, GenTranArgs a)
 {
     extern __shared__ unsigned char smraw[];
     const int lane = threadIdx.x;
-    const int b = blockIdx.x;
-    if (only && !only[b]) return;
-    const long long d0 = done ? (long long)done[b] : 0;        // hybrid stepping, see kernels_general.hip
-    if (done && d0 >= nSteps) return;
-    const long long sEnd = done ? (d0 + maxSteps < nSteps ? d0 + maxSteps : nSteps) : nSteps;
+    const int b = blockIdx.x, B = a.B;
+    if (a.only && !a.only[b]) return;
+    const StepWindow w = step_window(a.done, b, a.nSteps, a.maxSteps);
+    if (a.done && w.d0 >= a.nSteps) return;
     const int N = pl.N;
     const BigLds L = carve(smraw, N, pl.nTerms, pl.P);
-    // scratch matrices are handed out per running instance: slotOf maps instance -> slot
-    const int slot = slotOf ? slotOf[b] : b;
-    double* Gg = scratch + (size_t)slot * N * pl.LD;
+    double* Gg = a.scratch + (size_t)b * N * pl.LD;
     const csim_consts& K = pl.k;
-    int32_t* myPivLog = (pivLog && b == pivInstance) ? pivLog : nullptr;
+    int32_t* myPivLog = (a.pivLog && b == a.pivInstance) ? a.pivLog : nullptr;
 
-    for (int p = lane; p < pl.P; p += 64) L.Pv[p] = params[(int64_t)p * B + b];
+    for (int p = lane; p < pl.P; p += 64) L.Pv[p] = a.params[(int64_t)p * B + b];
     for (int t = lane; t < pl.nTerms; t += 64) L.T[t] = 0.0;
-    for (int i = lane; i < N; i += 64) { const double v = xio[(int64_t)i * B + b]; L.xs[i] = v; L.xp[i] = v; }
+    for (int i = lane; i < N; i += 64) { const double v = a.x[(int64_t)i * B + b]; L.xs[i] = v; L.xp[i] = v; }
     wave_sync();
-    terms_const<true>(pl, L.Pv, L.T, dt, lane);
+    terms_const<true>(pl, L.Pv, L.T, a.dt, lane);
     if (lane == 0) L.T[pl.termGmin] = K.tran_gmin;
     wave_sync();
 
-    if (stepFirst == 0 && d0 == 0 && wave)
-        for (int q = lane; q < nProbe; q += 64) wave[((int64_t)0 * nProbe + q) * B + b] = L.xs[probeEq[q]];
+    if (a.stepFirst == 0 && w.d0 == 0 && a.wave) store_probe_row(a.wave, 0, a.probeEq, a.nProbe, B, b, L.xs, lane, 64);
 
-    unsigned st = (status[b] & CSIM_ST_TRAN_NONFINITE);
-    if (done) st |= CSIM_ST_SCHED_FALLBACK;
+    unsigned st = (a.status[b] & CSIM_ST_TRAN_NONFINITE);
+    if (a.done) st |= CSIM_ST_SCHED_FALLBACK;
     long long itTotal = 0;
     bool aborted = (st & CSIM_ST_TRAN_NONFINITE) != 0;
 
-    for (long long s = d0 + 1; s <= sEnd && !aborted; ++s) {
-        const long long gstep = stepFirst + s;
-        const double tNow = (double)(int)gstep * dt;
-        terms_step_tran(pl, L.Pv, L.T, L.xp, tNow, lane);
+    for (long long s = w.d0 + 1; s <= w.sEnd && !aborted; ++s) {
+        const long long gstep = a.stepFirst + s;
+        terms_step_tran(pl, L.Pv, L.T, L.xp, tran_time(gstep, a.dt), lane);
         wave_sync();
         int it = 0;
         for (int iter = 0; iter < K.tran_max_iters; ++iter) {
@@ -429,20 +405,19 @@ k_tran_big(GenPlan pl, const double* __restrict__ params, int B, double dt, long
             if (iter == K.tran_max_iters - 1) st |= CSIM_ST_TRAN_NONCONV;
         }
         itTotal += it;
-        if (stepIters && lane == 0) stepIters[(s - 1) * (int64_t)B + b] = it;
+        if (a.stepIters && lane == 0) a.stepIters[(s - 1) * (int64_t)B + b] = it;
         if (aborted) break;
         for (int i = lane; i < N; i += 64) L.xp[i] = L.xs[i];
         wave_sync();
-        if (wave && (gstep % outStride) == 0)
-            for (int q = lane; q < nProbe; q += 64)
-                wave[((gstep / outStride) * nProbe + q) * (int64_t)B + b] = L.xs[probeEq[q]];
+        if (a.wave && (gstep % a.outStride) == 0)
+            store_probe_row(a.wave, gstep / a.outStride, a.probeEq, a.nProbe, B, b, L.xs, lane, 64);
     }
 
-    for (int i = lane; i < N; i += 64) xio[(int64_t)i * B + b] = L.xs[i];
+    for (int i = lane; i < N; i += 64) a.x[(int64_t)i * B + b] = L.xs[i];
     if (lane == 0) {
-        iters[b] += itTotal;
-        status[b] |= st;
-        if (done) done[b] = aborted ? (int32_t)nSteps : (int32_t)sEnd;
+        a.iters[b] += itTotal;
+        a.status[b] |= st;
+        step_window_close(a.done, b, a.nSteps, aborted, w.sEnd);      // this kernel hands nothing back early
     }
 }
 
@@ -453,31 +428,18 @@ int bigMaxUnknowns() { return BIG_MAX_N; }
 // element terms, parameters, three N-vectors and the N x (N+1) bit matrix must fit one CU's LDS (160 KB)
 bool bigSupports(int N, int nTerms, int P) { return N <= BIG_MAX_N && bigLdsBytes(N, nTerms, P) <= 160 * 1024; }
 
-hipError_t launchDcBig(const GenPlan& pl, const double* dParams, int B, double* dScratch, double* dX,
-                       int32_t* dIters, uint32_t* dStatus, hipStream_t stream, const uint8_t* dOnly, int32_t* dPivLog,
-                       int pivInstance)
+template <class Args>
+static hipError_t launchBig(void (*kernel)(GenPlan, Args), const GenPlan& pl, const Args& a, hipStream_t stream)
 {
+    if (!a.scratch) return hipErrorInvalidValue;
     const size_t lds = bigLdsBytes(pl.N, pl.nTerms, pl.P);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_dc_big), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_dc_big, dim3(B), dim3(64), lds, stream, pl, dParams, B, dScratch, dX, dIters, dStatus, dOnly, dPivLog,
-                       pivInstance);
+    hipLaunchKernelGGL(kernel, dim3(a.B), dim3(64), lds, stream, pl, a);
     return hipGetLastError();
 }
 
-hipError_t launchTranBig(const GenPlan& pl, const double* dParams, int B, double dt, long long stepFirst,
-                         long long nSteps, const int32_t* dProbeEq, int nProbe, int outStride, double* dWave,
-                         double* dX, long long* dIters, uint32_t* dStatus, int32_t* dStepIters,
-                         const uint8_t* dOnly, double* dScratch, const int32_t* dSlotOf, hipStream_t stream,
-                         int32_t* dPivLog, int pivInstance, int32_t* dDone, int maxSteps)
-{
-    const size_t lds = bigLdsBytes(pl.N, pl.nTerms, pl.P);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_tran_big), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_tran_big, dim3(B), dim3(64), lds, stream, pl, dParams, B, dt, stepFirst, nSteps, dProbeEq,
-                       nProbe, outStride, dWave, dX, dIters, dStatus, dStepIters, dOnly, dScratch, dSlotOf, dPivLog,
-                       pivInstance, dDone, maxSteps);
-    return hipGetLastError();
-}
+hipError_t launchDcBig(const GenPlan& pl, const GenDcArgs& a, hipStream_t stream) { return launchBig(k_dc_big, pl, a, stream); }
+hipError_t launchTranBig(const GenPlan& pl, const GenTranArgs& a, hipStream_t stream) { return launchBig(k_tran_big, pl, a, stream); }
 
 } // namespace csim

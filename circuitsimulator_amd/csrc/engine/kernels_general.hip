@@ -16,19 +16,11 @@
 #include <hip/hip_runtime.h>
 
 #include "device_common.hpp"
-#include "kernels.hpp"
+#include "general_shapes.hpp"
 
 namespace csim {
 
 namespace {
-
-__device__ __forceinline__ double clampd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-__device__ __forceinline__ double base_gmin(const csim_consts& k, double s)
-{
-    s = clampd(s, 0.0, 1.0);
-    return k.gmin_high * (1.0 - s) + k.gmin_low * s;        // dcanalysis.hpp:45-48
-}
 
 __device__ __forceinline__ bool wave_all_finite(double v, int N, int lane)
 {
@@ -40,15 +32,13 @@ __device__ __forceinline__ bool wave_all_finite(double v, int N, int lane)
 
 // ------------------------------------------------------------------ DC (K2)
 __global__ void __launch_bounds__(64)
-k_dc_general(GenPlan pl, const double* __restrict__ params, int B,
-             double* __restrict__ xout, int32_t* __restrict__ iters, uint32_t* __restrict__ status,
-             const uint8_t* __restrict__ only, int32_t* __restrict__ pivLog, int pivInstance)
+k_dc_general(GenPlan pl, GenDcArgs a)
 {
     extern __shared__ double sm[];
     const int lane = threadIdx.x;
-    const int b = blockIdx.x;
-    if (only && !only[b]) return;           // fallback / planner launches touch the flagged instances only
-    int32_t* myPivLog = (pivLog && b == pivInstance) ? pivLog : nullptr;
+    const int b = blockIdx.x, B = a.B;
+    if (a.only && !a.only[b]) return;       // fallback / planner launches touch the flagged instances only
+    int32_t* myPivLog = (a.pivLog && b == a.pivInstance) ? a.pivLog : nullptr;
     const int N = pl.N, LD = pl.LD;
     const LdsLayout L = ldsLayout(N, LD, pl.nTerms, pl.P);
     double* Gm = sm + L.G;
@@ -58,7 +48,7 @@ k_dc_general(GenPlan pl, const double* __restrict__ params, int B,
     double* sc = sm + L.sc;
     const csim_consts& K = pl.k;
 
-    for (int p = lane; p < pl.P; p += 64) Pv[p] = params[(int64_t)p * B + b];
+    for (int p = lane; p < pl.P; p += 64) Pv[p] = a.params[(int64_t)p * B + b];
     for (int t = lane; t < pl.nTerms; t += 64) T[t] = 0.0;
     if (lane < N) xs[lane] = 0.0;
     wave_sync();
@@ -97,16 +87,10 @@ k_dc_general(GenPlan pl, const double* __restrict__ params, int B,
                     continue;
                 }
                 // ConvController::update
-                const double alpha = clampd(K.dc_alpha, K.dc_alpha_min, K.dc_alpha_max);   // :274
                 const double xo = (lane < N) ? xs[lane] : 0.0;
-                const double xn = xo + alpha * (xr - xo);               // :275
+                const double xn = xo + dc_alpha(K) * (xr - xo);         // :275
                 const double err = norm_in_order(xn - xo, sc, N, lane); // :276
-                const double gb = base_gmin(K, scale);
-                double gnext = gb;
-                if (iter == 0 || !isfinite(prevErr)) gnext = gb;                          // :280-282
-                else if (err > prevErr * K.slow_ratio) gnext = fmin(gmin * 2.0, K.gmin_abs_max);   // :285-288
-                else if (err < prevErr * K.fast_ratio) gnext = 0.5 * gmin + 0.5 * gb;     // :289-293
-                else gnext = 0.7 * gmin + 0.3 * gb;                                       // :296
+                const double gnext = conv_gmin_next(K, iter, err, prevErr, gmin, base_gmin(K, scale));
                 if (lane < N) xs[lane] = xn;                            // :145
                 wave_sync();
                 gmin = gnext;
@@ -117,34 +101,24 @@ k_dc_general(GenPlan pl, const double* __restrict__ params, int B,
         }
     }
     wave_sync();
-    if (lane < N) xout[(int64_t)lane * B + b] = xs[lane];
+    if (lane < N) a.x[(int64_t)lane * B + b] = xs[lane];
     if (lane == 0) {
-        iters[b] = itTotal;
-        status[b] = (only && !pivLog) ? (st | CSIM_ST_SCHED_FALLBACK_DC) : st;
+        a.iters[b] = itTotal;
+        a.status[b] = (a.only && !a.pivLog) ? (st | CSIM_ST_SCHED_FALLBACK_DC) : st;
     }
 }
 
 // ------------------------------------------------------------ transient (K1)
 __global__ void __launch_bounds__(64)
-k_tran_general(GenPlan pl, const double* __restrict__ params, int B, double dt,
-               long long stepFirst, long long nSteps,
-               const int32_t* __restrict__ probeEq, int nProbe, int outStride,
-               double* __restrict__ wave, double* __restrict__ xio,
-               long long* __restrict__ iters, uint32_t* __restrict__ status,
-               int32_t* __restrict__ stepIters, const uint8_t* __restrict__ only,
-               int32_t* __restrict__ pivLog, int pivInstance, int32_t* __restrict__ done, int maxSteps,
-               const int32_t* __restrict__ knownAlts, int nKnown)
+k_tran_general(GenPlan pl, GenTranArgs a)
 {
     extern __shared__ double sm[];
     const int lane = threadIdx.x;
-    const int b = blockIdx.x;
-    if (only && !only[b]) return;           // planner launches touch the chosen instance only
-    // hybrid stepping: `done` = steps of this launch each instance has completed; this kernel
-    // advances an unfinished instance by at most maxSteps and hands it back
-    const long long d0 = done ? (long long)done[b] : 0;
-    if (done && d0 >= nSteps) return;
-    const long long sEnd = done ? (d0 + maxSteps < nSteps ? d0 + maxSteps : nSteps) : nSteps;
-    int32_t* myPivLog = (pivLog && b == pivInstance) ? pivLog : nullptr;
+    const int b = blockIdx.x, B = a.B;
+    if (a.only && !a.only[b]) return;       // planner launches touch the chosen instance only
+    const StepWindow w = step_window(a.done, b, a.nSteps, a.maxSteps);
+    if (a.done && w.d0 >= a.nSteps) return;
+    int32_t* myPivLog = (a.pivLog && b == a.pivInstance) ? a.pivLog : nullptr;
     const int N = pl.N, LD = pl.LD;
     const LdsLayout L = ldsLayout(N, LD, pl.nTerms, pl.P);
     double* Gm = sm + L.G;
@@ -153,38 +127,37 @@ k_tran_general(GenPlan pl, const double* __restrict__ params, int B, double dt,
     double* xs = sm + L.xs;
     double* xp = sm + L.xp;
     double* sc = sm + L.sc;
-    int32_t* curPiv = (done && knownAlts) ? reinterpret_cast<int32_t*>(sm + L.piv) : nullptr;
+    int32_t* curPiv = (a.done && a.knownAlts) ? reinterpret_cast<int32_t*>(sm + L.piv) : nullptr;
     const csim_consts& K = pl.k;
 
-    for (int p = lane; p < pl.P; p += 64) Pv[p] = params[(int64_t)p * B + b];
+    for (int p = lane; p < pl.P; p += 64) Pv[p] = a.params[(int64_t)p * B + b];
     for (int t = lane; t < pl.nTerms; t += 64) T[t] = 0.0;
     if (lane < N) {
-        const double v = xio[(int64_t)lane * B + b];
+        const double v = a.x[(int64_t)lane * B + b];
         xs[lane] = v;
         xp[lane] = v;                       // histories come from the previous state (:139-180)
     }
     wave_sync();
-    terms_const<true>(pl, Pv, T, dt, lane);
+    terms_const<true>(pl, Pv, T, a.dt, lane);
     if (lane == 0) T[pl.termGmin] = K.tran_gmin;
     wave_sync();
 
-    if (stepFirst == 0 && d0 == 0 && wave)          // t = 0 row (:250)
-        for (int q = lane; q < nProbe; q += 64) wave[((int64_t)0 * nProbe + q) * B + b] = xs[probeEq[q]];
+    if (a.stepFirst == 0 && w.d0 == 0 && a.wave)    // t = 0 row (:250)
+        store_probe_row(a.wave, 0, a.probeEq, a.nProbe, B, b, xs, lane, 64);
 
-    unsigned st = (status[b] & CSIM_ST_TRAN_NONFINITE);
-    if (done) st |= CSIM_ST_SCHED_FALLBACK;
+    unsigned st = (a.status[b] & CSIM_ST_TRAN_NONFINITE);
+    if (a.done) st |= CSIM_ST_SCHED_FALLBACK;
     long long itTotal = 0;
     bool aborted = (st & CSIM_ST_TRAN_NONFINITE) != 0;                 // an instance the reference would have thrown on stays stopped
 
     const int slowIters = slowStepIters(K.tran_tol, K.tran_alpha, K.tran_max_iters);
-    long long sLast = d0;
-    for (long long s = d0 + 1; s <= sEnd && !aborted; ++s) {
+    long long sLast = w.d0;
+    for (long long s = w.d0 + 1; s <= w.sEnd && !aborted; ++s) {
         sLast = s;
         bool stepKnown = curPiv != nullptr;     // every factorisation of this step on a known sequence?
         bool stepConverged = false;             // a slow step (plan.hpp slowStepIters) is not handed back either
-        const long long gstep = stepFirst + s;
-        const double tNow = (double)(int)gstep * dt;                    // :256
-        terms_step_tran(pl, Pv, T, xp, tNow, lane);
+        const long long gstep = a.stepFirst + s;
+        terms_step_tran(pl, Pv, T, xp, tran_time(gstep, a.dt), lane);
         wave_sync();
         int it = 0;
         for (int iter = 0; iter < K.tran_max_iters; ++iter) {
@@ -192,7 +165,7 @@ k_tran_general(GenPlan pl, const double* __restrict__ params, int B, double dt,
             wave_sync();
             assemble(pl, T, Gm, lane);                                  // :259-356
             const double xr = lu_solve_wave(Gm, N, LD, K.lu_eps, lane, st, myPivLog, curPiv);   // :359
-            if (stepKnown) stepKnown = sequence_is_known(curPiv, knownAlts, nKnown, N, lane);
+            if (stepKnown) stepKnown = sequence_is_known(curPiv, a.knownAlts, a.nKnown, N, lane);
             ++it;
             if (!wave_all_finite(xr, N, lane)) {                        // :360-362
                 st |= CSIM_ST_TRAN_NONFINITE;
@@ -208,21 +181,20 @@ k_tran_general(GenPlan pl, const double* __restrict__ params, int B, double dt,
             if (iter == K.tran_max_iters - 1) st |= CSIM_ST_TRAN_NONCONV;   // :372-376
         }
         itTotal += it;
-        if (stepIters && lane == 0) stepIters[(s - 1) * (int64_t)B + b] = it;
+        if (a.stepIters && lane == 0) a.stepIters[(s - 1) * (int64_t)B + b] = it;
         if (aborted) break;
         if (lane < N) xp[lane] = xs[lane];                              // :381-417
         wave_sync();
-        if (wave && (gstep % outStride) == 0)                           // :419
-            for (int q = lane; q < nProbe; q += 64)
-                wave[((gstep / outStride) * nProbe + q) * (int64_t)B + b] = xs[probeEq[q]];
+        if (a.wave && (gstep % a.outStride) == 0)                       // :419
+            store_probe_row(a.wave, gstep / a.outStride, a.probeEq, a.nProbe, B, b, xs, lane, 64);
         if (stepKnown && stepConverged) break;  // back on a recorded schedule and converging: hand the instance back
     }
 
-    if (lane < N) xio[(int64_t)lane * B + b] = xs[lane];
+    if (lane < N) a.x[(int64_t)lane * B + b] = xs[lane];
     if (lane == 0) {
-        iters[b] += itTotal;
-        status[b] |= st;
-        if (done) done[b] = aborted ? (int32_t)nSteps : (int32_t)sLast;
+        a.iters[b] += itTotal;
+        a.status[b] |= st;
+        step_window_close(a.done, b, a.nSteps, aborted, sLast);
     }
 }
 
@@ -274,33 +246,31 @@ hipError_t launchLuFactor(int n, int B, const double* dA, double* dLU, int32_t* 
     return hipGetLastError();
 }
 
-hipError_t launchDcGeneral(const GenPlan& pl, const double* dParams, int B, double* dX,
-                           int32_t* dIters, uint32_t* dStatus, hipStream_t stream, const uint8_t* dOnly,
-                           int32_t* dPivLog, int pivInstance)
+// the one place that chooses the shape of a general launch (kernels.hpp)
+enum class GenShape { Packed, Wave, Big };
+static GenShape shapeFor(const GenPlan& pl, const int32_t* pivLog)
 {
-    // small circuits: several instances per wavefront (kernels_packed.hip); the planner keeps the wave per instance
-    if (!dPivLog && packedLanesFor(pl) < 64) return launchDcPacked(pl, dParams, B, dX, dIters, dStatus, stream, dOnly);
-    const LdsLayout L = ldsLayout(pl.N, pl.LD, pl.nTerms, pl.P);
-    const size_t lds = sizeof(double) * (size_t)L.total;
-    hipLaunchKernelGGL(k_dc_general, dim3(B), dim3(64), lds, stream, pl, dParams, B, dX, dIters, dStatus, dOnly,
-                       dPivLog, pivInstance);
+    if (!pivLog && packedLanesFor(pl) == 16) return GenShape::Packed;   // the planner keeps the wave per instance
+    return pl.N <= 63 ? GenShape::Wave : GenShape::Big;
+}
+
+hipError_t launchDcGeneral(const GenPlan& pl, const GenDcArgs& a, hipStream_t stream)
+{
+    const GenShape shape = shapeFor(pl, a.pivLog);
+    if (shape == GenShape::Packed) return launchDcPacked(pl, a, stream);
+    if (shape == GenShape::Big) return launchDcBig(pl, a, stream);
+    const size_t lds = sizeof(double) * (size_t)ldsLayout(pl.N, pl.LD, pl.nTerms, pl.P).total;
+    hipLaunchKernelGGL(k_dc_general, dim3(a.B), dim3(64), lds, stream, pl, a);
     return hipGetLastError();
 }
 
-hipError_t launchTranGeneral(const GenPlan& pl, const double* dParams, int B, double dt,
-                             long long stepFirst, long long nSteps, const int32_t* dProbeEq, int nProbe,
-                             int outStride, double* dWave, double* dX, long long* dIters,
-                             uint32_t* dStatus, int32_t* dStepIters, const uint8_t* dOnly,
-                             hipStream_t stream, int32_t* dPivLog, int pivInstance, int32_t* dDone, int maxSteps,
-                             const int32_t* dKnownAlts, int nKnown)
+hipError_t launchTranGeneral(const GenPlan& pl, const GenTranArgs& a, hipStream_t stream)
 {
-    if (!dPivLog && packedLanesFor(pl) < 64)
-        return launchTranPacked(pl, dParams, B, dt, stepFirst, nSteps, dProbeEq, nProbe, outStride, dWave, dX, dIters, dStatus,
-                                dStepIters, dOnly, stream, dDone, maxSteps, dKnownAlts, nKnown);
-    const LdsLayout L = ldsLayout(pl.N, pl.LD, pl.nTerms, pl.P);
-    const size_t lds = sizeof(double) * (size_t)L.total;
-    hipLaunchKernelGGL(k_tran_general, dim3(B), dim3(64), lds, stream, pl, dParams, B, dt, stepFirst, nSteps,
-                       dProbeEq, nProbe, outStride, dWave, dX, dIters, dStatus, dStepIters, dOnly, dPivLog, pivInstance, dDone, maxSteps, dKnownAlts, nKnown);
+    const GenShape shape = shapeFor(pl, a.pivLog);
+    if (shape == GenShape::Packed) return launchTranPacked(pl, a, stream);
+    if (shape == GenShape::Big) return launchTranBig(pl, a, stream);
+    const size_t lds = sizeof(double) * (size_t)ldsLayout(pl.N, pl.LD, pl.nTerms, pl.P).total;
+    hipLaunchKernelGGL(k_tran_general, dim3(a.B), dim3(64), lds, stream, pl, a);
     return hipGetLastError();
 }
 
@@ -312,11 +282,6 @@ hipError_t launchLuSolve(int n, int B, const double* dA, const double* dRhs, dou
     const size_t lds = sizeof(double) * (size_t)n * (size_t)LD;
     hipLaunchKernelGGL(k_lu_solve, dim3(B), dim3(64), lds, stream, n, LD, B, dA, dRhs, dX, dFlags, eps);
     return hipGetLastError();
-}
-
-size_t generalLdsBytes(const GenPlan& pl)
-{
-    return sizeof(double) * (size_t)ldsLayout(pl.N, pl.LD, pl.nTerms, pl.P).total;
 }
 
 } // namespace csim

@@ -65,13 +65,6 @@ k_gs_solve(int n, int B, const double* __restrict__ A, const double* __restrict_
 // ------------------------------------------------------------------ DC (GS)
 namespace {
 
-__device__ __forceinline__ double clampd_gs(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ double base_gmin_gs(const csim_consts& k, double s)
-{
-    s = clampd_gs(s, 0.0, 1.0);
-    return k.gmin_high * (1.0 - s) + k.gmin_low * s;        // dcanalysis.hpp:45-48
-}
-
 // Sweeps on the LDS system [G | I] (row-major, leading dimension LD), warm start in xs, result in
 // xr.  rowPtr/rowCol: column indices (ascending, diagonal excluded) of the entries of each row that
 // may be non-zero.  Lane 0 works; returns false when a component turned non-finite.
@@ -176,7 +169,7 @@ k_dc_gs(GenPlan pl, const int32_t* __restrict__ rowPtr, const int32_t* __restric
     } else {
         for (int step = 1; step <= K.dc_ramp_steps; ++step) {                       // :183
             const double scale = (double)step / K.dc_ramp_steps;
-            double gmin = base_gmin_gs(K, scale);                                   // :186
+            double gmin = base_gmin(K, scale);                                  // :186
             double prevErr = INFINITY;
             const int maxIterThisStep = (step == K.dc_ramp_steps) ? maxNewton * 2 : maxNewton;   // :188-191
             terms_step_dc(pl, Pv, T, scale, lane);
@@ -196,16 +189,10 @@ k_dc_gs(GenPlan pl, const int32_t* __restrict__ rowPtr, const int32_t* __restric
                     continue;
                 }
                 // ConvController::update (:268-307); it ignores alphaCurrent (:274)
-                const double alpha = clampd_gs(K.dc_alpha, K.dc_alpha_min, K.dc_alpha_max);
                 const double xo_ = (lane < N) ? xs[lane] : 0.0;
-                const double xn = xo_ + alpha * ((lane < N ? xr[lane] : 0.0) - xo_);
+                const double xn = xo_ + dc_alpha(K) * ((lane < N ? xr[lane] : 0.0) - xo_);
                 const double err = norm_in_order(xn - xo_, Gm, N, lane);            // Gm is dead here: scratch
-                const double gb = base_gmin_gs(K, scale);
-                double gnext = gb;
-                if (iter == 0 || !isfinite(prevErr)) gnext = gb;
-                else if (err > prevErr * K.slow_ratio) gnext = fmin(gmin * 2.0, K.gmin_abs_max);
-                else if (err < prevErr * K.fast_ratio) gnext = 0.5 * gmin + 0.5 * gb;
-                else gnext = 0.7 * gmin + 0.3 * gb;
+                const double gnext = conv_gmin_next(K, iter, err, prevErr, gmin, base_gmin(K, scale));
                 if (lane < N) xs[lane] = xn;                                        // :220
                 wave_sync();
                 gmin = gnext;

@@ -32,7 +32,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_common.hpp"
-#include "kernels.hpp"
+#include "general_shapes.hpp"
 
 namespace csim {
 
@@ -99,7 +99,7 @@ k_dc_packed(GenPlan plArg, const double* __restrict__ params, int B, double* __r
     const int bRaw = blockIdx.x * IPW + q;
     const bool exists = bRaw < B;
     const int b = exists ? bRaw : B - 1;
-    const bool mine = exists && !(only && !only[b]);         // fallback launches touch the flagged instances only
+    const bool mine = exists && !(only && !only[b]);     // fallback launches touch the flagged instances only
     if (!__any(mine)) return;
     const int N = plArg.N, LD = plArg.LD;
     const PackedLayout L = packedLayout(plArg);
@@ -130,7 +130,7 @@ k_dc_packed(GenPlan plArg, const double* __restrict__ params, int B, double* __r
     const int rampSteps = nonlinear ? K.dc_ramp_steps : 1, maxIters = nonlinear ? K.dc_max_iters : 1;
     for (int step = 1; step <= rampSteps; ++step) {
         const double scale = (double)step / rampSteps;
-        double gmin = nonlinear ? base_gmin_p(K, scale) : 0.0;
+        double gmin = nonlinear ? base_gmin(K, scale) : 0.0;
         double prevErr = INFINITY;
         terms_step_dc(pl, Pv, T, scale, g, G16);
         wave_sync();
@@ -153,7 +153,7 @@ k_dc_packed(GenPlan plArg, const double* __restrict__ params, int B, double* __r
             }
             const bool finite = grp_all_finite<S>(xr, N, g, q);
             // ConvController::update, computed by every group, applied by the active ones
-            const double alpha = clampd_p(K.dc_alpha, K.dc_alpha_min, K.dc_alpha_max);
+            const double alpha = dc_alpha(K);
             double xn[S], dx[S];
 #pragma unroll
             for (int s = 0; s < S; ++s) {
@@ -162,12 +162,7 @@ k_dc_packed(GenPlan plArg, const double* __restrict__ params, int B, double* __r
                 dx[s] = xn[s] - xo;
             }
             const double err = grp_norm<S>(dx, sc, N, g);
-            const double gb = base_gmin_p(K, scale);
-            double gnext = gb;
-            if (iter == 0 || !isfinite(prevErr)) gnext = gb;
-            else if (err > prevErr * K.slow_ratio) gnext = fmin(gmin * 2.0, K.gmin_abs_max);
-            else if (err < prevErr * K.fast_ratio) gnext = 0.5 * gmin + 0.5 * gb;
-            else gnext = 0.7 * gmin + 0.3 * gb;
+            const double gnext = conv_gmin_next(K, iter, err, prevErr, gmin, base_gmin(K, scale));
             if (active && !finite) {                                            // :135-138: raise gmin, drop the pass
                 gmin = fmin(gmin * K.gmin_nonfinite_mul, K.gmin_nonfinite_cap);
                 st |= CSIM_ST_DC_NONFINITE;
@@ -204,6 +199,9 @@ k_tran_packed(GenPlan plArg, const double* __restrict__ params, int B, double dt
     const int bRaw = blockIdx.x * IPW + q;
     const bool exists = bRaw < B;
     const int b = exists ? bRaw : B - 1;
+    // The hybrid window, the probe rows and the write-back of done[b] are the statements of device_common.hpp's
+    // step_window, store_probe_row and step_window_close written out: this kernel fills the register file, and
+    // through the helpers it is allocated differently and runs slower.
     const long long d0 = done ? (long long)done[b] : 0;
     const bool mine = exists && !(only && !only[b]) && !(done && d0 >= nSteps);
     if (!__any(mine)) return;
@@ -252,8 +250,7 @@ k_tran_packed(GenPlan plArg, const double* __restrict__ params, int B, double dt
         bool stepKnown = curPiv != nullptr;
         bool stepConverged = false;
         const long long gstep = stepFirst + s;
-        const double tNow = (double)(int)gstep * dt;                       // :256
-        terms_step_tran(pl, Pv, T, xp, tNow, g, G16);
+        terms_step_tran(pl, Pv, T, xp, tran_time(gstep, dt), g, G16);
         wave_sync();
         int it = 0;
         bool active = running;
@@ -299,7 +296,7 @@ k_tran_packed(GenPlan plArg, const double* __restrict__ params, int B, double dt
         if (running && !aborted)
             for (int i = g; i < N; i += G16) xp[i] = xs[i];                // :381-417
         wave_sync();
-        if (running && !aborted && wave && (gstep % outStride) == 0)       // :419
+        if (running && !aborted && wave && (gstep % outStride) == 0)   // :419
             for (int pq = g; pq < nProbe; pq += G16)
                 wave[((gstep / outStride) * nProbe + pq) * (int64_t)B + b] = xs[probeEq[pq]];
         // hybrid stepping: back on a recorded schedule and converging -> hand the instance back
@@ -325,31 +322,24 @@ int packedLanesFor(const GenPlan& pl)
     return packedLdsBytes(pl) <= kStagedLdsLimit ? 16 : 64;
 }
 
-hipError_t launchDcPacked(const GenPlan& pl, const double* dParams, int B, double* dX, int32_t* dIters,
-                          uint32_t* dStatus, hipStream_t stream, const uint8_t* dOnly)
+// The packed kernels take the record unpacked, their pointers as __restrict__ parameters: by value the register
+// allocation of k_dc_packed<2> changes.
+hipError_t launchDcPacked(const GenPlan& pl, const GenDcArgs& a, hipStream_t stream)
 {
-    if (packedLanesFor(pl) != 16) return hipErrorInvalidValue;
-    const size_t lds = packedLdsBytes(pl);
-    const dim3 grid((B + IPW - 1) / IPW);
-    if (pl.N <= 16) hipLaunchKernelGGL(k_dc_packed<1>, grid, dim3(64), lds, stream, pl, dParams, B, dX, dIters, dStatus, dOnly);
-    else hipLaunchKernelGGL(k_dc_packed<2>, grid, dim3(64), lds, stream, pl, dParams, B, dX, dIters, dStatus, dOnly);
+    if (packedLanesFor(pl) != 16 || a.pivLog) return hipErrorInvalidValue;
+    const auto kernel = pl.N <= 16 ? &k_dc_packed<1> : &k_dc_packed<2>;
+    hipLaunchKernelGGL(kernel, dim3((a.B + IPW - 1) / IPW), dim3(64), packedLdsBytes(pl), stream, pl, a.params, a.B, a.x, a.iters,
+                       a.status, a.only);
     return hipGetLastError();
 }
 
-hipError_t launchTranPacked(const GenPlan& pl, const double* dParams, int B, double dt, long long stepFirst,
-                            long long nSteps, const int32_t* dProbeEq, int nProbe, int outStride, double* dWave,
-                            double* dX, long long* dIters, uint32_t* dStatus, int32_t* dStepIters, const uint8_t* dOnly,
-                            hipStream_t stream, int32_t* dDone, int maxSteps, const int32_t* dKnownAlts, int nKnown)
+hipError_t launchTranPacked(const GenPlan& pl, const GenTranArgs& a, hipStream_t stream)
 {
-    if (packedLanesFor(pl) != 16) return hipErrorInvalidValue;
-    const size_t lds = packedLdsBytes(pl);
-    const dim3 grid((B + IPW - 1) / IPW);
-    if (pl.N <= 16)
-        hipLaunchKernelGGL(k_tran_packed<1>, grid, dim3(64), lds, stream, pl, dParams, B, dt, stepFirst, nSteps, dProbeEq,
-                           nProbe, outStride, dWave, dX, dIters, dStatus, dStepIters, dOnly, dDone, maxSteps, dKnownAlts, nKnown);
-    else
-        hipLaunchKernelGGL(k_tran_packed<2>, grid, dim3(64), lds, stream, pl, dParams, B, dt, stepFirst, nSteps, dProbeEq,
-                           nProbe, outStride, dWave, dX, dIters, dStatus, dStepIters, dOnly, dDone, maxSteps, dKnownAlts, nKnown);
+    if (packedLanesFor(pl) != 16 || a.pivLog) return hipErrorInvalidValue;
+    const auto kernel = pl.N <= 16 ? &k_tran_packed<1> : &k_tran_packed<2>;
+    hipLaunchKernelGGL(kernel, dim3((a.B + IPW - 1) / IPW), dim3(64), packedLdsBytes(pl), stream, pl, a.params, a.B, a.dt,
+                       a.stepFirst, a.nSteps, a.probeEq, a.nProbe, a.outStride, a.wave, a.x, a.iters, a.status, a.stepIters, a.only,
+                       a.done, a.maxSteps, a.knownAlts, a.nKnown);
     return hipGetLastError();
 }
 

@@ -13,13 +13,6 @@ __device__ __forceinline__ unsigned grp_mask(bool pred, int q)
     return (unsigned)((__ballot(pred) >> (q * G16)) & 0xFFFFull);
 }
 
-__device__ __forceinline__ double clampd_p(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ double base_gmin_p(const csim_consts& k, double s)
-{
-    s = clampd_p(s, 0.0, 1.0);
-    return k.gmin_high * (1.0 - s) + k.gmin_low * s;
-}
-
 // ---- cross-lane plumbing inside one DPP row of 16 lanes (= one instance)
 template <int L> __device__ __forceinline__ double row_bcast(double v)          // lane L of the row -> every lane of it
 {
