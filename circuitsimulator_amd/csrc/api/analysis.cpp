@@ -139,6 +139,29 @@ BatchStbResult BatchEngine::stb(const std::vector<double>& params, int B, const 
     return r;
 }
 
+BatchPssResult BatchEngine::pss(const std::vector<double>& params, int B, double tstep, double f0, int nHarm,
+                                const std::vector<int32_t>& probeEq, double tol, int maxRounds)
+{
+    // The engine is built from a Circuit and carries no cards, so nothing here may be left to them: the result is
+    // sized from nHarm before the call, and csim_pss_batch would take another count from a card when f0 <= 0.
+    if (!(tstep > 0.0) || !(f0 > 0.0) || nHarm < 0 || B <= 0)
+        throw std::invalid_argument("BatchEngine::pss: tstep and f0 must be positive, nHarm >= 0, B >= 1 (pass the .TRAN "
+                                    "card's step and the .HB card's numbers from SimulationConfig)");
+    BatchPssResult r;
+    r.nHarm = nHarm;
+    r.nProbe = probeEq.empty() ? numUnknowns() : static_cast<int>(probeEq.size());
+    const std::size_t nB = static_cast<std::size_t>(B > 0 ? B : 0), nH = static_cast<std::size_t>(nHarm >= 0 ? nHarm + 1 : 0);
+    r.x0.assign(nB * static_cast<std::size_t>(numUnknowns()), 0.0);
+    r.harm.assign(nB * nH * static_cast<std::size_t>(r.nProbe), std::complex<double>());
+    r.rounds.assign(nB, 0);
+    r.status.assign(nB, 0);
+    if (csim_pss_batch(eng_, params.empty() ? nullptr : params.data(), B, tstep, f0, nHarm,
+                       probeEq.empty() ? nullptr : probeEq.data(), static_cast<int>(probeEq.size()), tol, maxRounds,
+                       r.x0.data(), reinterpret_cast<double*>(r.harm.data()), r.rounds.data(), r.status.data()) != CSIM_OK)
+        fail("csim_pss_batch");
+    return r;
+}
+
 BatchSpResult BatchEngine::sp(const std::vector<double>& params, int B, const std::vector<double>& freqs, bool wantS)
 {
     BatchSpResult r;

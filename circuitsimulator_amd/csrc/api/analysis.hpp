@@ -82,6 +82,14 @@ struct BatchStbResult {
     std::vector<uint32_t> status;                 // DC and LU bits (CSIM_ST_LU_TINY_PIVOT: a singular frequency, or den == 0)
 };
 
+struct BatchPssResult {
+    int nHarm = 0, nProbe = 0;
+    std::vector<double> x0;                       // [B][N]: the state the period starts and ends at
+    std::vector<std::complex<double>> harm;       // [B][nHarm+1][nProbe]: peak phasors, cosine reference at t = 0
+    std::vector<int32_t> rounds;                  // [B]: shooting rounds used
+    std::vector<uint32_t> status;                 // DC and transient bits, CSIM_ST_PSS_NONCONV, CSIM_ST_PSS_SINGULAR
+};
+
 // One engine per (circuit, GPU).  Throws std::runtime_error when no HIP
 // device is usable: there is no CPU path.
 class BatchEngine {
@@ -135,6 +143,14 @@ public:
     // strictly increasing positive frequencies.
     BatchStbResult stb(const std::vector<double>& params, int B, const std::vector<double>& freqs, int probeElem = -1,
                        bool wantMargins = true);
+
+    // Periodic steady state of the backward-Euler transient by shooting Newton (csim_pss_batch, include/csim.h): DC
+    // operating point, then rounds of one period each; harmonics 0 .. nHarm of probeEq (empty = every unknown).
+    // tol, maxRounds <= 0: the engine's pss_tol, pss_max_rounds.  tstep and f0 must be positive (std::invalid_argument
+    // otherwise): this engine is built from a Circuit and has no cards to fall back on -- pass sim.tran.tstep,
+    // sim.hb.f0 and sim.hb.nHarm of the parsed SimulationConfig.
+    BatchPssResult pss(const std::vector<double>& params, int B, double tstep, double f0, int nHarm,
+                       const std::vector<int32_t>& probeEq = {}, double tol = 0.0, int maxRounds = 0);
 
     // the transient of instance `instance` of params ([B][P], empty = nominal) as the reference's CSV
     // (src/tanalisis.cpp:189-231); probeEq empty: the netlist's .PLOTNV/.PRINT probes when `sim` names any, else

@@ -586,6 +586,78 @@ __device__ __forceinline__ bool lu_factor_wave(double* Gm, int N, int LD, double
     return true;
 }
 
+// Gaussian elimination with partial pivoting on [Gm | M], R right-hand sides at once (periodic steady state: the
+// sensitivity update W_k = J_k^-1 (Hm W_{k-1}), kernels_pss.hip).  Gm is the N x N matrix of lu_solve_wave (its own
+// column N is left alone); M is N x R, row-major with leading dimension LDM, R <= 64: lane j owns column j of M as
+// it owns column j of Gm.  Pivot rule and multiplier skipping are lu_solve_wave's.  Back substitution per column,
+// products with U(i,l) for l ascending, zero entries of U skipped.  On return M holds Gm^-1 M; false: a pivot column
+// with maximum < eps, M is then unusable.
+__device__ __forceinline__ bool lu_solve_multi_wave(double* Gm, int N, int LD, double* M, int R, int LDM, double eps, int lane)
+{
+    for (int k = 0; k < N; ++k) {
+        double colv = (lane < N) ? Gm[lane * LD + k] : 0.0;
+        const double av = fabs(colv);
+        const double akk = read_lane(av, k);
+        int piv = k;
+        double maxAbs = akk;
+        if (akk == akk) {
+            unsigned long long cand = __ballot(lane > k && lane < N && av > 0.0);
+            while (cand) {
+                const int i = __ffsll((long long)cand) - 1;
+                cand &= cand - 1;
+                const double v = read_lane(av, i);
+                if (v > maxAbs) { maxAbs = v; piv = i; }
+            }
+        }
+        if (maxAbs < eps) return false;
+        if (piv != k) {         // swap rows k and piv of Gm (columns >= k) and of M
+            if (lane >= k && lane < N) {
+                const double a = Gm[k * LD + lane], b = Gm[piv * LD + lane];
+                Gm[k * LD + lane] = b;
+                Gm[piv * LD + lane] = a;
+            }
+            if (lane < R) {
+                const double a = M[k * LDM + lane], b = M[piv * LDM + lane];
+                M[k * LDM + lane] = b;
+                M[piv * LDM + lane] = a;
+            }
+            const double ck = read_lane(colv, k), cp = read_lane(colv, piv);
+            if (lane == k) colv = cp;
+            if (lane == piv) colv = ck;
+            wave_sync();
+        }
+        const double pivv = read_lane(colv, k);
+        const double rowv = (lane > k && lane < N) ? Gm[k * LD + lane] : 0.0;
+        const double rowm = (lane < R) ? M[k * LDM + lane] : 0.0;
+        const bool active = lane > k && lane < N && colv != 0.0;
+        const double fmine = active ? colv / pivv : 0.0;
+        unsigned long long todo = __ballot(active);
+        while (todo) {
+            const int i = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const double f = read_lane(fmine, i);
+            if (lane > k && lane < N) Gm[i * LD + lane] -= f * rowv;
+            if (lane < R) M[i * LDM + lane] -= f * rowm;
+        }
+        wave_sync();
+    }
+    for (int i = N - 1; i >= 0; --i) {
+        const double u = (lane > i && lane < N) ? Gm[i * LD + lane] : 0.0;
+        unsigned long long todo = __ballot(u != 0.0);
+        double sum = (lane < R) ? M[i * LDM + lane] : 0.0;
+        while (todo) {
+            const int l = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const double ul = read_lane(u, l);
+            if (lane < R) sum -= ul * M[l * LDM + lane];        // rows l > i of this lane's column are final
+        }
+        const double d = Gm[i * LD + i];                         // the pivot of step i: |d| >= eps
+        if (lane < R) M[i * LDM + lane] = sum / d;
+    }
+    wave_sync();
+    return true;
+}
+
 // ||v||_2 with the squares summed in index order 0..N-1 (the order of the
 // oracle's norm); sc is an N-double LDS scratch
 __device__ __forceinline__ double norm_in_order(double d, double* sc, int N, int lane)

@@ -404,6 +404,11 @@ int csim_engine_create(const csim_netlist* nl, int32_t device, csim_engine** out
         eng->stbPoints = tc.nPoints;
         eng->stbFstart = tc.fstart;
         eng->stbFstop = tc.fstop;
+        eng->hbEnabled = nl->sim.hb.enabled ? 1 : 0;
+        eng->hbF0 = nl->sim.hb.f0;
+        eng->hbNHarm = nl->sim.hb.nHarm;
+        eng->tranEnabled = nl->sim.tran.enabled ? 1 : 0;
+        eng->tranTstep = nl->sim.tran.tstep;
     }
     if (!rc) {
         for (const csim::Port& p : nl->ports) { eng->spPortEq.push_back(p.branchEq); eng->spZ0.push_back(p.z0); }
@@ -510,6 +515,16 @@ int csim_engine_set_option(csim_engine* eng, const char* key, const char* value)
     else if (k == "near_test_rollback") c.nearTestRollback = iv != 0;
     else if (k == "hybrid_sync") c.hybridSync = iv != 0;
     else if (k == "dc_fast") c.dcFast = iv != 0;
+    else if (k == "pss_tol") {
+        const double tv = std::atof(value);
+        if (!(tv > 0.0) || !std::isfinite(tv)) { setError("pss_tol must be positive and finite"); return CSIM_ERR_ARG; }
+        c.pssTol = tv;
+    }
+    else if (k == "pss_max_rounds") {
+        if (iv < 1) { setError("pss_max_rounds must be >= 1"); return CSIM_ERR_ARG; }
+        c.pssMaxRounds = iv;
+    }
+    else if (k == "pss_chunk") c.pssChunk = std::max(0, iv);
     else if (k == "ac_kernel") {
         if (v == "auto") c.acKernel = csim::AC_KERNEL_AUTO;
         else if (v == "wave") c.acKernel = csim::AC_KERNEL_WAVE;

@@ -33,6 +33,16 @@ struct EngineConfig {
                                  // 4 block (opt-in: one workgroup per system, AC and noise up to 1024 unknowns)
     bool dcFast = false;         // dc_fast        / CSIM_DC_FAST: 1 = DC operating points start on the fast generated kernel
                                  // (contraction, reciprocal pivots, guarded decisions) instead of the faithful one
+    double pssTol = 2e-6;        // pss_tol: closure ||x_K - x0||_inf of the periodic steady state.  The period-to-period
+                                 // difference of the general transient run from DC stops falling at 1.03e-9 (RC low-pass,
+                                 // 100 V), 7.0e-13 (series RLC), 5.6e-13 (common-source stage), 1.4e-12 (buffer.sp at
+                                 // 10 MHz): the jitter of sin() at a growing argument, not a floor of the map.  Four times
+                                 // the largest, 4.1e-9, would sit below what a step's own stopping rule leaves of its
+                                 // Newton iteration, (1 - tran_alpha) / tran_alpha * tran_tol = 1.22e-6: a resistive
+                                 // divider is 7.4e-7 from closure at its DC point for that reason alone.  The default is
+                                 // that residue rounded up; a tighter tol costs one more round
+    int pssMaxRounds = 20;       // pss_max_rounds: cap of the shooting rounds per call
+    int pssChunk = 0;            // pss_chunk: instances per chunk of the W_K scratch, 0 = the sweeps' ac_chunk (test aid)
 };
 
 // auxiliaries of a generated library's csim_sched_launch (same struct in the generated source, codegen.cpp)
@@ -145,6 +155,10 @@ struct csim_engine {
     // Loop-gain analysis: the netlist's .STB card; stbElem is its probe element (-2: a name the netlist does not have)
     int stbEnabled = 0, stbElem = -2, stbSweep = 0, stbPoints = 0;
     double stbFstart = 0.0, stbFstop = 0.0;
+
+    // Periodic steady state: the netlist's .HB card and the step of its .TRAN card (the defaults of csim_pss_batch)
+    int hbEnabled = 0, hbNHarm = 0, tranEnabled = 0;
+    double hbF0 = 0.0, tranTstep = 0.0;
 
     // S-parameter analysis: the netlist's .SP card and its ports in port order (branch equation, Z0); spPortError
     // says what is wrong with the PORTNUM numbering, if anything

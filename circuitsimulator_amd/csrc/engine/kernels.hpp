@@ -216,6 +216,31 @@ hipError_t launchStbSweep(int which, const StbArgs& a, hipStream_t stream);
 hipError_t launchStbMargins(int F, int B, const double* dFreqs, const double* dT, double* dMargins, int32_t* dFound,
                             hipStream_t stream);
 
+// Periodic steady state (kernels_pss.hip): one shooting round of chunk instances b0 .. b0+Bc-1 of a batch of B -- the
+// period kernel (K steps of the general transient from x0, the sensitivity W_K, the harmonics of the probes), then the
+// update kernel (closure test, x0 += (I - W_K)^-1 (x_K - x0)).  Probe equations are checked by the caller: they index LDS.
+struct PssArgs {
+    const double* params;               // [P][B]
+    int B, b0, Bc;
+    double dt;
+    int K, H;                           // steps per period, highest harmonic
+    const int32_t* probeEq;             // [nProbe] equations, or null = every unknown (nProbe = N)
+    int nProbe;
+    const double *twc, *tws;            // [K] cos and sin of 2 pi j / K
+    double tol;
+    int maxRounds;
+    double* x0;                         // [N][B] in: start of the round, out: updated
+    double* xK;                         // [N][B] scratch: the state after the period
+    double* harm;                       // [H+1][nProbe][B] complex: the harmonics of this round's period
+    double* W;                          // [Bc][N][N] scratch: W_K
+    int32_t* rounds;                    // [B] rounds used
+    uint32_t* status;                   // [B], OR-ed
+    int32_t* done;                      // [B] 0 while an instance is still shooting
+    int32_t* unfinished;                // one counter: instances that go on to another round, added to
+};
+hipError_t launchPssRound(const GenPlan& pl, const PssArgs& a, hipStream_t stream);
+size_t pssLdsBytes(const GenPlan& pl);
+
 // layout helpers (transpose.hip): [rows][cols] <-> [cols][rows] of doubles
 hipError_t launchTranspose(const double* dIn, double* dOut, int rows, int cols, hipStream_t stream);
 

@@ -269,6 +269,16 @@ int csim_netlist_stb(const csim_netlist* nl, int32_t* enabled, int32_t* elem, in
     return CSIM_OK;
 }
 
+int csim_netlist_hb(const csim_netlist* nl, int32_t* enabled, double* f0, int32_t* n_harm)
+{
+    if (!nl) return CSIM_ERR_ARG;
+    const HbConfig& a = nl->sim.hb;
+    if (enabled) *enabled = a.enabled ? 1 : 0;
+    if (f0)      *f0 = a.f0;
+    if (n_harm)  *n_harm = a.nHarm;
+    return CSIM_OK;
+}
+
 int csim_netlist_num_ports(const csim_netlist* nl)
 {
     if (!nl) return CSIM_ERR_ARG;

@@ -30,6 +30,23 @@ def ac_freqs(sweep, n_points, fstart, fstop):
     return f
 
 
+def pss_num_steps(tstep, f0):
+    """K = round(1 / (f0 tstep)), the steps of one period (csim_pss_num_steps); raises CsimError when the step does not
+    divide the period or K exceeds 2^22."""
+    K = capi.lib().csim_pss_num_steps(float(tstep), float(f0))
+    if K < 0:
+        capi.check(int(K))
+    return int(K)
+
+
+def pss_twiddles(K):
+    """The library's own table of the periodic steady state's harmonics (csim_pss_twiddles):
+    -> (cos(2 pi j / K), sin(2 pi j / K)), numpy [K] each."""
+    c, s = np.zeros(int(K)), np.zeros(int(K))
+    capi.check(capi.lib().csim_pss_twiddles(int(K), c.ctypes.data, s.ctypes.data))
+    return c, s
+
+
 class Netlist:
     """A parsed, indexed and flattened netlist (host only)."""
 
@@ -123,6 +140,13 @@ class Netlist:
         capi.check(capi.lib().csim_netlist_stb(self._h, *[C.byref(x) for x in v], C.byref(f0), C.byref(f1)))
         en, el, ep, em, eb, sw, npt = [x.value for x in v]
         return (el, ep, em, eb, AC_SWEEPS[sw], npt, f0.value, f1.value) if en else None
+
+    @property
+    def hb(self):
+        """The .HB card: None, or (f0 in Hz, n_harm)."""
+        en, f0, nh = C.c_int32(), C.c_double(), C.c_int32()
+        capi.check(capi.lib().csim_netlist_hb(self._h, C.byref(en), C.byref(f0), C.byref(nh)))
+        return (f0.value, nh.value) if en.value else None
 
     def stb_freqs(self):
         """Frequency grid of the .STB card (numpy, Hz)."""
@@ -582,6 +606,66 @@ class Engine:
         capi.check(capi.lib().csim_stb_batch(self._h, ptr(params), B, f.ctypes.data, len(f), probe, t.ctypes.data, ptr(x),
                                              ptr(mg), ptr(fd), st.ctypes.data))
         return self._stb_dict(f, t, x, mg, fd, st, 1)
+
+    def _pss_args(self, tstep, f0, n_harm, probes, tol, max_rounds):
+        """-> (tstep, f0, n_harm, probe array or None, n_probe, tol, max_rounds) with the cards' values filled in, so the
+        output shapes are known (a non-positive tstep or f0 means the card, as in the C entry: the library would
+        otherwise take the card's harmonic count after the outputs are sized); 0 asks the library for an engine option"""
+        if f0 is not None and not float(f0) > 0.0 and np.isfinite(float(f0)):
+            f0, n_harm = None, None
+        if tstep is not None and not float(tstep) > 0.0 and np.isfinite(float(tstep)):
+            tstep = None
+        if f0 is None:
+            card = self.netlist.hb
+            if card is None:
+                raise capi.CsimError(capi.CSIM_ERR_CONFIG, "no f0 given and the netlist has no .HB card")
+            f0 = card[0]
+            n_harm = card[1] if n_harm is None else n_harm
+        if n_harm is None:
+            n_harm = 0
+        if tstep is None:
+            if not self.netlist.tran_enabled:
+                raise capi.CsimError(capi.CSIM_ERR_CONFIG, "no tstep given and the netlist has no .TRAN card")
+            tstep = self.netlist.tstep
+        pe = None if probes is None else (C.c_int32 * len(probes))(*probes)
+        return (float(tstep), float(f0), int(n_harm), pe, self.N if probes is None else len(probes),
+                0.0 if tol is None else float(tol), 0 if max_rounds is None else int(max_rounds))
+
+    def pss(self, params, x0, tstep=None, f0=None, n_harm=None, probes=None, tol=None, max_rounds=None, status=None):
+        """Periodic steady state of the batch by shooting Newton (csim_pss_batch_dev), started at x0 (device [N][B],
+        normally dc()'s; not modified).  tstep None = the .TRAN card's step; f0 None = the .HB card (n_harm too);
+        probes: equation indices (None = every unknown); tol, max_rounds None = the engine options.
+        -> dict(x0 [N][B], harm complex [n_harm+1][n_probe][B] (peak phasors, cosine reference), rounds [B],
+                status [B], K); device tensors; status is OR-ed into `status` when given.  The call waits on the stream."""
+        torch = _torch()
+        B = params.shape[1]
+        tstep, f0, n_harm, pe, n_probe, tol, max_rounds = self._pss_args(tstep, f0, n_harm, probes, tol, max_rounds)
+        dev = self._dev()
+        x = x0.clone().contiguous()
+        harm = torch.zeros((max(n_harm, 0) + 1, n_probe, B, 2), dtype=torch.float64, device=dev)
+        rounds = torch.zeros(B, dtype=torch.int32, device=dev)
+        st = status if status is not None else torch.zeros(B, dtype=torch.int32, device=dev)
+        capi.check(capi.lib().csim_pss_batch_dev(self._h, params.data_ptr(), B, tstep, f0, n_harm, pe, n_probe, tol,
+                                                 max_rounds, x.data_ptr(), harm.data_ptr(), rounds.data_ptr(),
+                                                 st.data_ptr(), self._stream()))
+        K = int(capi.lib().csim_pss_num_steps(tstep, f0))
+        return dict(x0=x, harm=torch.view_as_complex(harm), rounds=rounds, status=st, K=K)
+
+    def pss_host(self, params=None, B=1, tstep=None, f0=None, n_harm=None, probes=None, tol=None, max_rounds=None):
+        """DC operating point + periodic steady state (csim_pss_batch): numpy, instance-major.
+        -> dict(x0 [B][N], harm complex [B][n_harm+1][n_probe], rounds [B], status [B], K)"""
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=np.float64)
+            B = params.shape[0]
+        tstep, f0, n_harm, pe, n_probe, tol, max_rounds = self._pss_args(tstep, f0, n_harm, probes, tol, max_rounds)
+        x = np.zeros((B, self.N))
+        harm = np.zeros((B, max(n_harm, 0) + 1, n_probe), dtype=np.complex128)
+        rounds = np.zeros(B, dtype=np.int32)
+        st = np.zeros(B, dtype=np.uint32)
+        capi.check(capi.lib().csim_pss_batch(self._h, params.ctypes.data if params is not None else None, B, tstep, f0,
+                                             n_harm, pe, n_probe, tol, max_rounds, x.ctypes.data, harm.ctypes.data,
+                                             rounds.ctypes.data, st.ctypes.data))
+        return dict(x0=x, harm=harm, rounds=rounds, status=st, K=int(capi.lib().csim_pss_num_steps(tstep, f0)))
 
     def sp(self, params, x_op, freqs=None, want_s=True, status=None):
         """S-parameter sweep of the batch around the operating points x_op (device [N][B], from dc());

@@ -208,6 +208,7 @@ int  csim_engine_set_kernel(csim_engine* eng, int32_t which);
  *   dc_fast (CSIM_DC_FAST, 0)               DC operating points start on the fast generated kernel (FMA
  *                                           contraction, reciprocal pivots; controller decisions within
  *                                           its rounding noise are replayed) instead of the faithful one
+ *   pss_tol (2e-6), pss_max_rounds (20), pss_chunk (0)  periodic steady state, see csim_pss_batch_dev
  * Unknown key or bad value: CSIM_ERR_ARG.                                                        */
 int  csim_engine_set_option(csim_engine* eng, const char* key, const char* value);
 /* Counters of one engine since its creation (-1: unknown key).  Maintained in synchronous mode
@@ -591,6 +592,66 @@ int  csim_stb_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int
  * (F ignored).  t [B][F] complex; x [B][F][2][N] complex or NULL; margins [B][4] or NULL; found [B] or NULL.          */
 int  csim_stb_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F, int32_t probe_elem,
                     double* t, double* x, double* margins, int32_t* found, uint32_t* status);
+
+/* ---- Periodic steady state (.HB f0 nharm; the reference parses the card and its steady-state source is empty) ----
+ * The periodic steady state of this engine's own backward-Euler transient, found by shooting Newton, and the harmonics
+ * 0 .. n_harm of the probes, for every instance of the batch.
+ *   h = tstep, T = 1 / f0, K = round(T / h) (csim_pss_num_steps).  PHI maps a state x at step 0 to the state after steps
+ *   1 .. K of csim_tran_batch_dev (step_first = 0, t_k = k h) on the general kernel: the reference's damped Newton with
+ *   tran_alpha, tran_tol, tran_max_iters, tran_gmin, histories from the previous state; x is the whole state.
+ * Per instance the analysis returns
+ *   x0       with || PHI(x0) - x0 ||_inf < tol
+ *   X[m][p]  m = 0 .. n_harm, probes p: X[0] = (1/K) sum_{k=1..K} x_k[p] (imaginary part 0);
+ *            X[m] = (2/K) sum_{k=1..K} x_k[p] (c[(m k) mod K] - j s[(m k) mod K]) for m >= 1, with the table
+ *            c[j] = cos(2 pi j / K), s[j] = sin(2 pi j / K) made once on the host in double (csim_pss_twiddles) and
+ *            x_k the K steps that start at the returned x0.  Peak phasors, cosine reference at t = 0:
+ *            x(t) ~ Re sum_m X[m] e^{j m 2 pi f0 t}, the convention of the distortion analysis.  Real and imaginary sums
+ *            are accumulated separately, k ascending, every product and sum rounded on its own (no FMA contraction); the
+ *            scale (1/K or 2/K, one division) multiplies the finished sum.  A numpy loop over the same table gives
+ *            the same bits.
+ *   rounds   shooting rounds used, and status.
+ * Sources are evaluated exactly as the transient's first period evaluates them (t = k h, k = 1 .. K); the analysis answers
+ * for their periodic extension.  A SIN source's fourth number is a delay in seconds, so a source whose delay lies beyond
+ * the first period is a constant to the analysis, as it is to the transient there.  A waveform whose first period does
+ * not join itself (a delayed start inside the period, a PULSE of another period) is the caller's business: the analysis
+ * runs and answers for that period repeated.
+ * One shooting round: integrate one period from x0, carrying W_k = J_k^-1 (Hm W_{k-1}), W_0 = I, where J_k is the
+ * transient matrix assembled at the converged iterate of step k and Hm = d(right-hand side)/d(x_prev), which depends on
+ * the parameters and h only; r = x_K - x0; ||r||_inf < tol: the instance is done, its x0 is kept and this round's
+ * harmonics are its result; otherwise (I - W_K) d = r by the engine's real LU and x0 += d.  The first x0 is the caller's
+ * (normally the DC operating point).
+ * Rounds: a circuit without state closes in one round, a linear circuit in two PROVIDED what the first update leaves is
+ * below tol -- each step's truncated damped iteration leaves up to (1 - tran_alpha) / tran_alpha * tran_tol = 1.22e-6
+ * whose direction follows the trajectory, and a resonant circuit carries it to x_K amplified (a series RLC of Q = 7:
+ * 2.6e-5, a third round); after that the closure falls quadratically (DESIGN.md 8h has the table).
+ * Status: the transient's own bits are OR-ed in as the transient does.  CSIM_ST_PSS_NONCONV: max_rounds reached; x0 and
+ * the harmonics of the last round are still written (that x0 is the start of the period the harmonics describe).
+ * CSIM_ST_PSS_SINGULAR: a tiny pivot in I - W_K or in a step's sensitivity solve; the instance stops.  An instance whose
+ * start vector or trajectory is not finite stops with CSIM_ST_TRAN_NONFINITE and disturbs no other.
+ * Refused before anything looks at the device: null pointers, B <= 0, n_harm < 0, numbers that are not finite, a probe
+ * equation out of range: CSIM_ERR_ARG; no f0 and no .HB card (no tstep and no .TRAN card): CSIM_ERR_CONFIG;
+ * |K h f0 - 1| > 1e-9, K < 2 n_harm + 1 or K > 2^22 (the cap bounds the table and keeps the step time's int cast
+ * safe; buffer.sp's own card, .hb 1e-2 3 at its .TRAN step, falls under it): CSIM_ERR_CONFIG; more than 63 unknowns:
+ * CSIM_ERR_UNSUPPORTED.
+ * csim_pss_batch_dev: probe_eq host [n_probe] or NULL = every unknown; tol, max_rounds <= 0: the engine options pss_tol,
+ * pss_max_rounds.  d_x0 [N][B] in: start, out: steady state; d_harm [n_harm+1][n_probe][B] complex; d_rounds [B];
+ * d_status [B], OR-ed.  It runs at most max_rounds rounds and after each reads back one counter of unfinished instances,
+ * so UNLIKE THE SWEEPS THIS ENTRY WAITS ON THE STREAM; it returns with the results complete.
+ * csim_pss_batch: DC operating point first.  params [B][P] or NULL (nominal); tstep <= 0: the .TRAN card's step;
+ * f0 <= 0: the .HB card's f0 and n_harm; x0_out [B][N] or NULL; harm_out [B][n_harm+1][n_probe] complex; rounds, status
+ * [B] or NULL.  Engine options: pss_tol (2e-6: what a step's stopping rule may leave of its own Newton iteration,
+ * (1 - tran_alpha) / tran_alpha * tran_tol = 1.22e-6, rounded up; the transient's measured period-to-period floor lies far
+ * below it), pss_max_rounds (20, a cap), pss_chunk (test aid: instances per chunk of the W_K scratch,
+ * 0 = ac_chunk).  The exact order of every operation the analysis adds to the transient: engine/pss.hpp. */
+int  csim_netlist_hb(const csim_netlist* nl, int32_t* enabled, double* f0, int32_t* n_harm);
+int64_t csim_pss_num_steps(double tstep, double f0);            /* K, or < 0: CSIM_ERR_ARG / CSIM_ERR_CONFIG */
+int  csim_pss_twiddles(int64_t K, double* cos_out /*[K]*/, double* sin_out /*[K]*/);
+int  csim_pss_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int32_t B, double tstep, double f0,
+                        int32_t n_harm, const int32_t* probe_eq /*host*/, int32_t n_probe, double tol, int32_t max_rounds,
+                        double* d_x0 /*[N][B]*/, double* d_harm, int32_t* d_rounds, uint32_t* d_status, void* stream);
+int  csim_pss_batch(csim_engine* eng, const double* params, int32_t B, double tstep, double f0, int32_t n_harm,
+                    const int32_t* probe_eq, int32_t n_probe, double tol, int32_t max_rounds, double* x0_out,
+                    double* harm_out, int32_t* rounds, uint32_t* status);
 
 /* Batched dense solve A x = b with the engine's pivoted LU
  * (Solver::solveLinearSystemLU semantics: first-maximum partial pivoting,
