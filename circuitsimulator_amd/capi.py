@@ -32,6 +32,7 @@ ST_SCHED_FAITHFUL = 0x0100
 ST_LU_ZERO_DIAG = 0x0040
 ST_PSS_NONCONV = 0x0200
 ST_PSS_SINGULAR = 0x0400
+ST_PAC_SINGULAR = 0x0800
 
 # every symbol include/csim.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _u64, _dbl, _cp = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_double, C.c_char_p
@@ -83,6 +84,9 @@ PROTOTYPES = {
     "csim_pss_twiddles": (C.c_int, [_i64, _vp, _vp]),
     "csim_pss_batch_dev": (C.c_int, [_vp, _vp, _i32, _dbl, _dbl, _i32, _vp, _i32, _dbl, _i32, _vp, _vp, _vp, _vp, _vp]),
     "csim_pss_batch": (C.c_int, [_vp, _vp, _i32, _dbl, _dbl, _i32, _vp, _i32, _dbl, _i32, _vp, _vp, _vp, _vp]),
+    "csim_netlist_pac": (C.c_int, [_vp, _pi32, _pi32, _pi32, _pdbl, _pdbl, _pi32]),
+    "csim_pac_batch_dev": (C.c_int, [_vp, _vp, _i32, _dbl, _dbl, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "csim_pac_batch": (C.c_int, [_vp, _vp, _i32, _dbl, _dbl, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "csim_netlist_num_ports": (C.c_int, [_vp]),
     "csim_netlist_port": (C.c_int, [_vp, _i32, _pi32, _pi32, _pdbl]),
     "csim_netlist_sp": (C.c_int, [_vp, _pi32, _pi32, _pi32, _pdbl, _pdbl]),

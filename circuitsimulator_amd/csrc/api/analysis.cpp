@@ -162,6 +162,28 @@ BatchPssResult BatchEngine::pss(const std::vector<double>& params, int B, double
     return r;
 }
 
+BatchPacResult BatchEngine::pac(const std::vector<double>& params, int B, double tstep, double f0,
+                                const std::vector<double>& freqs, int nSide, const std::vector<int32_t>& probeEq)
+{
+    if (!(tstep > 0.0) || !(f0 > 0.0) || freqs.empty() || nSide < 0 || B <= 0)
+        throw std::invalid_argument("BatchEngine::pac: tstep and f0 must be positive, freqs not empty, nSide >= 0, B >= 1 "
+                                    "(pass the .TRAN, .HB and .PAC cards' numbers from SimulationConfig)");
+    BatchPacResult r;
+    r.nSide = nSide;
+    r.nProbe = probeEq.empty() ? numUnknowns() : static_cast<int>(probeEq.size());
+    r.freqs = freqs;
+    const std::size_t nB = static_cast<std::size_t>(B);
+    r.p.assign(nB * freqs.size() * static_cast<std::size_t>(2 * nSide + 1) * static_cast<std::size_t>(r.nProbe), std::complex<double>());
+    r.x0.assign(nB * static_cast<std::size_t>(numUnknowns()), 0.0);
+    r.rounds.assign(nB, 0);
+    r.status.assign(nB, 0);
+    if (csim_pac_batch(eng_, params.empty() ? nullptr : params.data(), B, tstep, f0, freqs.data(), static_cast<int>(freqs.size()),
+                       nSide, probeEq.empty() ? nullptr : probeEq.data(), static_cast<int>(probeEq.size()),
+                       reinterpret_cast<double*>(r.p.data()), r.x0.data(), r.rounds.data(), r.status.data()) != CSIM_OK)
+        fail("csim_pac_batch");
+    return r;
+}
+
 BatchSpResult BatchEngine::sp(const std::vector<double>& params, int B, const std::vector<double>& freqs, bool wantS)
 {
     BatchSpResult r;

@@ -90,6 +90,15 @@ struct BatchPssResult {
     std::vector<uint32_t> status;                 // DC and transient bits, CSIM_ST_PSS_NONCONV, CSIM_ST_PSS_SINGULAR
 };
 
+struct BatchPacResult {
+    int nSide = 0, nProbe = 0;
+    std::vector<double> freqs;                    // [F] Hz: the input frequencies
+    std::vector<std::complex<double>> p;          // [B][F][2 nSide + 1][nProbe]: transfer to f + m f0 at index m + nSide
+    std::vector<double> x0;                       // [B][N]: the start of the orbit the analysis linearised around
+    std::vector<int32_t> rounds;                  // [B]: shooting rounds the steady state used
+    std::vector<uint32_t> status;                 // DC, transient and steady-state bits, CSIM_ST_PAC_SINGULAR
+};
+
 // One engine per (circuit, GPU).  Throws std::runtime_error when no HIP
 // device is usable: there is no CPU path.
 class BatchEngine {
@@ -151,6 +160,13 @@ public:
     // sim.hb.f0 and sim.hb.nHarm of the parsed SimulationConfig.
     BatchPssResult pss(const std::vector<double>& params, int B, double tstep, double f0, int nHarm,
                        const std::vector<int32_t>& probeEq = {}, double tol = 0.0, int maxRounds = 0);
+
+    // Periodic AC analysis (csim_pac_batch, include/csim.h): DC operating point, periodic steady state, then the
+    // transfer from the `AC mag [phase]` sources to probeEq (empty = every unknown) at the sidebands f + m f0,
+    // m = -nSide .. nSide, of every input frequency of freqs (Hz).  tstep and f0 must be positive and freqs not empty
+    // (std::invalid_argument otherwise), for the reason given at pss(): pass the cards' numbers from SimulationConfig.
+    BatchPacResult pac(const std::vector<double>& params, int B, double tstep, double f0, const std::vector<double>& freqs,
+                       int nSide = 1, const std::vector<int32_t>& probeEq = {});
 
     // the transient of instance `instance` of params ([B][P], empty = nominal) as the reference's CSV
     // (src/tanalisis.cpp:189-231); probeEq empty: the netlist's .PLOTNV/.PRINT probes when `sim` names any, else

@@ -3,8 +3,8 @@
 //   whose first non-blank is '*' or ';' is a comment; a leading '+' continues
 //   the previous logical line; tokens split on blanks.
 //   Devices by first letter (any case): R C L V I M.   Cards: .MODEL (read in
-//   a first pass, so it may follow its users) .TRAN .OP .DC .AC .NOISE .SP .HB .PRINT
-//   .PLOTNV .PLOTNC; anything else is reported and skipped.
+//   a first pass, so it may follow its users) .TRAN .OP .DC .AC .NOISE .SP .DISTO .STB .HB .PAC
+//   .PRINT .PLOTNV .PLOTNC; anything else is reported and skipped.
 #include "parser.hpp"
 
 #include <algorithm>
@@ -13,6 +13,7 @@
 #include <fstream>
 #include <iostream>
 #include <sstream>
+#include <stdexcept>
 
 namespace {
 
@@ -428,6 +429,7 @@ void NetlistParser::dotCard(const Statement& st)
     else if (head == ".print")  printCard(st);
     else if (head == ".model")  modelCard(st);
     else if (head == ".hb")     hbCard(st);
+    else if (head == ".pac")    pacCard(st);
     else if (head == ".plotnv") plotNvCard(st);
     else if (head == ".plotnc") plotNcCard(st);
     else std::cerr << "Line " << st.lineNo << ": unsupported control card: " << st.raw << "\n";
@@ -649,6 +651,35 @@ void NetlistParser::hbCard(const Statement& st)
     }
     cfg.enabled = true;
     sim.hb = cfg;
+}
+
+// .PAC {LIN|DEC|OCT} npoints fstart fstop [nside]   (nside defaults to 1; any other token count is an error)
+void NetlistParser::pacCard(const Statement& st)
+{
+    const auto& t = st.tokens;
+    const std::string sweep = t.size() > 1 ? toLower(t[1]) : std::string();
+    if ((t.size() != 5 && t.size() != 6) || (sweep != "lin" && sweep != "oct" && sweep != "dec")) {
+        std::cerr << "Line " << st.lineNo << ": invalid .PAC syntax: " << st.raw << "\n";
+        return;
+    }
+    PacConfig cfg;
+    cfg.sweepType = sweep == "lin" ? AcSweepType::LIN : (sweep == "oct" ? AcSweepType::OCT : AcSweepType::DEC);
+    try {
+        cfg.nPoints = std::stoi(t[2]);
+        cfg.fstart  = parseSpiceNumber(t[3]);
+        cfg.fstop   = parseSpiceNumber(t[4]);
+        if (t.size() == 6) {
+            std::size_t used = 0;
+            cfg.nSide = std::stoi(t[5], &used);
+            if (used != t[5].size() || cfg.nSide < 0) throw std::invalid_argument("nside must be a whole number >= 0");
+        }
+    } catch (const std::exception& e) {
+        std::cerr << "Line " << st.lineNo << ": cannot parse .PAC arguments: " << e.what()
+                  << " in '" << st.raw << "'\n";
+        return;
+    }
+    cfg.enabled = true;
+    sim.pac = cfg;
 }
 
 // V(n) | V(n1,n2) | I(elem)

@@ -189,6 +189,15 @@ struct HbConfig {
     int nHarm = 0;
 };
 
+// .PAC {DEC|OCT|LIN} n fstart fstop [nside]
+struct PacConfig {
+    bool enabled = false;
+    AcSweepType sweepType = AcSweepType::DEC;
+    int nPoints = 0;
+    double fstart = 0.0, fstop = 0.0;
+    int nSide = 1;                  // sidebands -nSide .. nSide around the input frequency
+};
+
 struct ProbeSpec {
     ProbeKind kind = ProbeKind::NodeVoltage;
     std::string expr;
@@ -212,6 +221,7 @@ public:
     DistoConfig disto;
     StbConfig stb;
     HbConfig hb;
+    PacConfig pac;
     std::vector<PrintCommand> printCommands;
 
     bool hasAnyAnalysis() const

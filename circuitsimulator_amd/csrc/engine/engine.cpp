@@ -409,6 +409,13 @@ int csim_engine_create(const csim_netlist* nl, int32_t device, csim_engine** out
         eng->hbNHarm = nl->sim.hb.nHarm;
         eng->tranEnabled = nl->sim.tran.enabled ? 1 : 0;
         eng->tranTstep = nl->sim.tran.tstep;
+        const PacConfig& pc = nl->sim.pac;
+        eng->pacEnabled = pc.enabled ? 1 : 0;
+        eng->pacSweep = pc.sweepType == AcSweepType::DEC ? 0 : (pc.sweepType == AcSweepType::OCT ? 1 : 2);
+        eng->pacPoints = pc.nPoints;
+        eng->pacFstart = pc.fstart;
+        eng->pacFstop = pc.fstop;
+        eng->pacNSide = pc.nSide;
     }
     if (!rc) {
         for (const csim::Port& p : nl->ports) { eng->spPortEq.push_back(p.branchEq); eng->spZ0.push_back(p.z0); }

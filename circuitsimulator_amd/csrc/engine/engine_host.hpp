@@ -35,4 +35,8 @@ int stageParams(csim_engine* eng, const double* params, int B, DevBuf& dParams);
 // most instances per chunk of the frequency-domain sweeps, csim_engine_stat("ac_chunk") (engine_freq.cpp)
 size_t acChunkCap(const csim_engine* eng);
 
+// instances per chunk of the W_K scratch of the periodic steady state and the periodic AC analysis: the option
+// pss_chunk, else the sweeps' chunk (engine_pss.cpp)
+int pssChunk(const csim_engine* eng, int B);
+
 } // namespace csim

@@ -160,6 +160,10 @@ struct csim_engine {
     int hbEnabled = 0, hbNHarm = 0, tranEnabled = 0;
     double hbF0 = 0.0, tranTstep = 0.0;
 
+    // Periodic AC analysis: the netlist's .PAC card (the defaults of csim_pac_batch)
+    int pacEnabled = 0, pacSweep = 0, pacPoints = 0, pacNSide = 1;
+    double pacFstart = 0.0, pacFstop = 0.0;
+
     // S-parameter analysis: the netlist's .SP card and its ports in port order (branch equation, Z0); spPortError
     // says what is wrong with the PORTNUM numbering, if anything
     int spEnabled = 0, spSweep = 0, spPoints = 0;

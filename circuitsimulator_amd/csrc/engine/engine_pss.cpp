@@ -70,13 +70,13 @@ int pssResolve(const csim_engine* eng, const char* who, bool cardDefaults, doubl
     return CSIM_OK;
 }
 
-int pssChunk(const csim_engine* eng, int B)
+} // namespace
+
+int csim::pssChunk(const csim_engine* eng, int B)
 {
     const size_t cap = eng->cfg.pssChunk > 0 ? (size_t)eng->cfg.pssChunk : csim::acChunkCap(eng);
     return (int)std::min<size_t>((size_t)B, cap);
 }
-
-} // namespace
 
 extern "C" {
 
@@ -107,7 +107,7 @@ int csim_pss_batch_dev(csim_engine* eng, const double* d_params, int32_t B, doub
     HIPCHK(hipSetDevice(eng->device));
     hipStream_t hs = static_cast<hipStream_t>(stream);
     const int N = eng->plan.N;
-    const int chunk = pssChunk(eng, B);
+    const int chunk = csim::pssChunk(eng, B);
 
     std::vector<double> tw(2 * (size_t)p.K);
     csim::pss_twiddles(p.K, tw.data(), tw.data() + p.K);

@@ -239,7 +239,42 @@ struct PssArgs {
     int32_t* unfinished;                // one counter: instances that go on to another round, added to
 };
 hipError_t launchPssRound(const GenPlan& pl, const PssArgs& a, hipStream_t stream);
+// the period kernel alone (no update): x_K and W_K of the period that starts at x0; H = 0 and nProbe = 0 store no harmonics
+hipError_t launchPssPeriod(const GenPlan& pl, const PssArgs& a, hipStream_t stream);
 size_t pssLdsBytes(const GenPlan& pl);
+
+// Periodic AC analysis (kernels_pac.hip) of chunk instances b0 .. b0+Bc-1 of a batch of B at Fc <= 32 frequencies:
+// the period kernel integrates the orbit from x0 as the periodic steady state does and carries the Fc complex
+// perturbations p_k as 2 Fc real columns (re at 2 f, im at 2 f + 1) through J_k p_k = z (Hm p_{k-1}) + u; the close
+// kernel solves (I - z_K W_K) p_0 = r_K per (instance, frequency).  One launch of the period kernel with p0 == null
+// (p_0 = 0, leaves r_K), the close kernel, a second launch from that p_0 with out != null (the sideband sums).
+// Probe equations are checked by the caller: they index LDS.
+struct PacArgs {
+    const double* params;               // [P][B]
+    int B, b0, Bc;
+    double dt;
+    int K, M;                           // steps per period, sidebands -M .. M
+    int Fc, fFirst, F;                  // frequencies of this launch, the first one's index among the F of the call
+    const int32_t* probeEq;             // [nProbe] equations, or null = every unknown (nProbe = N)
+    int nProbe;
+    const double *twc, *tws;            // [K] cos and sin of 2 pi j / K
+    const double *acRe, *acIm;          // [nElem] the AC excitation of the sources
+    const double *zr, *zi;              // [Fc] z of this launch's frequencies
+    const double *zKr, *zKi;            // [Fc] z_K (close kernel)
+    const double* x0;                   // [N][B] start of the period, not modified
+    const double* W;                    // [Bc][N][N] W_K (close kernel)
+    const uint32_t* wStatus;            // [B] status of the launch that made W_K
+    const double* p0;                   // [Bc][N][2 Fc] start of the recursion, or null = zero
+    double* pK;                         // [Bc][N][2 Fc]: period kernel p_K out; close kernel r_K in, p_0 out (in place)
+    double* out;                        // [F][2 M + 1][nProbe][B] complex or null: the sideband transfers
+    int32_t* stop;                      // [Bc] scratch, zeroed per frequency chunk: instances that stopped
+    uint32_t* status;                   // [B], OR-ed
+};
+// bytes of dynamic LDS of the period kernel at Fc frequencies; pacMaxFc: the largest Fc <= 32 that fits, 0 = none
+size_t pacLdsBytes(const GenPlan& pl, int Fc, int M, int nProbe);
+int pacMaxFc(const GenPlan& pl, int M, int nProbe);
+hipError_t launchPacPeriod(const GenPlan& pl, const PacArgs& a, hipStream_t stream);
+hipError_t launchPacClose(const GenPlan& pl, const PacArgs& a, hipStream_t stream);
 
 // layout helpers (transpose.hip): [rows][cols] <-> [cols][rows] of doubles
 hipError_t launchTranspose(const double* dIn, double* dOut, int rows, int cols, hipStream_t stream);

@@ -18,45 +18,11 @@
 #include "device_common.hpp"
 #include "kernels.hpp"
 #include "pss.hpp"
+#include "pss_device.hpp"
 
 namespace csim {
 
 namespace {
-
-__device__ __forceinline__ bool pss_all_finite(double v, int N, int lane)
-{
-    const bool bad = (lane < N) && !isfinite(v);
-    return __ballot(bad) == 0ull;
-}
-
-// the right-hand side alone, as assemble() forms it: out[0 .. N-1]
-__device__ __forceinline__ void pss_rhs(const GenPlan& pl, const double* T, double* out, int lane)
-{
-    if (lane < pl.N) out[lane] = 0.0;
-    wave_sync();
-    for (int n = lane; n < pl.nnzI; n += 64) {
-        double acc = 0.0;
-        for (int c = pl.iPtr[n]; c < pl.iPtr[n + 1]; ++c) {
-            const int con = pl.iCon[c];
-            const double v = T[con >> 1];
-            acc = (con & 1) ? acc - v : acc + v;
-        }
-        out[pl.iRow[n]] = acc;
-    }
-    wave_sync();
-}
-
-// the history terms at xp with every source at zero
-__device__ __forceinline__ void pss_terms_history(const GenPlan& pl, const double* Pv, double* T, const double* xp, int lane)
-{
-    terms_step_tran(pl, Pv, T, xp, 0.0, lane);
-    wave_sync();
-    for (int e = lane; e < pl.nElem; e += 64) {
-        const int kind = pl.kind[e];
-        if (kind == CSIM_V || kind == CSIM_I) T[pl.termBase[e] + T_SRC_VAL] = 0.0;
-    }
-    wave_sync();
-}
 
 __device__ __forceinline__ size_t pss_harm_at(const PssArgs& a, int idx, int b) { return 2 * ((size_t)idx * (size_t)a.B + (size_t)b); }
 
@@ -250,7 +216,7 @@ size_t pssLdsBytes(const GenPlan& pl)
     return sizeof(double) * ((size_t)ldsLayout(pl.N, pl.LD, pl.nTerms, pl.P).total + 2 * (size_t)pl.N * (size_t)pl.N);
 }
 
-hipError_t launchPssRound(const GenPlan& pl, const PssArgs& a, hipStream_t stream)
+hipError_t launchPssPeriod(const GenPlan& pl, const PssArgs& a, hipStream_t stream)
 {
     if (pl.N < 1 || pl.N > 63) return hipErrorInvalidValue;
     const size_t lds = pssLdsBytes(pl);
@@ -259,7 +225,12 @@ hipError_t launchPssRound(const GenPlan& pl, const PssArgs& a, hipStream_t strea
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_pss_period, dim3(a.Bc), dim3(64), lds, stream, pl, a);
-    hipError_t e = hipGetLastError();
+    return hipGetLastError();
+}
+
+hipError_t launchPssRound(const GenPlan& pl, const PssArgs& a, hipStream_t stream)
+{
+    hipError_t e = launchPssPeriod(pl, a, stream);
     if (e != hipSuccess) return e;
     const size_t ldsU = sizeof(double) * ((size_t)pl.N * pl.LD + (size_t)pl.N);
     hipLaunchKernelGGL(k_pss_update, dim3(a.Bc), dim3(64), ldsU, stream, pl.N, pl.LD, pl.k.lu_eps, a);

@@ -279,6 +279,20 @@ int csim_netlist_hb(const csim_netlist* nl, int32_t* enabled, double* f0, int32_
     return CSIM_OK;
 }
 
+int csim_netlist_pac(const csim_netlist* nl, int32_t* enabled, int32_t* sweep, int32_t* n_points, double* fstart,
+                     double* fstop, int32_t* n_side)
+{
+    if (!nl) return CSIM_ERR_ARG;
+    const PacConfig& a = nl->sim.pac;
+    if (enabled)  *enabled = a.enabled ? 1 : 0;
+    if (sweep)    *sweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
+    if (n_points) *n_points = a.nPoints;
+    if (fstart)   *fstart = a.fstart;
+    if (fstop)    *fstop = a.fstop;
+    if (n_side)   *n_side = a.enabled ? a.nSide : 0;
+    return CSIM_OK;
+}
+
 int csim_netlist_num_ports(const csim_netlist* nl)
 {
     if (!nl) return CSIM_ERR_ARG;

@@ -148,6 +148,22 @@ class Netlist:
         capi.check(capi.lib().csim_netlist_hb(self._h, C.byref(en), C.byref(f0), C.byref(nh)))
         return (f0.value, nh.value) if en.value else None
 
+    @property
+    def pac(self):
+        """The .PAC card: None, or (sweep "dec" | "oct" | "lin", n_points, fstart, fstop, n_side)."""
+        en, sw, npt, ns = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        f0, f1 = C.c_double(), C.c_double()
+        capi.check(capi.lib().csim_netlist_pac(self._h, C.byref(en), C.byref(sw), C.byref(npt), C.byref(f0), C.byref(f1),
+                                               C.byref(ns)))
+        return (AC_SWEEPS[sw.value], npt.value, f0.value, f1.value, ns.value) if en.value else None
+
+    def pac_freqs(self):
+        """Frequency grid of the .PAC card (numpy, Hz)."""
+        card = self.pac
+        if card is None:
+            raise capi.CsimError(capi.CSIM_ERR_CONFIG, "the netlist has no .PAC card")
+        return ac_freqs(*card[:4])
+
     def stb_freqs(self):
         """Frequency grid of the .STB card (numpy, Hz)."""
         card = self.stb
@@ -666,6 +682,57 @@ class Engine:
                                              n_harm, pe, n_probe, tol, max_rounds, x.ctypes.data, harm.ctypes.data,
                                              rounds.ctypes.data, st.ctypes.data))
         return dict(x0=x, harm=harm, rounds=rounds, status=st, K=int(capi.lib().csim_pss_num_steps(tstep, f0)))
+
+    def _pac_args(self, freqs, n_side, tstep, f0, probes):
+        """-> (freqs, n_side, tstep, f0, probe array or None, n_probe) with the cards' values filled in, so the output
+        shapes are known; a non-positive tstep or f0 means the card, as in the C entry"""
+        tstep, f0, _, pe, n_probe, _, _ = self._pss_args(tstep, f0, 0, probes, None, None)
+        card = self.netlist.pac
+        if freqs is None:
+            if card is None:
+                raise capi.CsimError(capi.CSIM_ERR_ARG, "no frequencies given and the netlist has no .PAC card")
+            freqs = self.netlist.pac_freqs()
+        f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        if n_side is None:
+            n_side = card[4] if card is not None else 1
+        return f, int(n_side), tstep, f0, pe, n_probe
+
+    def pac(self, params, x0, freqs=None, n_side=None, tstep=None, f0=None, probes=None, status=None):
+        """Periodic AC analysis of the batch around the orbit that starts at x0 (device [N][B], normally pss()["x0"]; not
+        modified): csim_pac_batch_dev.  freqs: input frequencies in Hz, None = the .PAC card; n_side None = the card's
+        (1 without one); tstep None = the .TRAN card's step; f0 None = the .HB card's; probes: equation indices
+        (None = every unknown).
+        -> dict(freqs, p complex [F][2 n_side + 1][n_probe][B] (the transfer from the AC sources to the sideband
+                f + m f0 at index m + n_side), status [B], K, n_side); device tensors; status is OR-ed into `status` when
+        given.  The call waits on the stream."""
+        torch = _torch()
+        B = params.shape[1]
+        f, n_side, tstep, f0, pe, n_probe = self._pac_args(freqs, n_side, tstep, f0, probes)
+        dev = self._dev()
+        x = x0.contiguous()
+        out = torch.zeros((len(f), 2 * max(n_side, 0) + 1, n_probe, B, 2), dtype=torch.float64, device=dev)
+        st = status if status is not None else torch.zeros(B, dtype=torch.int32, device=dev)
+        capi.check(capi.lib().csim_pac_batch_dev(self._h, params.data_ptr(), B, tstep, f0, x.data_ptr(), f.ctypes.data, len(f),
+                                                 n_side, pe, n_probe, out.data_ptr(), st.data_ptr(), self._stream()))
+        return dict(freqs=f, p=torch.view_as_complex(out), status=st, K=int(capi.lib().csim_pss_num_steps(tstep, f0)),
+                    n_side=n_side)
+
+    def pac_host(self, params=None, B=1, freqs=None, n_side=None, tstep=None, f0=None, probes=None):
+        """DC operating point + periodic steady state + periodic AC analysis (csim_pac_batch): numpy, instance-major.
+        -> dict(freqs, p complex [B][F][2 n_side + 1][n_probe], x0 [B][N], rounds [B], status [B], K, n_side)"""
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=np.float64)
+            B = params.shape[0]
+        f, n_side, tstep, f0, pe, n_probe = self._pac_args(freqs, n_side, tstep, f0, probes)
+        out = np.zeros((B, len(f), 2 * max(n_side, 0) + 1, n_probe), dtype=np.complex128)
+        x = np.zeros((B, self.N))
+        rounds = np.zeros(B, dtype=np.int32)
+        st = np.zeros(B, dtype=np.uint32)
+        capi.check(capi.lib().csim_pac_batch(self._h, params.ctypes.data if params is not None else None, B, tstep, f0,
+                                             f.ctypes.data, len(f), n_side, pe, n_probe, out.ctypes.data, x.ctypes.data,
+                                             rounds.ctypes.data, st.ctypes.data))
+        return dict(freqs=f, p=out, x0=x, rounds=rounds, status=st, K=int(capi.lib().csim_pss_num_steps(tstep, f0)),
+                    n_side=n_side)
 
     def sp(self, params, x_op, freqs=None, want_s=True, status=None):
         """S-parameter sweep of the batch around the operating points x_op (device [N][B], from dc());

@@ -653,6 +653,63 @@ int  csim_pss_batch(csim_engine* eng, const double* params, int32_t B, double ts
                     const int32_t* probe_eq, int32_t n_probe, double tol, int32_t max_rounds, double* x0_out,
                     double* harm_out, int32_t* rounds, uint32_t* status);
 
+/* ---- Periodic AC analysis (.PAC): the backward-Euler transient linearised around a periodic orbit ----
+ * A small tone a e^{j 2 pi f t} on the netlist's `AC mag [phase]` sources, superposed on the large-signal orbit of
+ * "Periodic steady state", appears at every f + m f0: a mixer's conversion gain is the transfer to m = -1.  None of the
+ * analyses that linearise at a DC point can translate frequency; this one linearises the transient's step around the orbit.
+ * Carried over from the periodic steady state: h = tstep, f0, K = csim_pss_num_steps(h, f0), the table c[j], s[j].
+ * Orbit: the states x_1 .. x_K of K steps of the general transient from the given x0, integrated with the same device
+ *   functions in the same order as the periodic steady state's period, hence the same bits.  J_k is the transient matrix
+ *   assembled at the converged x_k (one more MOSFET pass and assembly), Hm = d(right-hand side)/d(x_prev) as there.
+ * Excitation: u, complex [N], is the right-hand side of the AC analysis: the source slots carry mag (cos, sin)(phase),
+ *   every history is zero.
+ * Frequency constants, for an input frequency f > 0, made on the host in double: z = cos(theta) - j sin(theta),
+ *   theta = 2 pi f h; z_K = cos(theta_K) - j sin(theta_K), theta_K = 2 pi (f / f0 - floor(f / f0)); z_K is not z powered.
+ * Recursion: with the perturbation written as dx_k = e^{j 2 pi f t_k} p_k, p periodic,
+ *     J_k p_k = z (Hm p_{k-1}) + u,  k = 1 .. K.
+ *   Operation order: q = Hm p_{k-1} row by row over the non-zero Hm(i, l), l ascending, product and sum rounded
+ *   separately, real and imaginary parts as two real columns; then re = (zr qr - zi qi) + ur, im = (zr qi + zi qr) + ui;
+ *   then the engine's real LU of J_k (first-maximum pivoting, zero multipliers skipped) on all 2 Fc columns at once.
+ *   With r_K the result from p_0 = 0, the periodic start solves the complex system (I - z_K W_K) p_0 = r_K, W_K the
+ *   periodic steady state's sensitivity of this orbit, entries ((i == j ? 1 : 0) - zKr w) + j (0 - zKi w), by the
+ *   complex LU of "AC analysis"; the recursion is run again from that p_0.
+ * Sidebands, m = -n_side .. n_side: P_m[q] = (1/K) sum_{k=1..K} p_k[q] (c[j] - j s[j]), j = ((m k) mod K + K) mod K:
+ *   re += pr c + pi s, im += pi c - pr s, k ascending, products and sums rounded separately; the scale 1/K (one
+ *   division) multiplies the finished sums.
+ * Meaning: with a e^{j 2 pi f t} on the source the response on the time grid is sum_m a P_m e^{j 2 pi (f + m f0) t}: P_m
+ *   at the output is the conversion gain to sideband m.  A linear circuit has P_0 = (J - z Hm)^-1 u, the AC solution
+ *   with j w replaced by (1 - e^{-j w h}) / h, and P_m = 0 for m != 0.
+ * Status: CSIM_ST_PAC_SINGULAR: a tiny pivot in I - z_K W_K or in a step's solve; the instance stops and its outputs
+ *   for that chunk of frequencies are zeros.  An instance whose start vector or orbit is not finite gets
+ *   CSIM_ST_TRAN_NONFINITE and zeros and disturbs no other; so does one that arrives with CSIM_ST_TRAN_NONFINITE or
+ *   CSIM_ST_PSS_SINGULAR in d_status (what the steady state leaves of an instance it gave up), zeros without a new bit.
+ *   The transient's other bits are OR-ed in as the periodic steady state does.  The device form does not check that x0
+ *   closes the period: x0 is the caller's, normally csim_pss_batch_dev's.
+ * Refused before anything looks at the device: null pointers, B <= 0, F <= 0 without a card, n_side < 0, numbers that
+ *   are not finite, a frequency <= 0, a probe equation out of range: CSIM_ERR_ARG; no f0 / tstep and no cards, K refused
+ *   as by csim_pss_num_steps, K < 2 n_side + 1, no source with an AC magnitude, sums that do not fit the LDS at one
+ *   frequency per launch: CSIM_ERR_CONFIG; more than 63 unknowns: CSIM_ERR_UNSUPPORTED.
+ * Card: `.PAC DEC|OCT|LIN n fstart fstop [nside]`, the grid of csim_ac_freqs, nside defaults to 1.  Any other token
+ *   count, or a number that does not parse, is a card error: reported, and the card is left off.
+ * csim_pac_batch_dev: freqs host [F] in Hz; probe_eq host [n_probe] or NULL = every unknown; d_x0 [N][B], not
+ *   modified; d_out [F][2 n_side + 1][n_probe][B] complex, sideband m at index m + n_side; d_status [B], OR-ed.
+ *   Frequencies go in chunks of the largest Fc <= 32 whose sums fit 160 KB of LDS, instances in the chunks of the
+ *   periodic steady state (option pss_chunk); per instance chunk one launch for W_K, per frequency chunk two period
+ *   passes around the closure solve.  LIKE csim_pss_batch_dev THIS ENTRY WAITS ON THE STREAM before it returns.
+ * csim_pac_batch: DC operating point, periodic steady state (engine options pss_tol, pss_max_rounds), then the
+ *   analysis; their status bits are OR-ed in.  params [B][P] or NULL (nominal); tstep <= 0: the .TRAN card's step;
+ *   f0 <= 0: the .HB card's f0; freqs NULL and F == 0: the .PAC card's grid (n_side is always the caller's;
+ *   csim_netlist_pac reports the card's); out [B][F][2 n_side + 1][n_probe] complex; x0_out [B][N], rounds [B],
+ *   status [B] or NULL.  The exact order of every operation the analysis adds: engine/pac.hpp. */
+int  csim_netlist_pac(const csim_netlist* nl, int32_t* enabled, int32_t* sweep, int32_t* n_points, double* fstart,
+                      double* fstop, int32_t* n_side);
+int  csim_pac_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int32_t B, double tstep, double f0,
+                        const double* d_x0 /*[N][B]*/, const double* freqs /*host [F]*/, int32_t F, int32_t n_side,
+                        const int32_t* probe_eq /*host*/, int32_t n_probe, double* d_out, uint32_t* d_status, void* stream);
+int  csim_pac_batch(csim_engine* eng, const double* params, int32_t B, double tstep, double f0, const double* freqs,
+                    int32_t F, int32_t n_side, const int32_t* probe_eq, int32_t n_probe, double* out, double* x0_out,
+                    int32_t* rounds, uint32_t* status);
+
 /* Batched dense solve A x = b with the engine's pivoted LU
  * (Solver::solveLinearSystemLU semantics: first-maximum partial pivoting,
  * tiny pivot -> zero vector).  A [B][n][n] row-major, b/x [B][n], host

@@ -156,6 +156,7 @@ static inline void csim_consts_default(csim_consts* k)
 #define CSIM_ST_SCHED_FALLBACK_DC 0x0080u /* same, for the DC operating point (informational: results are the general kernel's) */
 #define CSIM_ST_PSS_NONCONV      0x0200u  /* periodic steady state: the round cap was reached before the period closed */
 #define CSIM_ST_PSS_SINGULAR     0x0400u  /* periodic steady state: tiny pivot in I - W_K (or in a step's sensitivity solve); instance stopped */
+#define CSIM_ST_PAC_SINGULAR     0x0800u  /* periodic AC analysis: tiny pivot in I - z_K W_K (or in a step's solve); instance stopped, zeros for that frequency chunk */
 
 #ifdef __cplusplus
 }
