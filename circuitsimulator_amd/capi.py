@@ -87,6 +87,11 @@ PROTOTYPES = {
     "csim_netlist_pac": (C.c_int, [_vp, _pi32, _pi32, _pi32, _pdbl, _pdbl, _pi32]),
     "csim_pac_batch_dev": (C.c_int, [_vp, _vp, _i32, _dbl, _dbl, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "csim_pac_batch": (C.c_int, [_vp, _vp, _i32, _dbl, _dbl, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "csim_netlist_pnoise": (C.c_int, [_vp, _pi32, _pi32, _pi32, _pi32, _pi32, _pi32, _pdbl, _pdbl, _pi32]),
+    "csim_pnoise_batch_dev": (C.c_int, [_vp, _vp, _i32, _dbl, _dbl, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _vp,
+                                        _vp, _vp, _vp]),
+    "csim_pnoise_batch": (C.c_int, [_vp, _vp, _i32, _dbl, _dbl, _vp, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp]),
     "csim_netlist_num_ports": (C.c_int, [_vp]),
     "csim_netlist_port": (C.c_int, [_vp, _i32, _pi32, _pi32, _pdbl]),
     "csim_netlist_sp": (C.c_int, [_vp, _pi32, _pi32, _pi32, _pdbl, _pdbl]),

@@ -184,6 +184,31 @@ BatchPacResult BatchEngine::pac(const std::vector<double>& params, int B, double
     return r;
 }
 
+BatchPnoiseResult BatchEngine::pnoise(const std::vector<double>& params, int B, double tstep, double f0,
+                                      const std::vector<double>& freqs, int outP, int outM, int srcElem, int nSide, double tempK)
+{
+    if (!(tstep > 0.0) || !(f0 > 0.0) || freqs.empty() || nSide < 0 || B <= 0)
+        throw std::invalid_argument("BatchEngine::pnoise: tstep and f0 must be positive, freqs not empty, nSide >= 0, B >= 1 "
+                                    "(pass the .TRAN, .HB and .PNOISE cards' numbers from SimulationConfig)");
+    BatchPnoiseResult r;
+    r.nSide = nSide;
+    r.nSrc = csim_netlist_num_noise_sources(nl_);
+    r.freqs = freqs;
+    const std::size_t nB = static_cast<std::size_t>(B), nF = freqs.size(), nSb = static_cast<std::size_t>(2 * nSide + 1);
+    r.onoise.assign(nB * nF, 0.0);
+    r.gain.assign(nB * nF * nSb, std::complex<double>());
+    r.contrib.assign(nB * nF * static_cast<std::size_t>(r.nSrc), 0.0);
+    r.side.assign(nB * nF * nSb, 0.0);
+    r.x0.assign(nB * static_cast<std::size_t>(numUnknowns()), 0.0);
+    r.rounds.assign(nB, 0);
+    r.status.assign(nB, 0);
+    if (csim_pnoise_batch(eng_, params.empty() ? nullptr : params.data(), B, tstep, f0, freqs.data(), static_cast<int>(nF), nSide,
+                          outP, outM, srcElem, tempK, r.onoise.data(), srcElem >= 0 ? reinterpret_cast<double*>(r.gain.data()) : nullptr,
+                          r.contrib.data(), r.side.data(), r.x0.data(), r.rounds.data(), r.status.data()) != CSIM_OK)
+        fail("csim_pnoise_batch");
+    return r;
+}
+
 BatchSpResult BatchEngine::sp(const std::vector<double>& params, int B, const std::vector<double>& freqs, bool wantS)
 {
     BatchSpResult r;

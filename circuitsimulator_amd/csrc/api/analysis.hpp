@@ -99,6 +99,18 @@ struct BatchPacResult {
     std::vector<uint32_t> status;                 // DC, transient and steady-state bits, CSIM_ST_PAC_SINGULAR
 };
 
+struct BatchPnoiseResult {
+    int nSide = 0, nSrc = 0;
+    std::vector<double> freqs;                    // [F] Hz: the output frequencies
+    std::vector<double> onoise;                   // [B][F] V^2/Hz
+    std::vector<std::complex<double>> gain;       // [B][F][2 nSide + 1]: from f + m f0 at the source to the output at f, index m + nSide
+    std::vector<double> contrib;                  // [B][F][nSrc]: per generator (csim_netlist_noise_source's order)
+    std::vector<double> side;                     // [B][F][2 nSide + 1]: per sideband
+    std::vector<double> x0;                       // [B][N]: the start of the orbit the analysis linearised around
+    std::vector<int32_t> rounds;                  // [B]: shooting rounds the steady state used
+    std::vector<uint32_t> status;                 // DC, transient and steady-state bits, CSIM_ST_PAC_SINGULAR
+};
+
 // One engine per (circuit, GPU).  Throws std::runtime_error when no HIP
 // device is usable: there is no CPU path.
 class BatchEngine {
@@ -167,6 +179,14 @@ public:
     // (std::invalid_argument otherwise), for the reason given at pss(): pass the cards' numbers from SimulationConfig.
     BatchPacResult pac(const std::vector<double>& params, int B, double tstep, double f0, const std::vector<double>& freqs,
                        int nSide = 1, const std::vector<int32_t>& probeEq = {});
+
+    // Periodic noise analysis (csim_pnoise_batch, include/csim.h): DC operating point, periodic steady state, then the
+    // output noise at outP - outM (equations, -1 = ground) at every output frequency of freqs (Hz), folded down from the
+    // sidebands f + m f0, m = -nSide .. nSide, with the contribution of every generator and of every sideband, and the
+    // conversion gains from the V or I source srcElem (-1: none, gain stays zero).  tstep and f0 must be positive and
+    // freqs not empty (std::invalid_argument otherwise), for the reason given at pss().
+    BatchPnoiseResult pnoise(const std::vector<double>& params, int B, double tstep, double f0, const std::vector<double>& freqs,
+                             int outP, int outM = -1, int srcElem = -1, int nSide = 1, double tempK = 300.15);
 
     // the transient of instance `instance` of params ([B][P], empty = nominal) as the reference's CSV
     // (src/tanalisis.cpp:189-231); probeEq empty: the netlist's .PLOTNV/.PRINT probes when `sim` names any, else

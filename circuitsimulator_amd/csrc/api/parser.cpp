@@ -4,7 +4,7 @@
 //   the previous logical line; tokens split on blanks.
 //   Devices by first letter (any case): R C L V I M.   Cards: .MODEL (read in
 //   a first pass, so it may follow its users) .TRAN .OP .DC .AC .NOISE .SP .DISTO .STB .HB .PAC
-//   .PRINT .PLOTNV .PLOTNC; anything else is reported and skipped.
+//   .PNOISE .PRINT .PLOTNV .PLOTNC; anything else is reported and skipped.
 #include "parser.hpp"
 
 #include <algorithm>
@@ -430,6 +430,7 @@ void NetlistParser::dotCard(const Statement& st)
     else if (head == ".model")  modelCard(st);
     else if (head == ".hb")     hbCard(st);
     else if (head == ".pac")    pacCard(st);
+    else if (head == ".pnoise") pnoiseCard(st);
     else if (head == ".plotnv") plotNvCard(st);
     else if (head == ".plotnc") plotNcCard(st);
     else std::cerr << "Line " << st.lineNo << ": unsupported control card: " << st.raw << "\n";
@@ -680,6 +681,53 @@ void NetlistParser::pacCard(const Statement& st)
     }
     cfg.enabled = true;
     sim.pac = cfg;
+}
+
+// .PNOISE V(out[,ref]) [src] {LIN|DEC|OCT} npoints fstart fstop [nside]: the output and source of .NOISE, the grid and
+// nside of .PAC (nside defaults to 1; any other token count is an error)
+void NetlistParser::pnoiseCard(const Statement& st)
+{
+    // the output may be written with blanks inside its parentheses: join tokens up to the closing one
+    std::vector<std::string> t;
+    for (std::size_t i = 0; i < st.tokens.size(); ++i) {
+        if (i >= 2 && t.size() == 2 && t[1].find('(') != std::string::npos && t[1].find(')') == std::string::npos)
+            t[1] += st.tokens[i];
+        else
+            t.push_back(st.tokens[i]);
+    }
+    auto isSweep = [](const std::string& s) { const std::string l = toLower(s); return l == "dec" || l == "oct" || l == "lin"; };
+    const std::size_t at = t.size() > 2 && isSweep(t[2]) ? 2 : 3;      // the source may be left out
+    if ((t.size() != at + 4 && t.size() != at + 5) || !isSweep(t[at])) {
+        std::cerr << "Line " << st.lineNo << ": invalid .PNOISE syntax: " << st.raw << "\n";
+        return;
+    }
+    const ProbeSpec out = probeFromToken(t[1]);
+    if ((out.kind != ProbeKind::NodeVoltage && out.kind != ProbeKind::DiffVoltage) || out.node1.empty()) {
+        std::cerr << "Line " << st.lineNo << ": .PNOISE output must be V(node) or V(node,ref): " << st.raw << "\n";
+        return;
+    }
+    PnoiseConfig cfg;
+    cfg.outNode = out.node1;
+    cfg.refNode = out.node2;
+    if (at == 3) cfg.srcName = t[2];
+    const std::string sweep = toLower(t[at]);
+    cfg.sweepType = sweep == "lin" ? AcSweepType::LIN : (sweep == "oct" ? AcSweepType::OCT : AcSweepType::DEC);
+    try {
+        cfg.nPoints = std::stoi(t[at + 1]);
+        cfg.fstart  = parseSpiceNumber(t[at + 2]);
+        cfg.fstop   = parseSpiceNumber(t[at + 3]);
+        if (t.size() == at + 5) {
+            std::size_t used = 0;
+            cfg.nSide = std::stoi(t[at + 4], &used);
+            if (used != t[at + 4].size() || cfg.nSide < 0) throw std::invalid_argument("nside must be a whole number >= 0");
+        }
+    } catch (const std::exception& e) {
+        std::cerr << "Line " << st.lineNo << ": cannot parse .PNOISE arguments: " << e.what()
+                  << " in '" << st.raw << "'\n";
+        return;
+    }
+    cfg.enabled = true;
+    sim.pnoise = cfg;
 }
 
 // V(n) | V(n1,n2) | I(elem)

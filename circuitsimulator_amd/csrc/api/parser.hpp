@@ -55,6 +55,7 @@ private:
     void spCard(const Statement& st);
     void hbCard(const Statement& st);
     void pacCard(const Statement& st);
+    void pnoiseCard(const Statement& st);
     void printCard(const Statement& st);
     void plotNvCard(const Statement& st);
     void plotNcCard(const Statement& st);

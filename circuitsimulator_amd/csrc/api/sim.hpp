@@ -198,6 +198,17 @@ struct PacConfig {
     int nSide = 1;                  // sidebands -nSide .. nSide around the input frequency
 };
 
+// .PNOISE V(out[,ref]) [src] {DEC|OCT|LIN} n fstart fstop [nside] -- names as written; netlist_capi.cpp resolves them
+struct PnoiseConfig {
+    bool enabled = false;
+    std::string outNode, refNode;   // refNode empty or "0": ground
+    std::string srcName;            // input source for the conversion gain, empty: none
+    AcSweepType sweepType = AcSweepType::DEC;
+    int nPoints = 0;
+    double fstart = 0.0, fstop = 0.0;
+    int nSide = 1;                  // sidebands -nSide .. nSide around the output frequency
+};
+
 struct ProbeSpec {
     ProbeKind kind = ProbeKind::NodeVoltage;
     std::string expr;
@@ -222,6 +233,7 @@ public:
     StbConfig stb;
     HbConfig hb;
     PacConfig pac;
+    PnoiseConfig pnoise;
     std::vector<PrintCommand> printCommands;
 
     bool hasAnyAnalysis() const

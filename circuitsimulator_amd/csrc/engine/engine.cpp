@@ -416,6 +416,16 @@ int csim_engine_create(const csim_netlist* nl, int32_t device, csim_engine** out
         eng->pacFstart = pc.fstart;
         eng->pacFstop = pc.fstop;
         eng->pacNSide = pc.nSide;
+        const PnoiseConfig& pn = nl->sim.pnoise;
+        eng->pnoiseEnabled = pn.enabled ? 1 : 0;
+        eng->pnoiseOutP = nl->pnoiseOutP;
+        eng->pnoiseOutM = nl->pnoiseOutM;
+        eng->pnoiseSrcElem = nl->pnoiseSrcElem;
+        eng->pnoiseSweep = pn.sweepType == AcSweepType::DEC ? 0 : (pn.sweepType == AcSweepType::OCT ? 1 : 2);
+        eng->pnoisePoints = pn.nPoints;
+        eng->pnoiseFstart = pn.fstart;
+        eng->pnoiseFstop = pn.fstop;
+        eng->pnoiseNSide = pn.nSide;
     }
     if (!rc) {
         for (const csim::Port& p : nl->ports) { eng->spPortEq.push_back(p.branchEq); eng->spZ0.push_back(p.z0); }

@@ -496,6 +496,15 @@ int uploadGenerators(int S, int B, const int32_t* src_a, const int32_t* src_b, c
 
 } // namespace
 
+int csim::noiseResolve(const csim_engine* eng, int out_p, int out_m, int src_elem, double temp_k, int* inA, int* inB, double* kT4)
+{
+    csim::NoiseArgs a{};
+    if (const int rc = noiseSetup(eng, out_p, out_m, src_elem, temp_k, a, *kT4)) return rc;
+    *inA = a.inA;
+    *inB = a.inB;
+    return CSIM_OK;
+}
+
 size_t csim::acChunkCap(const csim_engine* eng)
 {
     size_t per = sizeof(double) * csim::acSystemDoubles(eng->plan.N);

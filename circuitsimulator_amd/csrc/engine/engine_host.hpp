@@ -35,6 +35,10 @@ int stageParams(csim_engine* eng, const double* params, int B, DevBuf& dParams);
 // most instances per chunk of the frequency-domain sweeps, csim_engine_stat("ac_chunk") (engine_freq.cpp)
 size_t acChunkCap(const csim_engine* eng);
 
+// the checks of a noise call (output pair, input source element or -1, temperature; engine_freq.cpp) -> the input's
+// unit excitation y(inA) - y(inB) (-1: none or ground) and 4 k_B T; the periodic noise analysis refuses what .NOISE does
+int noiseResolve(const csim_engine* eng, int out_p, int out_m, int src_elem, double temp_k, int* inA, int* inB, double* kT4);
+
 // instances per chunk of the W_K scratch of the periodic steady state and the periodic AC analysis: the option
 // pss_chunk, else the sweeps' chunk (engine_pss.cpp)
 int pssChunk(const csim_engine* eng, int B);

@@ -164,6 +164,10 @@ struct csim_engine {
     int pacEnabled = 0, pacSweep = 0, pacPoints = 0, pacNSide = 1;
     double pacFstart = 0.0, pacFstop = 0.0;
 
+    // Periodic noise analysis: the netlist's .PNOISE card, resolved (the defaults of csim_pnoise_batch)
+    int pnoiseEnabled = 0, pnoiseOutP = -2, pnoiseOutM = -1, pnoiseSrcElem = -1, pnoiseSweep = 0, pnoisePoints = 0, pnoiseNSide = 1;
+    double pnoiseFstart = 0.0, pnoiseFstop = 0.0;
+
     // S-parameter analysis: the netlist's .SP card and its ports in port order (branch equation, Z0); spPortError
     // says what is wrong with the PORTNUM numbering, if anything
     int spEnabled = 0, spSweep = 0, spPoints = 0;

@@ -276,6 +276,49 @@ int pacMaxFc(const GenPlan& pl, int M, int nProbe);
 hipError_t launchPacPeriod(const GenPlan& pl, const PacArgs& a, hipStream_t stream);
 hipError_t launchPacClose(const GenPlan& pl, const PacArgs& a, hipStream_t stream);
 
+// Periodic noise analysis (kernels_pnoise.hip) of chunk instances b0 .. b0+Bc-1 of a batch of B at Fc <= 32 output
+// frequencies.  The orbit kernel integrates the period from x0 as the periodic steady state does and stores every
+// converged state; the period kernel walks the stored orbit backwards, k = K .. 1, and carries the Fc complex adjoint
+// vectors as 2 Fc real columns (re at 2 f, im at 2 f + 1) through J_k^T q_k = z g_k + d, g_{k-1} = Hm^T q_k; the close
+// kernel solves (I - z_K W_K^T) g_K = r per (instance, frequency).  One launch of the period kernel with g0 == null
+// (g_K = 0, leaves r in gK), the close kernel, a second launch with g0 == gK, which adds the transfer sums and stores
+// the outputs.  Generator S (one past the noise generators) is the input source with sigma = 1.  Output, input and
+// generator equations are checked by the caller: they index LDS.
+struct PnoiseArgs {
+    const double* params;               // [P][B]
+    int B, b0, Bc;
+    double dt;
+    int K, M;                           // steps per period, sidebands -M .. M
+    int Fc, fFirst, F;                  // frequencies of this launch, the first one's index among the F of the call
+    const double *twc, *tws;            // [K] cos and sin of 2 pi j / K
+    const double *zr, *zi;              // [Fc] z of this launch's frequencies
+    const double *zKr, *zKi;            // [Fc] z_K (close kernel)
+    const double* x0;                   // [N][B] start of the period, not modified (orbit kernel)
+    double* orbit;                      // [Bc][K][N]: x_1 .. x_K of every chunk instance
+    const double* W;                    // [Bc][N][N] W_K (close kernel)
+    const uint32_t* wStatus;            // [B] status of the launch that made W_K (orbit kernel)
+    int outP, outM;                     // d = +1 at outP, -1 at outM (-1: ground)
+    int S;                              // noise generators
+    const int32_t *srcElem, *srcA, *srcB;   // [S] element and equations of every generator
+    int inA, inB;                       // the input source's unit excitation: q(inA) - q(inB), -1 = none / ground
+    double kT4;
+    const double* g0;                   // [Bc][N][2 Fc] start of the recursion, or null = zero (the first pass)
+    double* gK;                         // [Bc][N][2 Fc]: period kernel r out; close kernel r in, g_K out (in place)
+    double* onoise;                     // [F][B]
+    double* gain;                       // [F][2 M + 1][B] complex, or null
+    double* contrib;                    // [F][S][B], or null
+    double* side;                       // [F][2 M + 1][B], or null
+    int32_t* orbitStop;                 // [Bc]: instances the orbit kernel stopped
+    int32_t* stop;                      // [Bc] scratch, zeroed per frequency chunk: instances that stopped
+    uint32_t* status;                   // [B], OR-ed
+};
+// bytes of dynamic LDS of the period kernel at Fc frequencies; pnoiseMaxFc: the largest Fc <= 32 that fits, 0 = none
+size_t pnoiseLdsBytes(const GenPlan& pl, int Fc, int M, int S);
+int pnoiseMaxFc(const GenPlan& pl, int M, int S);
+hipError_t launchPnoiseOrbit(const GenPlan& pl, const PnoiseArgs& a, hipStream_t stream);
+hipError_t launchPnoisePeriod(const GenPlan& pl, const PnoiseArgs& a, hipStream_t stream);
+hipError_t launchPnoiseClose(const GenPlan& pl, const PnoiseArgs& a, hipStream_t stream);
+
 // layout helpers (transpose.hip): [rows][cols] <-> [cols][rows] of doubles
 hipError_t launchTranspose(const double* dIn, double* dOut, int rows, int cols, hipStream_t stream);
 

@@ -56,6 +56,20 @@ int finishNetlist(csim_netlist* nl)
             if (toLower(nl->ckt.elements[e]->getName()) == toLower(nc.srcName)) { nl->noiseSrcElem = static_cast<int>(e); break; }
     }
 
+    // .PNOISE card: names -> equation / element indices, as .NOISE
+    if (nl->sim.pnoise.enabled) {
+        const PnoiseConfig& nc = nl->sim.pnoise;
+        auto eqOf = [&](const std::string& name) {
+            if (name == "0") return -1;
+            const auto hit = nl->ckt.nodeNameToId.find(name);
+            return hit == nl->ckt.nodeNameToId.end() ? -2 : nl->ckt.nodes[static_cast<std::size_t>(hit->second)].eqIndex;
+        };
+        nl->pnoiseOutP = eqOf(nc.outNode);
+        nl->pnoiseOutM = nc.refNode.empty() ? -1 : eqOf(nc.refNode);
+        for (std::size_t e = 0; e < nl->ckt.elements.size() && !nc.srcName.empty(); ++e)
+            if (toLower(nl->ckt.elements[e]->getName()) == toLower(nc.srcName)) { nl->pnoiseSrcElem = static_cast<int>(e); break; }
+    }
+
     // .DISTO card: names -> equation indices
     if (nl->sim.disto.enabled) {
         const DistoConfig& dc = nl->sim.disto;
@@ -285,6 +299,23 @@ int csim_netlist_pac(const csim_netlist* nl, int32_t* enabled, int32_t* sweep, i
     if (!nl) return CSIM_ERR_ARG;
     const PacConfig& a = nl->sim.pac;
     if (enabled)  *enabled = a.enabled ? 1 : 0;
+    if (sweep)    *sweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
+    if (n_points) *n_points = a.nPoints;
+    if (fstart)   *fstart = a.fstart;
+    if (fstop)    *fstop = a.fstop;
+    if (n_side)   *n_side = a.enabled ? a.nSide : 0;
+    return CSIM_OK;
+}
+
+int csim_netlist_pnoise(const csim_netlist* nl, int32_t* enabled, int32_t* out_p_eq, int32_t* out_m_eq, int32_t* src_elem,
+                        int32_t* sweep, int32_t* n_points, double* fstart, double* fstop, int32_t* n_side)
+{
+    if (!nl) return CSIM_ERR_ARG;
+    const PnoiseConfig& a = nl->sim.pnoise;
+    if (enabled)  *enabled = a.enabled ? 1 : 0;
+    if (out_p_eq) *out_p_eq = nl->pnoiseOutP;
+    if (out_m_eq) *out_m_eq = nl->pnoiseOutM;
+    if (src_elem) *src_elem = nl->pnoiseSrcElem;
     if (sweep)    *sweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
     if (n_points) *n_points = a.nPoints;
     if (fstart)   *fstart = a.fstart;

@@ -21,6 +21,8 @@ struct csim_netlist {
     std::string csvHeader;
     // .NOISE card resolved to indices: output equations (-1 ground, -2 unknown node), input source element (-1 none)
     int noiseOutP = -2, noiseOutM = -1, noiseSrcElem = -1;
+    // .PNOISE card resolved the same way
+    int pnoiseOutP = -2, pnoiseOutM = -1, pnoiseSrcElem = -1;
     // .DISTO card resolved to indices: output equations (-1 ground, -2 unknown node)
     int distoOutP = -2, distoOutM = -1;
     // .STB card resolved: the probe's element index (-2: a name the netlist does not have)

@@ -164,6 +164,23 @@ class Netlist:
             raise capi.CsimError(capi.CSIM_ERR_CONFIG, "the netlist has no .PAC card")
         return ac_freqs(*card[:4])
 
+    @property
+    def pnoise(self):
+        """The .PNOISE card: None, or (out_p_eq, out_m_eq, src_elem, sweep, n_points, fstart, fstop, n_side); out_m_eq
+        -1 = ground, src_elem -1 = no input source."""
+        v = [C.c_int32() for _ in range(6)]
+        f0, f1, ns = C.c_double(), C.c_double(), C.c_int32()
+        capi.check(capi.lib().csim_netlist_pnoise(self._h, *[C.byref(x) for x in v], C.byref(f0), C.byref(f1), C.byref(ns)))
+        en, op, om, src, sw, npt = [x.value for x in v]
+        return (op, om, src, AC_SWEEPS[sw], npt, f0.value, f1.value, ns.value) if en else None
+
+    def pnoise_freqs(self):
+        """Frequency grid of the .PNOISE card (numpy, Hz)."""
+        card = self.pnoise
+        if card is None:
+            raise capi.CsimError(capi.CSIM_ERR_CONFIG, "the netlist has no .PNOISE card")
+        return ac_freqs(*card[3:7])
+
     def stb_freqs(self):
         """Frequency grid of the .STB card (numpy, Hz)."""
         card = self.stb
@@ -733,6 +750,85 @@ class Engine:
                                              rounds.ctypes.data, st.ctypes.data))
         return dict(freqs=f, p=out, x0=x, rounds=rounds, status=st, K=int(capi.lib().csim_pss_num_steps(tstep, f0)),
                     n_side=n_side)
+
+    def _pnoise_args(self, freqs, n_side, tstep, f0, out, src):
+        """-> (freqs, n_side, tstep, f0, out_p, out_m, src_elem): None takes the cards' values (.PNOISE for the grid,
+        n_side, output and source; .TRAN and .HB for tstep and f0), so the output shapes are known"""
+        tstep, f0, _, _, _, _, _ = self._pss_args(tstep, f0, 0, None, None, None)
+        card = self.netlist.pnoise
+        if freqs is None:
+            if card is None:
+                raise capi.CsimError(capi.CSIM_ERR_ARG, "no frequencies given and the netlist has no .PNOISE card")
+            freqs = self.netlist.pnoise_freqs()
+        f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+        if n_side is None:
+            n_side = card[7] if card is not None else 1
+        if out is None:
+            if card is None:
+                raise capi.CsimError(capi.CSIM_ERR_CONFIG, "no output given and the netlist has no .PNOISE card")
+            out_p, out_m = card[0], card[1]
+        elif isinstance(out, (tuple, list)):
+            out_p, out_m = int(out[0]), int(out[1])
+        else:
+            out_p, out_m = int(out), -1
+        if src is None:
+            src = card[2] if card is not None else -1
+        return f, int(n_side), tstep, f0, out_p, out_m, int(src)
+
+    def pnoise(self, params, x0, freqs=None, n_side=None, tstep=None, f0=None, out=None, src=None, temp=300.15,
+               contrib=False, side=False, status=None):
+        """Periodic noise analysis of the batch around the orbit that starts at x0 (device [N][B], normally pss()["x0"];
+        not modified): csim_pnoise_batch_dev.  freqs: output frequencies in Hz; out: equation or (out_p, out_m), -1 =
+        ground; src: V/I element index for the conversion gains, -1 = none; n_side -- None takes each from the .PNOISE
+        card (n_side 1 and src -1 without one); tstep None = the .TRAN card's step; f0 None = the .HB card's; temp in kelvin.
+        -> dict(freqs, onoise [F][B] V^2/Hz, gain complex [F][2 n_side + 1][B] or None (from f + m f0 at the source to
+                the output at f, index m + n_side), contrib [F][S][B] or None, side [F][2 n_side + 1][B] or None,
+                status [B], K, n_side); device tensors; status is OR-ed into `status` when given.  The call waits on the
+        stream."""
+        torch = _torch()
+        B = params.shape[1]
+        f, n_side, tstep, f0, out_p, out_m, src = self._pnoise_args(freqs, n_side, tstep, f0, out, src)
+        S = len(self.netlist.noise_sources)
+        nsb = 2 * max(n_side, 0) + 1
+        dev = self._dev()
+        x = x0.contiguous()
+        on = torch.zeros((len(f), B), dtype=torch.float64, device=dev)
+        g = torch.zeros((len(f), nsb, B, 2), dtype=torch.float64, device=dev) if src >= 0 else None
+        con = torch.zeros((len(f), S, B), dtype=torch.float64, device=dev) if contrib else None
+        sd = torch.zeros((len(f), nsb, B), dtype=torch.float64, device=dev) if side else None
+        st = status if status is not None else torch.zeros(B, dtype=torch.int32, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None     # noqa: E731
+        capi.check(capi.lib().csim_pnoise_batch_dev(self._h, params.data_ptr(), B, tstep, f0, x.data_ptr(), f.ctypes.data,
+                                                    len(f), n_side, out_p, out_m, src, float(temp), on.data_ptr(), ptr(g),
+                                                    ptr(con), ptr(sd), st.data_ptr(), self._stream()))
+        return dict(freqs=f, onoise=on, gain=torch.view_as_complex(g) if g is not None else None, contrib=con, side=sd,
+                    status=st, K=int(capi.lib().csim_pss_num_steps(tstep, f0)), n_side=n_side)
+
+    def pnoise_host(self, params=None, B=1, freqs=None, n_side=None, tstep=None, f0=None, out=None, src=None, temp=300.15,
+                    contrib=False, side=False):
+        """DC operating point + periodic steady state + periodic noise analysis (csim_pnoise_batch): numpy,
+        instance-major.
+        -> dict(freqs, onoise [B][F], gain complex [B][F][2 n_side + 1] or None, contrib [B][F][S] or None,
+                side [B][F][2 n_side + 1] or None, x0 [B][N], rounds [B], status [B], K, n_side)"""
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=np.float64)
+            B = params.shape[0]
+        f, n_side, tstep, f0, out_p, out_m, src = self._pnoise_args(freqs, n_side, tstep, f0, out, src)
+        S = len(self.netlist.noise_sources)
+        nsb = 2 * max(n_side, 0) + 1
+        on = np.zeros((B, len(f)))
+        g = np.zeros((B, len(f), nsb, 2)) if src >= 0 else None
+        con = np.zeros((B, len(f), S)) if contrib else None
+        sd = np.zeros((B, len(f), nsb)) if side else None
+        x = np.zeros((B, self.N))
+        rounds = np.zeros(B, dtype=np.int32)
+        st = np.zeros(B, dtype=np.uint32)
+        ptr = lambda a: a.ctypes.data if a is not None else None    # noqa: E731
+        capi.check(capi.lib().csim_pnoise_batch(self._h, ptr(params), B, tstep, f0, f.ctypes.data, len(f), n_side, out_p,
+                                                out_m, src, float(temp), on.ctypes.data, ptr(g), ptr(con), ptr(sd),
+                                                x.ctypes.data, rounds.ctypes.data, st.ctypes.data))
+        return dict(freqs=f, onoise=on, gain=g[..., 0] + 1j * g[..., 1] if g is not None else None, contrib=con, side=sd,
+                    x0=x, rounds=rounds, status=st, K=int(capi.lib().csim_pss_num_steps(tstep, f0)), n_side=n_side)
 
     def sp(self, params, x_op, freqs=None, want_s=True, status=None):
         """S-parameter sweep of the batch around the operating points x_op (device [N][B], from dc());

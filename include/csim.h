@@ -710,6 +710,75 @@ int  csim_pac_batch(csim_engine* eng, const double* params, int32_t B, double ts
                     int32_t F, int32_t n_side, const int32_t* probe_eq, int32_t n_probe, double* out, double* x0_out,
                     int32_t* rounds, uint32_t* status);
 
+/* ---- Periodic noise analysis (.PNOISE): the adjoint of the periodic AC recursion, run backwards over the orbit ----
+ * The noise at an output frequency f of a circuit on a periodic orbit is folded down from every f + m f0: each white
+ * generator is modulated by the orbit and translated by it.  "Noise analysis" linearises at a DC point and cannot see
+ * either.  This one solves the adjoint of "Periodic AC analysis": one column per OUTPUT frequency gives the transfer
+ * from every node at every time step to the output, which serves all generators and all sidebands at once.
+ * Carried over from the periodic AC analysis: h, f0, K, the table c[j], s[j], the orbit x_1 .. x_K from the given x0
+ *   (integrated by the general transient's device functions in the periodic steady state's order and stored), J_k at
+ *   the converged x_k, Hm, W_K, and for an output frequency f > 0 the constants z and z_K.
+ * Output selector: d, real [N], +1 at out_p, -1 at out_m (-1 = ground), as in "Noise analysis".
+ * Adjoint recursion, k = K down to 1, g periodic (g_0 = g_K):
+ *     J_k^T q_k = z g_k + d,   g_{k-1} = Hm^T q_k.
+ *   Operation order: re = (zr gr - zi gi) + d, im = (zr gi + zi gr) + 0.0; then the engine's real LU applied to the
+ *   matrix J_k^T (pivots chosen on the transposed matrix, first maximum, zero multipliers skipped) on all 2 Fc real
+ *   columns at once; then row i of the product over the non-zero Hm(l, i), l ascending, product and sum rounded
+ *   separately.  With r = g_0 obtained from g_K = 0 the periodic start solves (I - z_K W_K^T) g_K = r, entries
+ *   ((i == j ? 1 : 0) - zKr W_K(j, i)) + j (0 - zKi W_K(j, i)), by the complex LU of "AC analysis"; the recursion is run
+ *   again from that g_K.
+ * Generators: csim_netlist_noise_source's, in element order, evaluated at the state x_k of each step:
+ *   psd_{s,k} = kT4 (1 / R) for a resistor (constant; R == 0 gives 0), kT4 ((2/3) |gg(x_k)|) for a MOSFET channel, gg
+ *   from the MOSFET evaluation that assembled J_k; sigma_{s,k} = sqrt(psd_{s,k}); kT4 = 4 k_B temp_k.
+ * Transfers, m = -n_side .. n_side:
+ *     T_{s,m} = (1/K) sum_k sigma_{s,k} (q_k[a] - q_k[b]) (c[j] + j s[j]),  j = ((m k) mod K + K) mod K  (PLUS sign):
+ *   the transfer of a unit white source at f + m f0, modulated by the orbit, to the output at f.  Per step
+ *   w = sigma (q[a] - q[b]), re and im one product each; re += wr c - wi s, im += wi c + wr s.  THE STEPS ARE ADDED IN THE
+ *   ORDER THE RECURSION VISITS THEM, k = K, K - 1, .. 1.  Everything is rounded separately; the scale 1/K (one division)
+ *   multiplies the finished sums.
+ * Outputs per (frequency, instance), |T|^2 = re re + im im:
+ *   contrib[s] = 0.0 + sum_m |T_{s,m}|^2, m ascending;  side[m] = 0.0 + sum_s |T_{s,m}|^2, s ascending;
+ *   onoise = 0.0 + sum_s contrib[s], s ascending, in V^2/Hz.
+ * Periodic transfer function (src_elem >= 0): the same sums with sigma = 1 and the source's unit excitation in place of
+ *   (a, b): a V source with branch equation k gives q_k[k], an I source (p, m) gives q_k[m] - q_k[p].  gain[m] is the
+ *   conversion gain from f + m f0 at that source to the output at f; it equals the periodic AC analysis' P_{-m} at the
+ *   output for the input frequency f + m f0.  Without a source a gain buffer receives zeros.
+ * Status: a tiny pivot in the closure or in a step's solve sets CSIM_ST_PAC_SINGULAR (the closure matrix is the
+ *   periodic AC analysis' transposed: the same condition); the instance's outputs for that chunk of frequencies are
+ *   +0.0.  A start that is not finite, and instances that arrive with CSIM_ST_TRAN_NONFINITE or CSIM_ST_PSS_SINGULAR,
+ *   behave as in the periodic AC analysis.
+ * Refused before anything looks at the device: what the periodic AC analysis and the noise analysis refuse -- null
+ *   pointers, B <= 0, F <= 0 without a card, n_side < 0, numbers that are not finite, a frequency <= 0, out_p == out_m
+ *   or out_p < 0 or an equation out of range, a src_elem that is not a V or I source: CSIM_ERR_ARG; temp_k <= 0 or not
+ *   finite, no f0 / tstep and no cards, K refused as by csim_pss_num_steps, K < 2 n_side + 1, sums that do not fit the
+ *   LDS at one frequency per launch, an orbit of one instance (K N 8 bytes) beyond the orbit store's budget:
+ *   CSIM_ERR_CONFIG; more than 63 unknowns: CSIM_ERR_UNSUPPORTED.  No AC source is needed.
+ * Card: `.PNOISE V(out[,ref]) [src] DEC|OCT|LIN n fstart fstop [nside]`: output and source as .NOISE's, grid and nside
+ *   (default 1) as .PAC's.  A card error is reported and the card left off.
+ * csim_pnoise_batch_dev: freqs host [F] in Hz; d_x0 [N][B], not modified; d_onoise [F][B]; d_gain
+ *   [F][2 n_side + 1][B] complex or NULL; d_contrib [F][S][B] or NULL; d_side [F][2 n_side + 1][B] or NULL, sideband m
+ *   at index m + n_side; d_status [B], OR-ed.  Frequencies go in chunks of the largest Fc <= 32 whose LDS image (the
+ *   general kernel's, Hm, the g and q planes, the generators' sigma and equations, 2 (S + 1)(2 n_side + 1) Fc sums)
+ *   fits 160 KB; instances in the chunks of the periodic steady state (option pss_chunk), reduced so that the orbit
+ *   store, chunk K N 8 bytes, stays within 256 MiB.  Per instance chunk one launch for W_K and one for the orbit, per
+ *   frequency chunk two backward passes around the closure solve.  THIS ENTRY WAITS ON THE STREAM before it returns.
+ * csim_pnoise_batch: DC operating point, periodic steady state, then the analysis; their status bits are OR-ed in.
+ *   params [B][P] or NULL (nominal); tstep <= 0: the .TRAN card's step; f0 <= 0: the .HB card's f0; freqs NULL and
+ *   F == 0: the .PNOISE card's grid; out_p_eq == -2: the card's output and source (n_side is always the caller's;
+ *   csim_netlist_pnoise reports the card's); onoise [B][F], gain [B][F][2 n_side + 1] complex, contrib [B][F][S],
+ *   side [B][F][2 n_side + 1], x0_out [B][N], rounds [B], status [B]; all but onoise may be NULL.
+ *   The exact order of every operation the analysis adds: engine/pnoise.hpp. */
+int  csim_netlist_pnoise(const csim_netlist* nl, int32_t* enabled, int32_t* out_p_eq, int32_t* out_m_eq, int32_t* src_elem,
+                         int32_t* sweep, int32_t* n_points, double* fstart, double* fstop, int32_t* n_side);
+int  csim_pnoise_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int32_t B, double tstep, double f0,
+                           const double* d_x0 /*[N][B]*/, const double* freqs /*host [F]*/, int32_t F, int32_t n_side,
+                           int32_t out_p_eq, int32_t out_m_eq, int32_t src_elem, double temp_k, double* d_onoise,
+                           double* d_gain, double* d_contrib, double* d_side, uint32_t* d_status, void* stream);
+int  csim_pnoise_batch(csim_engine* eng, const double* params, int32_t B, double tstep, double f0, const double* freqs,
+                       int32_t F, int32_t n_side, int32_t out_p_eq, int32_t out_m_eq, int32_t src_elem, double temp_k,
+                       double* onoise, double* gain, double* contrib, double* side, double* x0_out, int32_t* rounds,
+                       uint32_t* status);
+
 /* Batched dense solve A x = b with the engine's pivoted LU
  * (Solver::solveLinearSystemLU semantics: first-maximum partial pivoting,
  * tiny pivot -> zero vector).  A [B][n][n] row-major, b/x [B][n], host
