@@ -162,6 +162,13 @@ __device__ __forceinline__ double wave_max(double v)
     return v;
 }
 
+// the wave's vote that lanes 0 .. N-1 all hold a finite value
+__device__ __forceinline__ bool wave_all_finite(double v, int N, int lane)
+{
+    const bool bad = (lane < N) && !isfinite(v);
+    return __ballot(bad) == 0ull;
+}
+
 __device__ __forceinline__ double volt_of(const double* x, int eq) { return eq >= 0 ? x[eq] : 0.0; }
 
 // SourceSpec::evalDC (sim.hpp:152-158)

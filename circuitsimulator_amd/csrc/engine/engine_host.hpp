@@ -5,9 +5,11 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <vector>
 
 #include "csim.h"
 #include "engine_internal.hpp"
+#include "kernels.hpp"
 #include "netlist_internal.hpp"
 
 #define HIPCHK(call)                                                                   \
@@ -42,5 +44,36 @@ int noiseResolve(const csim_engine* eng, int out_p, int out_m, int src_elem, dou
 // instances per chunk of the W_K scratch of the periodic steady state and the periodic AC analysis: the option
 // pss_chunk, else the sweeps' chunk (engine_pss.cpp)
 int pssChunk(const csim_engine* eng, int B);
+
+// ---- what the periodic analyses (engine_pss.cpp, engine_pac.cpp, engine_pnoise.cpp) share; all in engine_pss.cpp
+
+// tstep from the .TRAN card when cardDefaults and none is given, the f0 check, K = the steps per period.  `who` heads
+// the messages.
+int periodResolveSteps(const csim_engine* eng, const std::string& who, bool cardDefaults, double& tstep, double f0, int64_t& K);
+
+// the sweep of a .PAC or .PNOISE card (`card` names it in the message)
+struct PeriodSweepCard { const char* card; int enabled, sweep, points; double fstart, fstop; };
+// the frequencies of a call: the caller's F, or with F == 0 the card's; every one finite and positive
+int periodResolveFreqs(const std::string& who, bool cardDefaults, const PeriodSweepCard& card, const double* freqs, int F,
+                       std::vector<double>& out);
+
+// The W_K launch of the analyses that follow a steady state: the periodic steady state's period kernel on a status word
+// of its own, no harmonics, no update.  Holds on the device its scratch, the twiddle table (args.twc, args.tws) and
+// zr, zi, zKr, zKi ([F] each, in this order in dZ), and the filled launch record but for b0 and Bc: W_K comes out in
+// args.W, the launch's status in args.status.  The scratch must live until the stream has drained: keep the holder
+// until after a synchronisation.
+struct PeriodWk {
+    DevBuf dTw, dZ, dXk, dW, dDone, dWst;
+    PssArgs args{};
+};
+// allocates for chunks of `chunk` instances, uploads the tables and queues the memsets on hs
+int periodWkSetup(PeriodWk& wk, const csim_engine* eng, const double* d_params, int B, int chunk, double tstep, double f0,
+                  int64_t K, const std::vector<double>& freqs, const double* d_x0, hipStream_t hs);
+
+// The host forms of the analyses that follow a steady state: the parameters staged, the DC operating point and the
+// periodic steady state with no harmonics stored (prologue); x0, rounds and status copied back (epilogue, null = skip).
+struct PeriodHostState { DevBuf dParams, dX, dIters, dStatus, dHarm, dRounds; };
+int periodHostPrologue(csim_engine* eng, const double* params, int B, double tstep, double f0, PeriodHostState& h);
+int periodHostEpilogue(const csim_engine* eng, int B, PeriodHostState& h, double* x0_out, int32_t* rounds, uint32_t* status);
 
 } // namespace csim

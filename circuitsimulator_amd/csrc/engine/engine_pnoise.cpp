@@ -37,17 +37,9 @@ int pnoiseResolve(const csim_engine* eng, const char* who, bool cardDefaults, do
     }
     if (F < 0 || (F > 0 && !freqs)) { setError(w + ": bad argument"); return CSIM_ERR_ARG; }
     if (n_side < 0) { setError(w + ": n_side must be >= 0"); return CSIM_ERR_ARG; }
-    if (F == 0) {
-        if (!cardDefaults || freqs || !eng->pnoiseEnabled) { setError(w + ": no frequencies given and no .PNOISE card to take them from"); return CSIM_ERR_ARG; }
-        const int64_t n = csim_ac_num_freqs(eng->pnoiseSweep, eng->pnoisePoints, eng->pnoiseFstart, eng->pnoiseFstop);
-        if (n < 0) return (int)n;
-        p.freqs.resize((size_t)n);
-        if (const int rc = csim_ac_freqs(eng->pnoiseSweep, eng->pnoisePoints, eng->pnoiseFstart, eng->pnoiseFstop, p.freqs.data())) return rc;
-    } else {
-        p.freqs.assign(freqs, freqs + F);
-    }
-    for (const double f : p.freqs)
-        if (!std::isfinite(f) || !(f > 0.0)) { setError(w + ": every frequency must be finite and positive"); return CSIM_ERR_ARG; }
+    const csim::PeriodSweepCard card{".PNOISE", eng->pnoiseEnabled, eng->pnoiseSweep, eng->pnoisePoints, eng->pnoiseFstart,
+                                     eng->pnoiseFstop};
+    if (const int rc = csim::periodResolveFreqs(w, cardDefaults, card, freqs, F, p.freqs)) return rc;
     if (cardDefaults && out_p == -2) {
         if (!eng->pnoiseEnabled) { setError(w + ": no output given and the netlist has no .PNOISE card"); return CSIM_ERR_CONFIG; }
         out_p = eng->pnoiseOutP;
@@ -58,16 +50,8 @@ int pnoiseResolve(const csim_engine* eng, const char* who, bool cardDefaults, do
         if (!eng->hbEnabled) { setError(w + ": no f0 given and the netlist has no .HB card"); return CSIM_ERR_CONFIG; }
         f0 = eng->hbF0;
     }
-    if (cardDefaults && !(tstep > 0.0)) {
-        if (!eng->tranEnabled) { setError(w + ": no tstep given and the netlist has no .TRAN card"); return CSIM_ERR_CONFIG; }
-        tstep = eng->tranTstep;
-    }
-    if (!(f0 > 0.0)) { setError(w + ": no f0 given"); return CSIM_ERR_CONFIG; }
-    const int64_t K = csim::pss_num_steps(tstep, f0);
-    if (K < 0) {
-        setError(w + ": the period 1/f0 must be a whole number of steps, at most 2^22 (|K tstep f0 - 1| <= 1e-9)");
-        return (int)K;
-    }
+    int64_t K = 0;
+    if (const int rc = csim::periodResolveSteps(eng, w, cardDefaults, tstep, f0, K)) return rc;
     if (K < 2 * (int64_t)n_side + 1) {
         setError(w + ": " + std::to_string(K) + " steps per period cannot tell " + std::to_string(n_side) + " sidebands apart (K >= 2 n_side + 1)");
         return CSIM_ERR_CONFIG;
@@ -105,40 +89,19 @@ int pnoiseRun(csim_engine* eng, const PnoisePlan& p, const double* d_params, int
     const size_t perInstance = (size_t)p.K * (size_t)N * sizeof(double);
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)csim::pssChunk(eng, B), csim::PNOISE_ORBIT_BUDGET / perInstance));
 
-    std::vector<double> tw(2 * (size_t)p.K);
-    csim::pss_twiddles(p.K, tw.data(), tw.data() + p.K);
-    std::vector<double> z(4 * (size_t)F);                   // zr, zi, zKr, zKi, [F] each
-    for (int f = 0; f < F; ++f) csim::pac_z(p.freqs[(size_t)f], p.tstep, p.f0, &z[f], &z[F + f], &z[2 * F + f], &z[3 * F + f]);
-
-    DevBuf dTw, dZ, dXk, dW, dDone, dWst, dGk, dStop, dOrbitStop, dOrbit;
-    HIPCHK(dTw.alloc(sizeof(double) * tw.size()));
-    HIPCHK(hipMemcpy(dTw.p, tw.data(), sizeof(double) * tw.size(), hipMemcpyHostToDevice));
-    HIPCHK(dZ.alloc(sizeof(double) * z.size()));
-    HIPCHK(hipMemcpy(dZ.p, z.data(), sizeof(double) * z.size(), hipMemcpyHostToDevice));
-    HIPCHK(dXk.alloc(sizeof(double) * (size_t)N * (size_t)B));
-    HIPCHK(dW.alloc(sizeof(double) * (size_t)N * (size_t)N * (size_t)chunk));
-    HIPCHK(dDone.alloc(sizeof(int32_t) * (size_t)B));
-    HIPCHK(dWst.alloc(sizeof(uint32_t) * (size_t)B));
+    csim::PeriodWk wk;
+    DevBuf dGk, dStop, dOrbitStop, dOrbit;
+    if (const int rc = csim::periodWkSetup(wk, eng, d_params, B, chunk, p.tstep, p.f0, p.K, p.freqs, d_x0, hs)) return rc;
     HIPCHK(dGk.alloc(sizeof(double) * (size_t)N * 2 * (size_t)Fc * (size_t)chunk));
     HIPCHK(dStop.alloc(sizeof(int32_t) * (size_t)chunk));
     HIPCHK(dOrbitStop.alloc(sizeof(int32_t) * (size_t)chunk));
     HIPCHK(dOrbit.alloc(perInstance * (size_t)chunk));
-    HIPCHK(hipMemsetAsync(dDone.p, 0, sizeof(int32_t) * (size_t)B, hs));
-    HIPCHK(hipMemsetAsync(dWst.p, 0, sizeof(uint32_t) * (size_t)B, hs));
-
-    // the W_K launch is the periodic steady state's period kernel on a status word of its own: no harmonics, no update
-    csim::PssArgs wa{};
-    wa.params = d_params; wa.B = B; wa.dt = p.tstep; wa.K = (int)p.K; wa.H = 0;
-    wa.probeEq = nullptr; wa.nProbe = 0;
-    wa.twc = dTw.as<double>(); wa.tws = dTw.as<double>() + p.K;
-    wa.x0 = const_cast<double*>(d_x0);                      // the period kernel reads it only
-    wa.xK = dXk.as<double>(); wa.harm = nullptr; wa.W = dW.as<double>();
-    wa.status = dWst.as<uint32_t>(); wa.done = dDone.as<int32_t>();
+    csim::PssArgs& wa = wk.args;
 
     csim::PnoiseArgs a{};
     a.params = d_params; a.B = B; a.dt = p.tstep; a.K = (int)p.K; a.M = p.nSide; a.F = F;
     a.twc = wa.twc; a.tws = wa.tws;
-    a.x0 = d_x0; a.orbit = dOrbit.as<double>(); a.W = dW.as<double>(); a.wStatus = dWst.as<uint32_t>();
+    a.x0 = d_x0; a.orbit = dOrbit.as<double>(); a.wStatus = wa.status;
     a.outP = p.outP; a.outM = p.outM;
     a.S = eng->nNoiseSrc; a.srcElem = eng->dNoiseElem; a.srcA = eng->dNoiseA; a.srcB = eng->dNoiseB;
     a.inA = p.inA; a.inB = p.inB; a.kT4 = p.kT4;
@@ -146,22 +109,25 @@ int pnoiseRun(csim_engine* eng, const PnoisePlan& p, const double* d_params, int
     a.onoise = d_onoise; a.gain = d_gain; a.contrib = d_contrib; a.side = d_side;
     a.orbitStop = dOrbitStop.as<int32_t>(); a.stop = dStop.as<int32_t>(); a.status = d_status;
 
+    csim::PeriodCloseArgs cl{};
+    cl.W = wa.W; cl.v = a.gK; cl.stop = a.stop; cl.status = d_status; cl.transposeW = true;
+
     // The scratch above lives until the stream has drained: the one exit below comes after a synchronisation.
     hipError_t e = hipSuccess;
     for (int b0 = 0; b0 < B && e == hipSuccess; b0 += chunk) {
-        wa.b0 = a.b0 = b0;
-        wa.Bc = a.Bc = std::min(chunk, B - b0);
+        wa.b0 = a.b0 = cl.b0 = b0;
+        wa.Bc = a.Bc = cl.Bc = std::min(chunk, B - b0);
         e = csim::launchPssPeriod(eng->gpTran, wa, hs);
         if (e == hipSuccess) e = hipMemsetAsync(dOrbitStop.p, 0, sizeof(int32_t) * (size_t)a.Bc, hs);
         if (e == hipSuccess) e = csim::launchPnoiseOrbit(eng->gpTran, a, hs);
         for (int f0i = 0; f0i < F && e == hipSuccess; f0i += Fc) {
             a.fFirst = f0i;
-            a.Fc = std::min(Fc, F - f0i);
-            a.zr = dZ.as<double>() + f0i; a.zi = a.zr + F; a.zKr = a.zi + F; a.zKi = a.zKr + F;
+            a.Fc = cl.Fc = std::min(Fc, F - f0i);
+            a.zr = wk.dZ.as<double>() + f0i; a.zi = a.zr + F; cl.zKr = a.zi + F; cl.zKi = cl.zKr + F;
             e = hipMemsetAsync(dStop.p, 0, sizeof(int32_t) * (size_t)a.Bc, hs);
             a.g0 = nullptr;
             if (e == hipSuccess) e = csim::launchPnoisePeriod(eng->gpTran, a, hs);
-            if (e == hipSuccess) e = csim::launchPnoiseClose(eng->gpTran, a, hs);
+            if (e == hipSuccess) e = csim::launchPeriodClose(eng->gpTran, cl, hs);
             a.g0 = a.gK;
             if (e == hipSuccess) e = csim::launchPnoisePeriod(eng->gpTran, a, hs);
         }
@@ -202,26 +168,16 @@ int csim_pnoise_batch(csim_engine* eng, const double* params, int32_t B, double 
     if (const int rc = pnoiseResolve(eng, "csim_pnoise_batch", true, tstep, f0, freqs, F, n_side, out_p_eq, out_m_eq, src_elem,
                                      temp_k, p)) return rc;
     HIPCHK(hipSetDevice(eng->device));
-    const int N = eng->plan.N, nF = (int)p.freqs.size(), nSb = 2 * p.nSide + 1, S = eng->nNoiseSrc;
-    DevBuf dParams, dX, dIters, dStatus, dHarm, dRounds, dOn, dGain, dCon, dSide;
-    if (const int rc = csim::stageParams(eng, params, B, dParams)) return rc;
-    HIPCHK(dX.alloc(sizeof(double) * (size_t)N * B));
-    HIPCHK(dIters.alloc(sizeof(int32_t) * (size_t)B));
-    HIPCHK(dStatus.alloc(sizeof(uint32_t) * (size_t)B));
-    HIPCHK(dHarm.alloc(sizeof(double) * 2));
-    HIPCHK(dRounds.alloc(sizeof(int32_t) * (size_t)B));
+    const int nF = (int)p.freqs.size(), nSb = 2 * p.nSide + 1, S = eng->nNoiseSrc;
+    csim::PeriodHostState s;
+    DevBuf dOn, dGain, dCon, dSide;
     HIPCHK(dOn.alloc(sizeof(double) * (size_t)nF * B));
     if (gain) HIPCHK(dGain.alloc(sizeof(double) * 2 * (size_t)nF * nSb * B));
     if (contrib) HIPCHK(dCon.alloc(sizeof(double) * (size_t)nF * S * B));
     if (side) HIPCHK(dSide.alloc(sizeof(double) * (size_t)nF * nSb * B));
-    if (const int rc = csim_dc_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), dIters.as<int32_t>(),
-                                         dStatus.as<uint32_t>(), nullptr)) return rc;
-    // the steady state with no harmonics stored: an empty probe list
-    const int32_t none = 0;
-    if (const int rc = csim_pss_batch_dev(eng, dParams.as<double>(), B, p.tstep, p.f0, 0, &none, 0, 0.0, 0, dX.as<double>(),
-                                          dHarm.as<double>(), dRounds.as<int32_t>(), dStatus.as<uint32_t>(), nullptr)) return rc;
-    if (const int rc = pnoiseRun(eng, p, dParams.as<double>(), B, dX.as<double>(), dOn.as<double>(), dGain.as<double>(),
-                                 dCon.as<double>(), dSide.as<double>(), dStatus.as<uint32_t>(), nullptr)) return rc;
+    if (const int rc = csim::periodHostPrologue(eng, params, B, p.tstep, p.f0, s)) return rc;
+    if (const int rc = pnoiseRun(eng, p, s.dParams.as<double>(), B, s.dX.as<double>(), dOn.as<double>(), dGain.as<double>(),
+                                 dCon.as<double>(), dSide.as<double>(), s.dStatus.as<uint32_t>(), nullptr)) return rc;
     HIPCHK(hipDeviceSynchronize());
     // [F][per][B] (x width) on the device -> [B][F][per] (x width) for the caller
     auto fetch = [&](DevBuf& d, double* out, size_t per, int width) -> int {
@@ -238,15 +194,7 @@ int csim_pnoise_batch(csim_engine* eng, const double* params, int32_t B, double 
     if (const int rc = fetch(dGain, gain, (size_t)nSb, 2)) return rc;
     if (const int rc = fetch(dCon, contrib, (size_t)S, 1)) return rc;
     if (const int rc = fetch(dSide, side, (size_t)nSb, 1)) return rc;
-    if (x0_out) {
-        std::vector<double> x((size_t)N * B);
-        HIPCHK(hipMemcpy(x.data(), dX.p, sizeof(double) * x.size(), hipMemcpyDeviceToHost));
-        for (int i = 0; i < N; ++i)
-            for (int b = 0; b < B; ++b) x0_out[(size_t)b * N + i] = x[(size_t)i * B + b];
-    }
-    if (rounds) HIPCHK(hipMemcpy(rounds, dRounds.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    if (status) HIPCHK(hipMemcpy(status, dStatus.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    return CSIM_OK;
+    return csim::periodHostEpilogue(eng, B, s, x0_out, rounds, status);
 }
 
 } // extern "C"

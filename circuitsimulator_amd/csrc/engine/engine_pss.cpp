@@ -1,6 +1,8 @@
 // engine_pss.cpp -- C-ABI of the periodic-steady-state analysis (include/csim.h "Periodic steady state"): the device
 // form csim_pss_batch_dev (shooting rounds on the caller's stream, one counter read back per round), the host form
-// csim_pss_batch (DC operating point first) and the two helpers that give a test the library's own K and table.
+// csim_pss_batch (DC operating point first) and the two helpers that give a test the library's own K and table; and
+// what the periodic AC and noise analyses share with it on the host (engine_host.hpp): the resolve blocks, the W_K
+// launch's scratch, the host forms' prologue and epilogue.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,6 +13,7 @@
 #include "csim.h"
 #include "engine_host.hpp"
 #include "kernels.hpp"
+#include "pac.hpp"
 #include "pss.hpp"
 
 using csim::setError;
@@ -41,16 +44,8 @@ int pssResolve(const csim_engine* eng, const char* who, bool cardDefaults, doubl
         n_harm = eng->hbNHarm;
         if (n_harm < 0) { setError(w + ": the .HB card's harmonic count is negative"); return CSIM_ERR_CONFIG; }
     }
-    if (cardDefaults && !(tstep > 0.0)) {
-        if (!eng->tranEnabled) { setError(w + ": no tstep given and the netlist has no .TRAN card"); return CSIM_ERR_CONFIG; }
-        tstep = eng->tranTstep;
-    }
-    if (!(f0 > 0.0)) { setError(w + ": no f0 given"); return CSIM_ERR_CONFIG; }
-    const int64_t K = csim::pss_num_steps(tstep, f0);
-    if (K < 0) {
-        setError(w + ": the period 1/f0 must be a whole number of steps, at most 2^22 (|K tstep f0 - 1| <= 1e-9)");
-        return (int)K;
-    }
+    int64_t K = 0;
+    if (const int rc = csim::periodResolveSteps(eng, w, cardDefaults, tstep, f0, K)) return rc;
     if (K < 2 * (int64_t)n_harm + 1) {
         setError(w + ": " + std::to_string(K) + " steps per period cannot carry " + std::to_string(n_harm) + " harmonics (K >= 2 n_harm + 1)");
         return CSIM_ERR_CONFIG;
@@ -76,6 +71,103 @@ int csim::pssChunk(const csim_engine* eng, int B)
 {
     const size_t cap = eng->cfg.pssChunk > 0 ? (size_t)eng->cfg.pssChunk : csim::acChunkCap(eng);
     return (int)std::min<size_t>((size_t)B, cap);
+}
+
+int csim::periodResolveSteps(const csim_engine* eng, const std::string& w, bool cardDefaults, double& tstep, double f0, int64_t& K)
+{
+    if (cardDefaults && !(tstep > 0.0)) {
+        if (!eng->tranEnabled) { setError(w + ": no tstep given and the netlist has no .TRAN card"); return CSIM_ERR_CONFIG; }
+        tstep = eng->tranTstep;
+    }
+    if (!(f0 > 0.0)) { setError(w + ": no f0 given"); return CSIM_ERR_CONFIG; }
+    K = csim::pss_num_steps(tstep, f0);
+    if (K < 0) {
+        setError(w + ": the period 1/f0 must be a whole number of steps, at most 2^22 (|K tstep f0 - 1| <= 1e-9)");
+        return (int)K;
+    }
+    return CSIM_OK;
+}
+
+int csim::periodResolveFreqs(const std::string& w, bool cardDefaults, const PeriodSweepCard& card, const double* freqs, int F,
+                             std::vector<double>& out)
+{
+    if (F == 0) {
+        if (!cardDefaults || freqs || !card.enabled) {
+            setError(w + ": no frequencies given and no " + card.card + " card to take them from");
+            return CSIM_ERR_ARG;
+        }
+        const int64_t n = csim_ac_num_freqs(card.sweep, card.points, card.fstart, card.fstop);
+        if (n < 0) return (int)n;
+        out.resize((size_t)n);
+        if (const int rc = csim_ac_freqs(card.sweep, card.points, card.fstart, card.fstop, out.data())) return rc;
+    } else {
+        out.assign(freqs, freqs + F);
+    }
+    for (const double f : out)
+        if (!std::isfinite(f) || !(f > 0.0)) { setError(w + ": every frequency must be finite and positive"); return CSIM_ERR_ARG; }
+    return CSIM_OK;
+}
+
+int csim::periodWkSetup(PeriodWk& wk, const csim_engine* eng, const double* d_params, int B, int chunk, double tstep, double f0,
+                        int64_t K, const std::vector<double>& freqs, const double* d_x0, hipStream_t hs)
+{
+    const int N = eng->plan.N;
+    const size_t F = freqs.size();
+    std::vector<double> tw(2 * (size_t)K);
+    csim::pss_twiddles(K, tw.data(), tw.data() + K);
+    std::vector<double> z(4 * F);                           // zr, zi, zKr, zKi, [F] each
+    for (size_t f = 0; f < F; ++f) csim::pac_z(freqs[f], tstep, f0, &z[f], &z[F + f], &z[2 * F + f], &z[3 * F + f]);
+
+    HIPCHK(wk.dTw.alloc(sizeof(double) * tw.size()));
+    HIPCHK(hipMemcpy(wk.dTw.p, tw.data(), sizeof(double) * tw.size(), hipMemcpyHostToDevice));
+    HIPCHK(wk.dZ.alloc(sizeof(double) * z.size()));
+    HIPCHK(hipMemcpy(wk.dZ.p, z.data(), sizeof(double) * z.size(), hipMemcpyHostToDevice));
+    HIPCHK(wk.dXk.alloc(sizeof(double) * (size_t)N * (size_t)B));
+    HIPCHK(wk.dW.alloc(sizeof(double) * (size_t)N * (size_t)N * (size_t)chunk));
+    HIPCHK(wk.dDone.alloc(sizeof(int32_t) * (size_t)B));
+    HIPCHK(wk.dWst.alloc(sizeof(uint32_t) * (size_t)B));
+    HIPCHK(hipMemsetAsync(wk.dDone.p, 0, sizeof(int32_t) * (size_t)B, hs));
+    HIPCHK(hipMemsetAsync(wk.dWst.p, 0, sizeof(uint32_t) * (size_t)B, hs));
+
+    csim::PssArgs& wa = wk.args;
+    wa.params = d_params; wa.B = B; wa.dt = tstep; wa.K = (int)K; wa.H = 0;
+    wa.probeEq = nullptr; wa.nProbe = 0;
+    wa.twc = wk.dTw.as<double>(); wa.tws = wk.dTw.as<double>() + K;
+    wa.x0 = const_cast<double*>(d_x0);                      // the period kernel reads it only
+    wa.xK = wk.dXk.as<double>(); wa.harm = nullptr; wa.W = wk.dW.as<double>();
+    wa.status = wk.dWst.as<uint32_t>(); wa.done = wk.dDone.as<int32_t>();
+    return CSIM_OK;
+}
+
+int csim::periodHostPrologue(csim_engine* eng, const double* params, int B, double tstep, double f0, PeriodHostState& h)
+{
+    const int N = eng->plan.N;
+    if (const int rc = csim::stageParams(eng, params, B, h.dParams)) return rc;
+    HIPCHK(h.dX.alloc(sizeof(double) * (size_t)N * B));
+    HIPCHK(h.dIters.alloc(sizeof(int32_t) * (size_t)B));
+    HIPCHK(h.dStatus.alloc(sizeof(uint32_t) * (size_t)B));
+    HIPCHK(h.dHarm.alloc(sizeof(double) * 2));
+    HIPCHK(h.dRounds.alloc(sizeof(int32_t) * (size_t)B));
+    if (const int rc = csim_dc_batch_dev(eng, h.dParams.as<double>(), B, h.dX.as<double>(), h.dIters.as<int32_t>(),
+                                         h.dStatus.as<uint32_t>(), nullptr)) return rc;
+    // the steady state with no harmonics stored: an empty probe list
+    const int32_t none = 0;
+    return csim_pss_batch_dev(eng, h.dParams.as<double>(), B, tstep, f0, 0, &none, 0, 0.0, 0, h.dX.as<double>(),
+                              h.dHarm.as<double>(), h.dRounds.as<int32_t>(), h.dStatus.as<uint32_t>(), nullptr);
+}
+
+int csim::periodHostEpilogue(const csim_engine* eng, int B, PeriodHostState& h, double* x0_out, int32_t* rounds, uint32_t* status)
+{
+    const int N = eng->plan.N;
+    if (x0_out) {                                           // [N][B] -> [B][N]
+        std::vector<double> x((size_t)N * B);
+        HIPCHK(hipMemcpy(x.data(), h.dX.p, sizeof(double) * x.size(), hipMemcpyDeviceToHost));
+        for (int i = 0; i < N; ++i)
+            for (int b = 0; b < B; ++b) x0_out[(size_t)b * N + i] = x[(size_t)i * B + b];
+    }
+    if (rounds) HIPCHK(hipMemcpy(rounds, h.dRounds.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, h.dStatus.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    return CSIM_OK;
 }
 
 extern "C" {
@@ -162,34 +254,26 @@ int csim_pss_batch(csim_engine* eng, const double* params, int32_t B, double tst
     if (const int rc = pssResolve(eng, "csim_pss_batch", true, tstep, f0, n_harm, probe_eq, n_probe, tol, max_rounds, p)) return rc;
     HIPCHK(hipSetDevice(eng->device));
     const int N = eng->plan.N, H1 = p.nHarm + 1;
-    DevBuf dParams, dX, dIters, dStatus, dHarm, dRounds;
-    if (const int rc = csim::stageParams(eng, params, B, dParams)) return rc;
-    HIPCHK(dX.alloc(sizeof(double) * (size_t)N * B));
-    HIPCHK(dIters.alloc(sizeof(int32_t) * (size_t)B));
-    HIPCHK(dStatus.alloc(sizeof(uint32_t) * (size_t)B));
-    HIPCHK(dHarm.alloc(sizeof(double) * 2 * (size_t)H1 * p.nProbe * B));
-    HIPCHK(dRounds.alloc(sizeof(int32_t) * (size_t)B));
-    if (const int rc = csim_dc_batch_dev(eng, dParams.as<double>(), B, dX.as<double>(), dIters.as<int32_t>(),
-                                         dStatus.as<uint32_t>(), nullptr)) return rc;
-    if (const int rc = csim_pss_batch_dev(eng, dParams.as<double>(), B, p.tstep, p.f0, p.nHarm, probe_eq, n_probe, p.tol,
-                                          p.maxRounds, dX.as<double>(), dHarm.as<double>(), dRounds.as<int32_t>(),
-                                          dStatus.as<uint32_t>(), nullptr)) return rc;
+    csim::PeriodHostState s;                                // as periodHostPrologue, but with the harmonics asked for
+    if (const int rc = csim::stageParams(eng, params, B, s.dParams)) return rc;
+    HIPCHK(s.dX.alloc(sizeof(double) * (size_t)N * B));
+    HIPCHK(s.dIters.alloc(sizeof(int32_t) * (size_t)B));
+    HIPCHK(s.dStatus.alloc(sizeof(uint32_t) * (size_t)B));
+    HIPCHK(s.dHarm.alloc(sizeof(double) * 2 * (size_t)H1 * p.nProbe * B));
+    HIPCHK(s.dRounds.alloc(sizeof(int32_t) * (size_t)B));
+    if (const int rc = csim_dc_batch_dev(eng, s.dParams.as<double>(), B, s.dX.as<double>(), s.dIters.as<int32_t>(),
+                                         s.dStatus.as<uint32_t>(), nullptr)) return rc;
+    if (const int rc = csim_pss_batch_dev(eng, s.dParams.as<double>(), B, p.tstep, p.f0, p.nHarm, probe_eq, n_probe, p.tol,
+                                          p.maxRounds, s.dX.as<double>(), s.dHarm.as<double>(), s.dRounds.as<int32_t>(),
+                                          s.dStatus.as<uint32_t>(), nullptr)) return rc;
     HIPCHK(hipDeviceSynchronize());
-    // [H+1][nProbe][B] complex -> [B][H+1][nProbe] complex, [N][B] -> [B][N]
+    // [H+1][nProbe][B] complex -> [B][H+1][nProbe] complex
     std::vector<double> h(2 * (size_t)H1 * p.nProbe * B);
-    HIPCHK(hipMemcpy(h.data(), dHarm.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.data(), s.dHarm.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
     for (size_t e = 0; e < (size_t)H1 * p.nProbe; ++e)
         for (int b = 0; b < B; ++b)
             for (int k = 0; k < 2; ++k) harm_out[2 * ((size_t)b * H1 * p.nProbe + e) + k] = h[2 * (e * B + b) + k];
-    if (x0_out) {
-        std::vector<double> x((size_t)N * B);
-        HIPCHK(hipMemcpy(x.data(), dX.p, sizeof(double) * x.size(), hipMemcpyDeviceToHost));
-        for (int i = 0; i < N; ++i)
-            for (int b = 0; b < B; ++b) x0_out[(size_t)b * N + i] = x[(size_t)i * B + b];
-    }
-    if (rounds) HIPCHK(hipMemcpy(rounds, dRounds.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    if (status) HIPCHK(hipMemcpy(status, dStatus.p, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    return CSIM_OK;
+    return csim::periodHostEpilogue(eng, B, s, x0_out, rounds, status);
 }
 
 } // extern "C"

@@ -1,4 +1,5 @@
-// kernels.hpp -- host-callable launchers of the HIP kernels (library-private).
+// kernels.hpp -- host-callable launchers of the HIP kernels (library-private), and the launch idiom of the
+// wave-per-workgroup kernels whose dynamic LDS may pass 64 KB (launchWave).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -7,6 +8,18 @@
 #include "device_common.hpp"
 
 namespace csim {
+
+// One 64-lane wavefront per workgroup with ldsBytes of dynamic LDS: above 64 KB the kernel's limit is raised first.
+template <class... Params, class... Args>
+inline hipError_t launchWave(void (*kernel)(Params...), dim3 grid, size_t ldsBytes, hipStream_t stream, const Args&... args)
+{
+    if (ldsBytes > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, grid, dim3(64), ldsBytes, stream, args...);
+    return hipGetLastError();
+}
 
 // The general DC and transient kernels (run-time pivoting, bit-faithful): one record and one launcher per analysis.
 // The launcher chooses the shape: four instances per wavefront with the matrix in registers (kernels_packed.hip)
@@ -246,8 +259,9 @@ size_t pssLdsBytes(const GenPlan& pl);
 // Periodic AC analysis (kernels_pac.hip) of chunk instances b0 .. b0+Bc-1 of a batch of B at Fc <= 32 frequencies:
 // the period kernel integrates the orbit from x0 as the periodic steady state does and carries the Fc complex
 // perturbations p_k as 2 Fc real columns (re at 2 f, im at 2 f + 1) through J_k p_k = z (Hm p_{k-1}) + u; the close
-// kernel solves (I - z_K W_K) p_0 = r_K per (instance, frequency).  One launch of the period kernel with p0 == null
-// (p_0 = 0, leaves r_K), the close kernel, a second launch from that p_0 with out != null (the sideband sums).
+// kernel (PeriodCloseArgs below) solves (I - z_K W_K) p_0 = r_K per (instance, frequency).  One launch of the period
+// kernel with p0 == null (p_0 = 0, leaves r_K), the close kernel, a second launch from that p_0 with out != null (the
+// sideband sums).
 // Probe equations are checked by the caller: they index LDS.
 struct PacArgs {
     const double* params;               // [P][B]
@@ -260,9 +274,7 @@ struct PacArgs {
     const double *twc, *tws;            // [K] cos and sin of 2 pi j / K
     const double *acRe, *acIm;          // [nElem] the AC excitation of the sources
     const double *zr, *zi;              // [Fc] z of this launch's frequencies
-    const double *zKr, *zKi;            // [Fc] z_K (close kernel)
     const double* x0;                   // [N][B] start of the period, not modified
-    const double* W;                    // [Bc][N][N] W_K (close kernel)
     const uint32_t* wStatus;            // [B] status of the launch that made W_K
     const double* p0;                   // [Bc][N][2 Fc] start of the recursion, or null = zero
     double* pK;                         // [Bc][N][2 Fc]: period kernel p_K out; close kernel r_K in, p_0 out (in place)
@@ -274,13 +286,26 @@ struct PacArgs {
 size_t pacLdsBytes(const GenPlan& pl, int Fc, int M, int nProbe);
 int pacMaxFc(const GenPlan& pl, int M, int nProbe);
 hipError_t launchPacPeriod(const GenPlan& pl, const PacArgs& a, hipStream_t stream);
-hipError_t launchPacClose(const GenPlan& pl, const PacArgs& a, hipStream_t stream);
+
+// The closure of the periodic AC and the periodic noise analysis (k_period_close, kernels_pac.hip), one wavefront per
+// (chunk instance, frequency): (I - z_K W_K) v = v in place, W_K read transposed for the adjoint (periodic noise).  A
+// singular closure stops the instance: stop[c] = 1, CSIM_ST_PAC_SINGULAR | CSIM_ST_LU_TINY_PIVOT into its status.
+struct PeriodCloseArgs {
+    int b0, Bc, Fc;
+    const double* W;                    // [Bc][N][N] W_K
+    const double *zKr, *zKi;            // [Fc] z_K of this launch's frequencies
+    double* v;                          // [Bc][N][2 Fc]: the right-hand sides in, the solutions out
+    int32_t* stop;                      // [Bc]: stopped instances are skipped
+    uint32_t* status;                   // [B], OR-ed
+    bool transposeW;
+};
+hipError_t launchPeriodClose(const GenPlan& pl, const PeriodCloseArgs& a, hipStream_t stream);
 
 // Periodic noise analysis (kernels_pnoise.hip) of chunk instances b0 .. b0+Bc-1 of a batch of B at Fc <= 32 output
 // frequencies.  The orbit kernel integrates the period from x0 as the periodic steady state does and stores every
 // converged state; the period kernel walks the stored orbit backwards, k = K .. 1, and carries the Fc complex adjoint
 // vectors as 2 Fc real columns (re at 2 f, im at 2 f + 1) through J_k^T q_k = z g_k + d, g_{k-1} = Hm^T q_k; the close
-// kernel solves (I - z_K W_K^T) g_K = r per (instance, frequency).  One launch of the period kernel with g0 == null
+// kernel (PeriodCloseArgs, transposeW) solves (I - z_K W_K^T) g_K = r per (instance, frequency).  One launch of the period kernel with g0 == null
 // (g_K = 0, leaves r in gK), the close kernel, a second launch with g0 == gK, which adds the transfer sums and stores
 // the outputs.  Generator S (one past the noise generators) is the input source with sigma = 1.  Output, input and
 // generator equations are checked by the caller: they index LDS.
@@ -292,10 +317,8 @@ struct PnoiseArgs {
     int Fc, fFirst, F;                  // frequencies of this launch, the first one's index among the F of the call
     const double *twc, *tws;            // [K] cos and sin of 2 pi j / K
     const double *zr, *zi;              // [Fc] z of this launch's frequencies
-    const double *zKr, *zKi;            // [Fc] z_K (close kernel)
     const double* x0;                   // [N][B] start of the period, not modified (orbit kernel)
     double* orbit;                      // [Bc][K][N]: x_1 .. x_K of every chunk instance
-    const double* W;                    // [Bc][N][N] W_K (close kernel)
     const uint32_t* wStatus;            // [B] status of the launch that made W_K (orbit kernel)
     int outP, outM;                     // d = +1 at outP, -1 at outM (-1: ground)
     int S;                              // noise generators
@@ -317,7 +340,6 @@ size_t pnoiseLdsBytes(const GenPlan& pl, int Fc, int M, int S);
 int pnoiseMaxFc(const GenPlan& pl, int M, int S);
 hipError_t launchPnoiseOrbit(const GenPlan& pl, const PnoiseArgs& a, hipStream_t stream);
 hipError_t launchPnoisePeriod(const GenPlan& pl, const PnoiseArgs& a, hipStream_t stream);
-hipError_t launchPnoiseClose(const GenPlan& pl, const PnoiseArgs& a, hipStream_t stream);
 
 // layout helpers (transpose.hip): [rows][cols] <-> [cols][rows] of doubles
 hipError_t launchTranspose(const double* dIn, double* dOut, int rows, int cols, hipStream_t stream);

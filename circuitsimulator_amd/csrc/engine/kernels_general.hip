@@ -20,16 +20,6 @@
 
 namespace csim {
 
-namespace {
-
-__device__ __forceinline__ bool wave_all_finite(double v, int N, int lane)
-{
-    const bool bad = (lane < N) && !isfinite(v);
-    return __ballot(bad) == 0ull;
-}
-
-} // namespace
-
 // ------------------------------------------------------------------ DC (K2)
 __global__ void __launch_bounds__(64)
 k_dc_general(GenPlan pl, GenDcArgs a)

@@ -1,14 +1,15 @@
 // kernels_pac.hip -- periodic AC analysis: the backward-Euler transient linearised around a periodic orbit
 // (include/csim.h "Periodic AC analysis", arithmetic in pac.hpp, budget and measurements in DESIGN.md 8i).
 //
-//   k_pac_period   one wavefront = one workgroup = one instance, N <= 63, Fc <= 32 frequencies.  K backward-Euler steps
-//                  from x0 whose body is k_tran_general's (the same device functions in the same order as k_pss_period,
-//                  so the orbit is that kernel's bit for bit); after every converged step Q = Hm P_{k-1}, P = z Q + u per
-//                  frequency, J_k at the converged iterate, P <- J_k^-1 P.  The first launch starts at p_0 = 0 and leaves
-//                  r_K; the second starts at the p_0 the close kernel solved for and adds the sideband sums, kept in LDS
-//                  and stored once.
-//   k_pac_close    one wavefront per (instance, frequency): (I - z_K W_K) p_0 = r_K through acw_solve, the project's
-//                  one complex LU.
+//   k_pac_period    one wavefront = one workgroup = one instance, N <= 63, Fc <= 32 frequencies.  K backward-Euler steps
+//                   from x0, each one period_newton_step (pss_device.hpp), the step k_pss_period takes, so the orbit is
+//                   that kernel's bit for bit; after every converged step Q = Hm P_{k-1}, P = z Q + u per frequency, J_k
+//                   at the converged iterate, P <- J_k^-1 P.  The first launch starts at p_0 = 0 and leaves r_K; the
+//                   second starts at the p_0 the close kernel solved for and adds the sideband sums, kept in LDS and
+//                   stored once.
+//   k_period_close  one wavefront per (instance, frequency): (I - z_K W_K) p_0 = r_K through acw_solve, the project's
+//                   one complex LU.  The periodic noise analysis closes its adjoint recursion with the same kernel and
+//                   W_K read transposed (PeriodCloseArgs::transposeW): one uniform branch where the matrix is filled.
 //
 // The P plane is N x 2 Fc real: frequency f has its real part in column 2 f and its imaginary part in column 2 f + 1, and
 // lane j owns column j as lu_solve_multi_wave wants.  LDS of the period kernel: the general kernel's carve-up, Hm
@@ -20,6 +21,7 @@
 #include "device_common.hpp"
 #include "kernels.hpp"
 #include "pac.hpp"
+#include "pnoise.hpp"
 #include "pss_device.hpp"
 
 namespace csim {
@@ -103,40 +105,15 @@ k_pac_period(GenPlan pl, PacArgs a)
     unsigned st = 0;
     bool stop = a.stop[c] != 0;
     const double xin = (lane < N) ? a.x0[(int64_t)lane * B + b] : 0.0;
-    if (!second) {
-        const unsigned in = a.status[b], ws = a.wStatus[b];
-        st |= ws & (CSIM_ST_TRAN_NONFINITE | CSIM_ST_TRAN_NONCONV | CSIM_ST_LU_TINY_PIVOT | CSIM_ST_LU_ZERO_DIAG);
-        if (ws & CSIM_ST_PSS_SINGULAR) st |= CSIM_ST_PAC_SINGULAR;
-        if (!pss_all_finite(xin, N, lane)) st |= CSIM_ST_TRAN_NONFINITE;
-        stop = ((in | st) & CSIM_ST_TRAN_NONFINITE) || (in & CSIM_ST_PSS_SINGULAR) || (st & CSIM_ST_PAC_SINGULAR);
-    }
+    if (!second) stop = period_start_status(a.status[b], a.wStatus[b], xin, N, lane, st);
     if (stop) {
         if (second) zeros_out();
         else if (lane == 0) { a.stop[c] = 1; a.status[b] |= st; }
         return;
     }
 
-    for (int p = lane; p < pl.P; p += 64) Pv[p] = a.params[(int64_t)p * B + b];
-    for (int t = lane; t < pl.nTerms; t += 64) T[t] = 0.0;
-    if (lane < N) { xs[lane] = xin; xp[lane] = 0.0; }
-    wave_sync();
-    terms_const<true>(pl, Pv, T, a.dt, lane);
-    if (lane == 0) T[pl.termGmin] = K.tran_gmin;
-    wave_sync();
-
-    // Hm = d(right-hand side)/d(x_prev), as k_pss_period forms it
-    pss_terms_history(pl, Pv, T, xp, lane);
-    pss_rhs(pl, T, sc, lane);
-    const double base = (lane < N) ? sc[lane] : 0.0;
-    for (int l = 0; l < N; ++l) {
-        if (lane == l) xp[l] = 1.0;
-        wave_sync();
-        pss_terms_history(pl, Pv, T, xp, lane);
-        pss_rhs(pl, T, sc, lane);
-        if (lane < N) Hm[lane * N + l] = sc[lane] - base;
-        if (lane == l) xp[l] = 0.0;
-        wave_sync();
-    }
+    period_load(pl, a.params, B, b, a.dt, Pv, T, xs, xin, xp, 0.0, lane);
+    period_hm(pl, Pv, T, xp, sc, Hm, N, 1, lane);
     // u: the right-hand side with the AC excitation in the source slots and every history zero, as the AC analysis has it
     pss_terms_history(pl, Pv, T, xp, lane);
     pac_set_sources(pl, T, a.acRe, lane);
@@ -160,45 +137,11 @@ k_pac_period(GenPlan pl, PacArgs a)
 
     bool aborted = false;
     for (long long s = 1; s <= a.K && !aborted; ++s) {
-        // ---- the step: k_tran_general's body
-        terms_step_tran(pl, Pv, T, xp, tran_time(s, a.dt), lane);
-        wave_sync();
-        for (int iter = 0; iter < K.tran_max_iters; ++iter) {
-            terms_iter_mos(pl, Pv, T, xs, lane);
-            wave_sync();
-            assemble(pl, T, Gm, lane);
-            const double xr = lu_solve_wave(Gm, N, LD, K.lu_eps, lane, st);
-            if (!pss_all_finite(xr, N, lane)) {
-                st |= CSIM_ST_TRAN_NONFINITE;
-                aborted = true;
-                break;
-            }
-            const double xo = (lane < N) ? xs[lane] : 0.0;
-            const double xn = xo + K.tran_alpha * (xr - xo);
-            const double err = norm_in_order(xn - xo, sc, N, lane);
-            if (lane < N) xs[lane] = xn;
-            wave_sync();
-            if (err < K.tran_tol) break;
-            if (iter == K.tran_max_iters - 1) st |= CSIM_ST_TRAN_NONCONV;
-        }
-        if (aborted) break;
-        if (lane < N) xp[lane] = xs[lane];
-        wave_sync();
+        // ---- the step, k_pss_period's
+        if (!period_newton_step(pl, Pv, T, Gm, xs, xp, sc, s, a.dt, lane, st)) { aborted = true; break; }
 
         // ---- Q = Hm P_{k-1}, walking the non-zeros of Hm's row; P = z Q + u per frequency
-        for (int i = 0; i < N; ++i) {
-            const double hv = (lane < N) ? Hm[i * N + lane] : 0.0;
-            unsigned long long todo = __ballot(hv != 0.0);
-            double acc = 0.0;
-            while (todo) {
-                const int l = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                const double h = read_lane(hv, l);
-                if (lane < R) acc = pac_hm_add(acc, h, Pm[l * R + lane]);
-            }
-            if (lane < R) Qm[i * R + lane] = acc;
-        }
-        wave_sync();
+        period_hm_product(Hm, N, Pm, R, Qm, R, R, lane);
         for (int i = 0; i < N; ++i)
             if (lane < R) {
                 double re, im;
@@ -254,8 +197,9 @@ k_pac_period(GenPlan pl, PacArgs a)
     }
 }
 
+// the closure of both analyses that carry a recursion round the orbit: v <- (I - z_K W_K)^-1 v, or with W_K^T
 __global__ void __launch_bounds__(64)
-k_pac_close(int N, double eps, PacArgs a)
+k_period_close(int N, double eps, PeriodCloseArgs a)
 {
     extern __shared__ double sm[];
     const int lane = threadIdx.x;
@@ -265,18 +209,19 @@ k_pac_close(int N, double eps, PacArgs a)
     const int LD = acw_ld(N, 1);
     const AcwLds m = acw_carve(sm, N, 1, LD);
     const double* W = a.W + (size_t)c * (size_t)(N * N);
-    double* pK = a.pK + (size_t)c * (size_t)(N * R);
+    double* v = a.v + (size_t)c * (size_t)(N * R);
     const double zKr = a.zKr[f], zKi = a.zKi[f];
     for (int idx = lane; idx < N * N; idx += 64) {
         const int i = idx / N, j = idx - i * N;
         double re, im;
-        pac_close_entry(i, j, W[idx], zKr, zKi, &re, &im);
+        if (a.transposeW) pnoise_close_entry(i, j, N, W, zKr, zKi, &re, &im);
+        else pac_close_entry(i, j, W[idx], zKr, zKi, &re, &im);
         m.Ar[i * LD + j] = re;
         m.Ai[i * LD + j] = im;
     }
     if (lane < N) {
-        m.Ar[lane * LD + N] = pK[lane * R + 2 * f];
-        m.Ai[lane * LD + N] = pK[lane * R + 2 * f + 1];
+        m.Ar[lane * LD + N] = v[lane * R + 2 * f];
+        m.Ai[lane * LD + N] = v[lane * R + 2 * f + 1];
     }
     wave_sync();
     const bool failed = acw_solve(N, 1, LD, m.Ar, m.Ai, m.Lr, m.Li, m.Xr, m.Xi, eps * eps, lane);
@@ -288,8 +233,8 @@ k_pac_close(int N, double eps, PacArgs a)
         return;
     }
     if (lane < N) {
-        pK[lane * R + 2 * f] = m.Xr[lane];
-        pK[lane * R + 2 * f + 1] = m.Xi[lane];
+        v[lane * R + 2 * f] = m.Xr[lane];
+        v[lane * R + 2 * f + 1] = m.Xi[lane];
     }
 }
 
@@ -310,24 +255,13 @@ hipError_t launchPacPeriod(const GenPlan& pl, const PacArgs& a, hipStream_t stre
     if (pl.N < 1 || pl.N > 63 || a.Fc < 1 || a.Fc > PAC_MAX_FC || a.M < 0 || a.nProbe < 0) return hipErrorInvalidValue;
     const size_t lds = pacLdsBytes(pl, a.Fc, a.M, a.nProbe);
     if (lds > PAC_LDS_LIMIT) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*)k_pac_period, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_pac_period, dim3(a.Bc), dim3(64), lds, stream, pl, a);
-    return hipGetLastError();
+    return launchWave(k_pac_period, dim3(a.Bc), lds, stream, pl, a);
 }
 
-hipError_t launchPacClose(const GenPlan& pl, const PacArgs& a, hipStream_t stream)
+hipError_t launchPeriodClose(const GenPlan& pl, const PeriodCloseArgs& a, hipStream_t stream)
 {
     if (pl.N < 1 || pl.N > 63 || a.Fc < 1 || a.Fc > PAC_MAX_FC) return hipErrorInvalidValue;
-    const size_t lds = acw_lds_bytes(pl.N, 1);
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*)k_pac_close, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_pac_close, dim3(a.Bc, a.Fc), dim3(64), lds, stream, pl.N, pl.k.lu_eps, a);
-    return hipGetLastError();
+    return launchWave(k_period_close, dim3(a.Bc, a.Fc), acw_lds_bytes(pl.N, 1), stream, pl.N, pl.k.lu_eps, a);
 }
 
 } // namespace csim

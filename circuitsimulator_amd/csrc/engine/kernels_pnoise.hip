@@ -1,16 +1,17 @@
 // kernels_pnoise.hip -- periodic noise analysis: the adjoint of the periodic AC recursion, backwards over a stored orbit
 // (include/csim.h "Periodic noise analysis", arithmetic in pnoise.hpp, budget and measurements in DESIGN.md 8j).
 //
-//   k_pnoise_orbit   one wavefront = one workgroup = one instance, N <= 63.  K backward-Euler steps from x0 whose body
-//                    is k_tran_general's (the same device functions in the same order as k_pss_period and k_pac_period,
-//                    so the orbit is theirs bit for bit); every converged x_k goes to the orbit store [c][k][N].
+//   k_pnoise_orbit   one wavefront = one workgroup = one instance, N <= 63.  K backward-Euler steps from x0, each one
+//                    period_newton_step (pss_device.hpp), the step k_pss_period and k_pac_period take, so the orbit is
+//                    theirs bit for bit; every converged x_k goes to the orbit store [c][k][N].
 //   k_pnoise_period  one wavefront per instance, Fc <= 32 output frequencies.  k = K .. 1: x_k from the store, one MOSFET
 //                    pass and one assembly of J_k, transposed (no Newton iterations), the right-hand side z g_k + d, the
 //                    real LU on 2 Fc columns, the generators' sigma from the same MOSFET pass, the transfer sums (second
 //                    pass only, kept in LDS and stored once), g_{k-1} = Hm^T q_k.  The first launch starts at g_K = 0
 //                    and leaves r; the second starts at the g_K the close kernel solved for.
-//   k_pnoise_close   one wavefront per (instance, frequency): (I - z_K W_K^T) g_K = r through acw_solve, the project's
-//                    one complex LU: k_pac_close with W read transposed.
+//
+// The close kernel, (I - z_K W_K^T) g_K = r per (instance, frequency), is k_period_close (kernels_pac.hip) with W read
+// transposed.
 //
 // The g and q planes are N x 2 Fc real: frequency f has its real part in column 2 f and its imaginary part in column
 // 2 f + 1, and lane j owns column j as lu_solve_multi_wave wants.  LDS of the period kernel: the general kernel's
@@ -81,60 +82,22 @@ k_pnoise_orbit(GenPlan pl, PnoiseArgs a)
     double* xs = sm + L.xs;
     double* xp = sm + L.xp;
     double* sc = sm + L.sc;
-    const csim_consts& K = pl.k;
 
-    // an instance stops before it starts: a start vector, an earlier analysis or the W_K launch that was not finite or
-    // singular, as in k_pac_period
     unsigned st = 0;
     const double xin = (lane < N) ? a.x0[(int64_t)lane * B + b] : 0.0;
-    const unsigned in = a.status[b], ws = a.wStatus[b];
-    st |= ws & (CSIM_ST_TRAN_NONFINITE | CSIM_ST_TRAN_NONCONV | CSIM_ST_LU_TINY_PIVOT | CSIM_ST_LU_ZERO_DIAG);
-    if (ws & CSIM_ST_PSS_SINGULAR) st |= CSIM_ST_PAC_SINGULAR;
-    if (!pss_all_finite(xin, N, lane)) st |= CSIM_ST_TRAN_NONFINITE;
-    if (((in | st) & CSIM_ST_TRAN_NONFINITE) || (in & CSIM_ST_PSS_SINGULAR) || (st & CSIM_ST_PAC_SINGULAR)) {
+    if (period_start_status(a.status[b], a.wStatus[b], xin, N, lane, st)) {
         if (lane == 0) { a.orbitStop[c] = 1; a.status[b] |= st; }
         return;
     }
 
-    for (int p = lane; p < pl.P; p += 64) Pv[p] = a.params[(int64_t)p * B + b];
-    for (int t = lane; t < pl.nTerms; t += 64) T[t] = 0.0;
-    if (lane < N) { xs[lane] = xin; xp[lane] = xin; }                   // histories come from the previous state
-    wave_sync();
-    terms_const<true>(pl, Pv, T, a.dt, lane);
-    if (lane == 0) T[pl.termGmin] = K.tran_gmin;
-    wave_sync();
+    period_load(pl, a.params, B, b, a.dt, Pv, T, xs, xin, xp, xin, lane);   // histories come from the previous state
 
     double* orbit = a.orbit + (size_t)c * (size_t)a.K * (size_t)N;
     bool aborted = false;
     for (long long s = 1; s <= a.K && !aborted; ++s) {
-        // ---- the step: k_tran_general's body
-        terms_step_tran(pl, Pv, T, xp, tran_time(s, a.dt), lane);
-        wave_sync();
-        for (int iter = 0; iter < K.tran_max_iters; ++iter) {
-            terms_iter_mos(pl, Pv, T, xs, lane);
-            wave_sync();
-            assemble(pl, T, Gm, lane);
-            const double xr = lu_solve_wave(Gm, N, LD, K.lu_eps, lane, st);
-            if (!pss_all_finite(xr, N, lane)) {
-                st |= CSIM_ST_TRAN_NONFINITE;
-                aborted = true;
-                break;
-            }
-            const double xo = (lane < N) ? xs[lane] : 0.0;
-            const double xn = xo + K.tran_alpha * (xr - xo);
-            const double err = norm_in_order(xn - xo, sc, N, lane);
-            if (lane < N) xs[lane] = xn;
-            wave_sync();
-            if (err < K.tran_tol) break;
-            if (iter == K.tran_max_iters - 1) st |= CSIM_ST_TRAN_NONCONV;
-        }
-        if (aborted) break;
-        if (lane < N) {
-            const double v = xs[lane];
-            xp[lane] = v;
-            orbit[(size_t)(s - 1) * (size_t)N + lane] = v;
-        }
-        wave_sync();
+        // ---- the step, k_pss_period's; every converged state goes to the store
+        if (!period_newton_step(pl, Pv, T, Gm, xs, xp, sc, s, a.dt, lane, st)) { aborted = true; break; }
+        if (lane < N) orbit[(size_t)(s - 1) * (size_t)N + lane] = xs[lane];
     }
     if (lane == 0) {
         a.status[b] |= st;
@@ -191,27 +154,8 @@ k_pnoise_period(GenPlan pl, PnoiseArgs a)
     }
 
     unsigned st = 0;
-    for (int p = lane; p < pl.P; p += 64) Pv[p] = a.params[(int64_t)p * B + b];
-    for (int t = lane; t < pl.nTerms; t += 64) T[t] = 0.0;
-    if (lane < N) { xs[lane] = 0.0; xp[lane] = 0.0; }
-    wave_sync();
-    terms_const<true>(pl, Pv, T, a.dt, lane);
-    if (lane == 0) T[pl.termGmin] = K.tran_gmin;
-    wave_sync();
-
-    // Hm = d(right-hand side)/d(x_prev), as k_pss_period forms it; column l of Hm becomes row l of HmT
-    pss_terms_history(pl, Pv, T, xp, lane);
-    pss_rhs(pl, T, sc, lane);
-    const double base = (lane < N) ? sc[lane] : 0.0;
-    for (int l = 0; l < N; ++l) {
-        if (lane == l) xp[l] = 1.0;
-        wave_sync();
-        pss_terms_history(pl, Pv, T, xp, lane);
-        pss_rhs(pl, T, sc, lane);
-        if (lane < N) HmT[l * N + lane] = sc[lane] - base;
-        if (lane == l) xp[l] = 0.0;
-        wave_sync();
-    }
+    period_load(pl, a.params, B, b, a.dt, Pv, T, xs, 0.0, xp, 0.0, lane);
+    period_hm(pl, Pv, T, xp, sc, HmT, 1, N, lane);                      // column l of Hm becomes row l of HmT
     for (int g = lane; g < nGen; g += 64) {
         term[2 * g] = g < S ? a.srcA[g] : a.inA;
         term[2 * g + 1] = g < S ? a.srcB[g] : a.inB;
@@ -281,19 +225,7 @@ k_pnoise_period(GenPlan pl, PnoiseArgs a)
         }
 
         // ---- g = Hm^T q, walking the non-zeros of Hm's column
-        for (int i = 0; i < N; ++i) {
-            const double hv = (lane < N) ? HmT[i * N + lane] : 0.0;
-            unsigned long long todo = __ballot(hv != 0.0);
-            double acc = 0.0;
-            while (todo) {
-                const int l = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                const double h = read_lane(hv, l);
-                if (lane < R) acc = pac_hm_add(acc, h, Qp[l * R + lane]);
-            }
-            if (lane < R) Gp[i * R + lane] = acc;
-        }
-        wave_sync();
+        period_hm_product(HmT, N, Qp, R, Gp, R, R, lane);
     }
 
     if (lane == 0) {
@@ -351,45 +283,6 @@ k_pnoise_period(GenPlan pl, PnoiseArgs a)
     }
 }
 
-__global__ void __launch_bounds__(64)
-k_pnoise_close(int N, double eps, PnoiseArgs a)
-{
-    extern __shared__ double sm[];
-    const int lane = threadIdx.x;
-    const int c = blockIdx.x, f = blockIdx.y, b = a.b0 + c;
-    if (a.stop[c]) return;
-    const int R = 2 * a.Fc;
-    const int LD = acw_ld(N, 1);
-    const AcwLds m = acw_carve(sm, N, 1, LD);
-    const double* W = a.W + (size_t)c * (size_t)(N * N);
-    double* gK = a.gK + (size_t)c * (size_t)(N * R);
-    const double zKr = a.zKr[f], zKi = a.zKi[f];
-    for (int idx = lane; idx < N * N; idx += 64) {
-        const int i = idx / N, j = idx - i * N;
-        double re, im;
-        pnoise_close_entry(i, j, N, W, zKr, zKi, &re, &im);
-        m.Ar[i * LD + j] = re;
-        m.Ai[i * LD + j] = im;
-    }
-    if (lane < N) {
-        m.Ar[lane * LD + N] = gK[lane * R + 2 * f];
-        m.Ai[lane * LD + N] = gK[lane * R + 2 * f + 1];
-    }
-    wave_sync();
-    const bool failed = acw_solve(N, 1, LD, m.Ar, m.Ai, m.Lr, m.Li, m.Xr, m.Xi, eps * eps, lane);
-    if (failed) {
-        if (lane == 0) {
-            a.stop[c] = 1;
-            atomicOr(&a.status[b], CSIM_ST_PAC_SINGULAR | CSIM_ST_LU_TINY_PIVOT);
-        }
-        return;
-    }
-    if (lane < N) {
-        gK[lane * R + 2 * f] = m.Xr[lane];
-        gK[lane * R + 2 * f + 1] = m.Xi[lane];
-    }
-}
-
 size_t pnoiseLdsBytes(const GenPlan& pl, int Fc, int M, int S)
 {
     return sizeof(double) * (size_t)pnoiseLds(pl.N, pl.LD, pl.nTerms, pl.P, Fc, M, S).total;
@@ -407,12 +300,7 @@ hipError_t launchPnoiseOrbit(const GenPlan& pl, const PnoiseArgs& a, hipStream_t
     if (pl.N < 1 || pl.N > 63 || a.K < 1 || !a.orbit) return hipErrorInvalidValue;
     const size_t lds = sizeof(double) * (size_t)ldsLayout(pl.N, pl.LD, pl.nTerms, pl.P).total;
     if (lds > PAC_LDS_LIMIT) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*)k_pnoise_orbit, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_pnoise_orbit, dim3(a.Bc), dim3(64), lds, stream, pl, a);
-    return hipGetLastError();
+    return launchWave(k_pnoise_orbit, dim3(a.Bc), lds, stream, pl, a);
 }
 
 hipError_t launchPnoisePeriod(const GenPlan& pl, const PnoiseArgs& a, hipStream_t stream)
@@ -421,24 +309,7 @@ hipError_t launchPnoisePeriod(const GenPlan& pl, const PnoiseArgs& a, hipStream_
     if (a.outP < 0 || a.outP >= pl.N || a.outM < -1 || a.outM >= pl.N || a.inA >= pl.N || a.inB >= pl.N) return hipErrorInvalidValue;
     const size_t lds = pnoiseLdsBytes(pl, a.Fc, a.M, a.S);
     if (lds > PAC_LDS_LIMIT) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*)k_pnoise_period, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_pnoise_period, dim3(a.Bc), dim3(64), lds, stream, pl, a);
-    return hipGetLastError();
-}
-
-hipError_t launchPnoiseClose(const GenPlan& pl, const PnoiseArgs& a, hipStream_t stream)
-{
-    if (pl.N < 1 || pl.N > 63 || a.Fc < 1 || a.Fc > PAC_MAX_FC) return hipErrorInvalidValue;
-    const size_t lds = acw_lds_bytes(pl.N, 1);
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*)k_pnoise_close, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_pnoise_close, dim3(a.Bc, a.Fc), dim3(64), lds, stream, pl.N, pl.k.lu_eps, a);
-    return hipGetLastError();
+    return launchWave(k_pnoise_period, dim3(a.Bc), lds, stream, pl, a);
 }
 
 } // namespace csim

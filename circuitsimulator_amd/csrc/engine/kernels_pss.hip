@@ -1,10 +1,11 @@
 // kernels_pss.hip -- periodic steady state by shooting Newton (include/csim.h "Periodic steady state", arithmetic
 // in pss.hpp, budget and measurements in DESIGN.md 8h).
 //
-//   k_pss_period   one wavefront = one workgroup = one instance, N <= 63.  K backward-Euler steps from x0 whose body is
-//                  k_tran_general's (the same device functions in the same order), so the trajectory is that kernel's
-//                  bit for bit; after every converged step the sensitivity W_k = J_k^-1 (Hm W_{k-1}) and the DFT sums of
-//                  the probes.  Leaves x_K, W_K and the harmonics of this period.
+//   k_pss_period   one wavefront = one workgroup = one instance, N <= 63.  K backward-Euler steps from x0, each one
+//                  period_newton_step (pss_device.hpp: k_tran_general's body, so the trajectory is that kernel's bit
+//                  for bit, and the one step the periodic AC and noise kernels take too); after every converged step
+//                  the sensitivity W_k = J_k^-1 (Hm W_{k-1}) and the DFT sums of the probes.  Leaves x_K, W_K and the
+//                  harmonics of this period.
 //   k_pss_update   one wavefront per instance: r = x_K - x0, the closure test, (I - W_K) d = r through lu_solve_wave,
 //                  x0 += d; counts the instances that go on.
 //
@@ -49,7 +50,7 @@ k_pss_period(GenPlan pl, PssArgs a)
 
     unsigned st = a.status[b] & CSIM_ST_TRAN_NONFINITE;
     const double xin = (lane < N) ? a.x0[(int64_t)lane * B + b] : 0.0;
-    if (!pss_all_finite(xin, N, lane)) st |= CSIM_ST_TRAN_NONFINITE;    // a start vector that is not finite stops its instance
+    if (!wave_all_finite(xin, N, lane)) st |= CSIM_ST_TRAN_NONFINITE;    // a start vector that is not finite stops its instance
     const int nAcc = (a.H + 1) * a.nProbe;
     for (int idx = lane; idx < nAcc; idx += 64) {                       // the sums start at zero; a stopped instance reports zeros
         const size_t at = pss_harm_at(a, idx, b);
@@ -61,28 +62,8 @@ k_pss_period(GenPlan pl, PssArgs a)
         return;                                                         // the update kernel closes the instance
     }
 
-    for (int p = lane; p < pl.P; p += 64) Pv[p] = a.params[(int64_t)p * B + b];
-    for (int t = lane; t < pl.nTerms; t += 64) T[t] = 0.0;
-    if (lane < N) { xs[lane] = xin; xp[lane] = 0.0; }
-    wave_sync();
-    terms_const<true>(pl, Pv, T, a.dt, lane);
-    if (lane == 0) T[pl.termGmin] = K.tran_gmin;
-    wave_sync();
-
-    // Hm = d(right-hand side)/d(x_prev): the history currents are linear and source-free in xp, and no MOS term has
-    // been written yet, so column l is rhs(e_l) - rhs(0) with both exact
-    pss_terms_history(pl, Pv, T, xp, lane);
-    pss_rhs(pl, T, sc, lane);
-    const double base = (lane < N) ? sc[lane] : 0.0;
-    for (int l = 0; l < N; ++l) {
-        if (lane == l) xp[l] = 1.0;
-        wave_sync();
-        pss_terms_history(pl, Pv, T, xp, lane);
-        pss_rhs(pl, T, sc, lane);
-        if (lane < N) Hm[lane * N + l] = sc[lane] - base;
-        if (lane == l) xp[l] = 0.0;
-        wave_sync();
-    }
+    period_load(pl, a.params, B, b, a.dt, Pv, T, xs, xin, xp, 0.0, lane);
+    period_hm(pl, Pv, T, xp, sc, Hm, N, 1, lane);
     for (int i = 0; i < N; ++i)
         if (lane < N) Wm[i * N + lane] = (i == lane) ? 1.0 : 0.0;     // W_0 = I
     if (lane < N) xp[lane] = xin;                                       // histories come from the previous state
@@ -90,45 +71,11 @@ k_pss_period(GenPlan pl, PssArgs a)
 
     bool aborted = false;
     for (long long s = 1; s <= a.K && !aborted; ++s) {
-        // ---- the step: k_tran_general's body
-        terms_step_tran(pl, Pv, T, xp, tran_time(s, a.dt), lane);
-        wave_sync();
-        for (int iter = 0; iter < K.tran_max_iters; ++iter) {
-            terms_iter_mos(pl, Pv, T, xs, lane);
-            wave_sync();
-            assemble(pl, T, Gm, lane);
-            const double xr = lu_solve_wave(Gm, N, LD, K.lu_eps, lane, st);
-            if (!pss_all_finite(xr, N, lane)) {
-                st |= CSIM_ST_TRAN_NONFINITE;
-                aborted = true;
-                break;
-            }
-            const double xo = (lane < N) ? xs[lane] : 0.0;
-            const double xn = xo + K.tran_alpha * (xr - xo);
-            const double err = norm_in_order(xn - xo, sc, N, lane);
-            if (lane < N) xs[lane] = xn;
-            wave_sync();
-            if (err < K.tran_tol) break;
-            if (iter == K.tran_max_iters - 1) st |= CSIM_ST_TRAN_NONCONV;
-        }
-        if (aborted) break;
-        if (lane < N) xp[lane] = xs[lane];
-        wave_sync();
+        // ---- the step
+        if (!period_newton_step(pl, Pv, T, Gm, xs, xp, sc, s, a.dt, lane, st)) { aborted = true; break; }
 
         // ---- sensitivity: Hm W_{k-1} into the matrix area (dead here), over W, then J_k at the converged iterate
-        for (int i = 0; i < N; ++i) {
-            const double hv = (lane < N) ? Hm[i * N + lane] : 0.0;
-            unsigned long long todo = __ballot(hv != 0.0);
-            double acc = 0.0;
-            while (todo) {
-                const int l = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                const double h = read_lane(hv, l);
-                if (lane < N) acc += h * Wm[l * N + lane];
-            }
-            if (lane < N) Gm[i * LD + lane] = acc;
-        }
-        wave_sync();
+        period_hm_product(Hm, N, Wm, N, Gm, LD, N, lane);
         for (int i = 0; i < N; ++i)
             if (lane < N) Wm[i * N + lane] = Gm[i * LD + lane];
         wave_sync();
@@ -219,13 +166,7 @@ size_t pssLdsBytes(const GenPlan& pl)
 hipError_t launchPssPeriod(const GenPlan& pl, const PssArgs& a, hipStream_t stream)
 {
     if (pl.N < 1 || pl.N > 63) return hipErrorInvalidValue;
-    const size_t lds = pssLdsBytes(pl);
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*)k_pss_period, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_pss_period, dim3(a.Bc), dim3(64), lds, stream, pl, a);
-    return hipGetLastError();
+    return launchWave(k_pss_period, dim3(a.Bc), pssLdsBytes(pl), stream, pl, a);
 }
 
 hipError_t launchPssRound(const GenPlan& pl, const PssArgs& a, hipStream_t stream)

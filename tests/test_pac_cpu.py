@@ -313,6 +313,6 @@ def test_pac_kernel_registers(tmp_path):
         num = lambda key: int(re.search(key + r": (\d+)", blk).group(1))     # noqa: E731
         seen[fn] = (num(r"VGPRs"), num(r"ScratchSize \[bytes/lane\]"), num(r"VGPRs Spill"))
     print(seen)
-    assert any("k_pac_period" in k for k in seen) and any("k_pac_close" in k for k in seen)
+    assert any("k_pac_period" in k for k in seen) and any("k_period_close" in k for k in seen)
     for fn, (vgpr, scratch, spill) in seen.items():
         assert scratch == 0 and spill == 0, (fn, vgpr, scratch, spill)

@@ -394,7 +394,7 @@ def test_pnoise_kernel_registers(tmp_path):
         num = lambda key: int(re.search(key + r": (\d+)", blk).group(1))     # noqa: E731
         seen[fn] = (num(r"VGPRs"), num(r"ScratchSize \[bytes/lane\]"), num(r"VGPRs Spill"))
     print(seen)
-    for k in ("k_pnoise_orbit", "k_pnoise_period", "k_pnoise_close"):
+    for k in ("k_pnoise_orbit", "k_pnoise_period"):
         assert any(k in fn for fn in seen), k
     for fn, (vgpr, scratch, spill) in seen.items():
         assert scratch == 0 and spill == 0, (fn, vgpr, scratch, spill)
