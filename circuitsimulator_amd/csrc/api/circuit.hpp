@@ -109,4 +109,26 @@ struct CircuitIR {
 // src/main.cpp:34, this is the caller's duty).
 CircuitIR flatten(const Circuit& ckt);
 
+// The two name lookups of an indexed circuit, as every card and tool resolves a name:
+// a node's name as written -> its equation (-1: the ground node), -2: a name the circuit does not have
+inline int nodeEquation(const Circuit& ckt, const std::string& name)
+{
+    const auto hit = ckt.nodeNameToId.find(name);
+    return hit == ckt.nodeNameToId.end() ? -2 : ckt.nodes[static_cast<std::size_t>(hit->second)].eqIndex;
+}
+
+// a node named on a card, V(out[,ref]): "0" is ground, and so is a reference that is left out
+inline int cardNodeEquation(const Circuit& ckt, const std::string& name)
+{
+    return name.empty() || name == "0" ? -1 : nodeEquation(ckt, name);
+}
+
+// an element's name in either letter case -> its index, `none`: a name the circuit does not have
+inline int elementIndex(const Circuit& ckt, const std::string& name, int none)
+{
+    for (std::size_t e = 0; e < ckt.elements.size(); ++e)
+        if (toLower(ckt.elements[e]->getName()) == toLower(name)) return static_cast<int>(e);
+    return none;
+}
+
 } // namespace csim

@@ -480,157 +480,141 @@ void NetlistParser::tranCard(const Statement& st)
     sim.tran = cfg;
 }
 
-// .AC {LIN|DEC|OCT} npoints fstart fstop
+// ---- what the sweep cards share: each rule is written once ---------------------
+
+void NetlistParser::invalidSyntax(const Statement& st, const char* card)
+{
+    std::cerr << "Line " << st.lineNo << ": invalid " << card << " syntax: " << st.raw << "\n";
+}
+
+bool NetlistParser::cannotParse(const Statement& st, const char* card, const char* what)
+{
+    std::cerr << "Line " << st.lineNo << ": cannot parse " << card << " arguments: " << what << " in '" << st.raw << "'\n";
+    return false;
+}
+
+// LIN | OCT | DEC in either case -> out.  Any other word is DEC; strict: and false (the reference's .AC takes any word
+// for DEC, src/parser.cpp:435-439; the cards added here refuse it)
+bool NetlistParser::sweepWord(const std::string& token, bool strict, AcSweepType& out)
+{
+    const std::string w = toLower(token);
+    out = w == "lin" ? AcSweepType::LIN : (w == "oct" ? AcSweepType::OCT : AcSweepType::DEC);
+    return !strict || w == "lin" || w == "oct" || w == "dec";
+}
+
+// npoints fstart fstop at t[at .. at + 2] -> the grid, enabled.  A trailing tail of the point count is accepted (stoi).
+bool NetlistParser::sweepGrid(const Statement& st, const std::vector<std::string>& t, std::size_t at, const char* card,
+                              AcConfig& grid)
+{
+    try {
+        grid.nPoints = std::stoi(t[at]);
+        grid.fstart  = parseSpiceNumber(t[at + 1]);
+        grid.fstop   = parseSpiceNumber(t[at + 2]);
+    } catch (const std::exception& e) {
+        return cannotParse(st, card, e.what());
+    }
+    grid.enabled = true;
+    return true;
+}
+
+// nside: a whole number >= 0, nothing after it; reported as the grid's numbers are
+bool NetlistParser::sideCount(const Statement& st, const std::string& token, const char* card, int& nSide)
+{
+    try {
+        std::size_t used = 0;
+        nSide = std::stoi(token, &used);
+        if (used != token.size() || nSide < 0) throw std::invalid_argument("nside must be a whole number >= 0");
+    } catch (const std::exception& e) {
+        return cannotParse(st, card, e.what());
+    }
+    return true;
+}
+
+// the output may be written with blanks inside its parentheses: the tokens with t[1] joined up to the closing one
+std::vector<std::string> NetlistParser::joinOutput(const std::vector<std::string>& tokens)
+{
+    std::vector<std::string> t;
+    for (std::size_t i = 0; i < tokens.size(); ++i) {
+        if (i >= 2 && t.size() == 2 && t[1].find('(') != std::string::npos && t[1].find(')') == std::string::npos)
+            t[1] += tokens[i];
+        else
+            t.push_back(tokens[i]);
+    }
+    return t;
+}
+
+// where the sweep word of V(out[,ref]) [src] {sweep} ... stands: at 2 when the source is left out, else 3
+std::size_t NetlistParser::sweepAfterOutput(const std::vector<std::string>& t)
+{
+    AcSweepType word;
+    return t.size() > 2 && sweepWord(t[2], true, word) ? 2 : 3;
+}
+
+// t[1] = V(node) | V(node,ref), and t[2] the source when the sweep word stands at 3
+bool NetlistParser::outputPair(const Statement& st, const std::vector<std::string>& t, std::size_t at, const char* card,
+                               OutputPair& out)
+{
+    const ProbeSpec p = probeFromToken(t[1]);
+    if ((p.kind != ProbeKind::NodeVoltage && p.kind != ProbeKind::DiffVoltage) || p.node1.empty()) {
+        std::cerr << "Line " << st.lineNo << ": " << card << " output must be V(node) or V(node,ref): " << st.raw << "\n";
+        return false;
+    }
+    out.outNode = p.node1;
+    out.refNode = p.node2;
+    if (at == 3) out.srcName = t[2];
+    return true;
+}
+
+// ---- the cards: token count and sweep word, then the output, then the numbers; a card that fails changes nothing ----
+
+// .AC {LIN|DEC|OCT} npoints fstart fstop   (further tokens are ignored)
 void NetlistParser::acCard(const Statement& st)
 {
     const auto& t = st.tokens;
-    if (t.size() < 5) {
-        std::cerr << "Line " << st.lineNo << ": invalid .AC syntax: " << st.raw << "\n";
-        return;
-    }
+    if (t.size() < 5) return invalidSyntax(st, ".AC");
     AcConfig cfg;
-    const std::string sweep = toLower(t[1]);
-    cfg.sweepType = sweep == "lin" ? AcSweepType::LIN : (sweep == "oct" ? AcSweepType::OCT : AcSweepType::DEC);
-    try {
-        cfg.nPoints = std::stoi(t[2]);
-        cfg.fstart  = parseSpiceNumber(t[3]);
-        cfg.fstop   = parseSpiceNumber(t[4]);
-    } catch (const std::exception& e) {
-        std::cerr << "Line " << st.lineNo << ": cannot parse .AC arguments: " << e.what()
-                  << " in '" << st.raw << "'\n";
-        return;
-    }
-    cfg.enabled = true;
-    sim.ac = cfg;
+    sweepWord(t[1], false, cfg.sweepType);
+    if (sweepGrid(st, t, 2, ".AC", cfg)) sim.ac = cfg;
 }
 
 // .SP {LIN|DEC|OCT} npoints fstart fstop [0|1]   (a sixth token 1: noise too; anything else is ignored)
 void NetlistParser::spCard(const Statement& st)
 {
     const auto& t = st.tokens;
-    const std::string sweep = t.size() > 1 ? toLower(t[1]) : std::string();
-    if (t.size() < 5 || (sweep != "lin" && sweep != "oct" && sweep != "dec")) {
-        std::cerr << "Line " << st.lineNo << ": invalid .SP syntax: " << st.raw << "\n";
-        return;
-    }
     SpConfig cfg;
-    cfg.sweepType = sweep == "lin" ? AcSweepType::LIN : (sweep == "oct" ? AcSweepType::OCT : AcSweepType::DEC);
-    try {
-        cfg.nPoints = std::stoi(t[2]);
-        cfg.fstart  = parseSpiceNumber(t[3]);
-        cfg.fstop   = parseSpiceNumber(t[4]);
-    } catch (const std::exception& e) {
-        std::cerr << "Line " << st.lineNo << ": cannot parse .SP arguments: " << e.what()
-                  << " in '" << st.raw << "'\n";
-        return;
-    }
+    if (t.size() < 5 || !sweepWord(t[1], true, cfg.sweepType)) return invalidSyntax(st, ".SP");
+    if (!sweepGrid(st, t, 2, ".SP", cfg)) return;
     cfg.doNoise = t.size() > 5 && t[5] == "1";
-    cfg.enabled = true;
     sim.sp = cfg;
 }
 
-// .NOISE V(out[,ref]) [src] {LIN|DEC|OCT} npoints fstart fstop
+// .NOISE V(out[,ref]) [src] {LIN|DEC|OCT} npoints fstart fstop   (further tokens are ignored)
 void NetlistParser::noiseCard(const Statement& st)
 {
-    // the output may be written with blanks inside its parentheses: join tokens up to the closing one
-    std::vector<std::string> t;
-    for (std::size_t i = 0; i < st.tokens.size(); ++i) {
-        if (i >= 2 && t.size() == 2 && t[1].find('(') != std::string::npos && t[1].find(')') == std::string::npos)
-            t[1] += st.tokens[i];
-        else
-            t.push_back(st.tokens[i]);
-    }
-    auto isSweep = [](const std::string& s) { const std::string l = toLower(s); return l == "dec" || l == "oct" || l == "lin"; };
-    const std::size_t at = t.size() > 2 && isSweep(t[2]) ? 2 : 3;      // the source may be left out
-    if (t.size() < at + 4 || !isSweep(t[at])) {
-        std::cerr << "Line " << st.lineNo << ": invalid .NOISE syntax: " << st.raw << "\n";
-        return;
-    }
-    const ProbeSpec out = probeFromToken(t[1]);
-    if ((out.kind != ProbeKind::NodeVoltage && out.kind != ProbeKind::DiffVoltage) || out.node1.empty()) {
-        std::cerr << "Line " << st.lineNo << ": .NOISE output must be V(node) or V(node,ref): " << st.raw << "\n";
-        return;
-    }
+    const std::vector<std::string> t = joinOutput(st.tokens);
+    const std::size_t at = sweepAfterOutput(t);
     NoiseConfig cfg;
-    cfg.outNode = out.node1;
-    cfg.refNode = out.node2;
-    if (at == 3) cfg.srcName = t[2];
-    const std::string sweep = toLower(t[at]);
-    cfg.sweepType = sweep == "lin" ? AcSweepType::LIN : (sweep == "oct" ? AcSweepType::OCT : AcSweepType::DEC);
-    try {
-        cfg.nPoints = std::stoi(t[at + 1]);
-        cfg.fstart  = parseSpiceNumber(t[at + 2]);
-        cfg.fstop   = parseSpiceNumber(t[at + 3]);
-    } catch (const std::exception& e) {
-        std::cerr << "Line " << st.lineNo << ": cannot parse .NOISE arguments: " << e.what()
-                  << " in '" << st.raw << "'\n";
-        return;
-    }
-    cfg.enabled = true;
-    sim.noise = cfg;
+    if (t.size() < at + 4 || !sweepWord(t[at], true, cfg.sweepType)) return invalidSyntax(st, ".NOISE");
+    if (outputPair(st, t, at, ".NOISE", cfg) && sweepGrid(st, t, at + 1, ".NOISE", cfg)) sim.noise = cfg;
 }
 
 // .DISTO V(out[,ref]) {LIN|DEC|OCT} npoints fstart fstop   (single tone: a further token, ngspice's f2overf1, is an error)
 void NetlistParser::distoCard(const Statement& st)
 {
-    // the output may be written with blanks inside its parentheses: join tokens up to the closing one
-    std::vector<std::string> t;
-    for (std::size_t i = 0; i < st.tokens.size(); ++i) {
-        if (i >= 2 && t.size() == 2 && t[1].find('(') != std::string::npos && t[1].find(')') == std::string::npos)
-            t[1] += st.tokens[i];
-        else
-            t.push_back(st.tokens[i]);
-    }
-    const std::string sweep = t.size() > 2 ? toLower(t[2]) : std::string();
-    if (t.size() != 6 || (sweep != "lin" && sweep != "oct" && sweep != "dec")) {
-        std::cerr << "Line " << st.lineNo << ": invalid .DISTO syntax: " << st.raw << "\n";
-        return;
-    }
-    const ProbeSpec out = probeFromToken(t[1]);
-    if ((out.kind != ProbeKind::NodeVoltage && out.kind != ProbeKind::DiffVoltage) || out.node1.empty()) {
-        std::cerr << "Line " << st.lineNo << ": .DISTO output must be V(node) or V(node,ref): " << st.raw << "\n";
-        return;
-    }
+    const std::vector<std::string> t = joinOutput(st.tokens);
     DistoConfig cfg;
-    cfg.outNode = out.node1;
-    cfg.refNode = out.node2;
-    cfg.sweepType = sweep == "lin" ? AcSweepType::LIN : (sweep == "oct" ? AcSweepType::OCT : AcSweepType::DEC);
-    try {
-        cfg.nPoints = std::stoi(t[3]);
-        cfg.fstart  = parseSpiceNumber(t[4]);
-        cfg.fstop   = parseSpiceNumber(t[5]);
-    } catch (const std::exception& e) {
-        std::cerr << "Line " << st.lineNo << ": cannot parse .DISTO arguments: " << e.what()
-                  << " in '" << st.raw << "'\n";
-        return;
-    }
-    cfg.enabled = true;
-    sim.disto = cfg;
+    if (t.size() != 6 || !sweepWord(t[2], true, cfg.sweepType)) return invalidSyntax(st, ".DISTO");
+    if (outputPair(st, t, 2, ".DISTO", cfg) && sweepGrid(st, t, 3, ".DISTO", cfg)) sim.disto = cfg;
 }
 
 // .STB Vprobe {LIN|DEC|OCT} npoints fstart fstop   (any other token count is an error)
 void NetlistParser::stbCard(const Statement& st)
 {
     const auto& t = st.tokens;
-    const std::string sweep = t.size() > 2 ? toLower(t[2]) : std::string();
-    if (t.size() != 6 || (sweep != "lin" && sweep != "oct" && sweep != "dec")) {
-        std::cerr << "Line " << st.lineNo << ": invalid .STB syntax: " << st.raw << "\n";
-        return;
-    }
     StbConfig cfg;
+    if (t.size() != 6 || !sweepWord(t[2], true, cfg.sweepType)) return invalidSyntax(st, ".STB");
     cfg.probeName = t[1];
-    cfg.sweepType = sweep == "lin" ? AcSweepType::LIN : (sweep == "oct" ? AcSweepType::OCT : AcSweepType::DEC);
-    try {
-        cfg.nPoints = std::stoi(t[3]);
-        cfg.fstart  = parseSpiceNumber(t[4]);
-        cfg.fstop   = parseSpiceNumber(t[5]);
-    } catch (const std::exception& e) {
-        std::cerr << "Line " << st.lineNo << ": cannot parse .STB arguments: " << e.what()
-                  << " in '" << st.raw << "'\n";
-        return;
-    }
-    cfg.enabled = true;
-    sim.stb = cfg;
+    if (sweepGrid(st, t, 3, ".STB", cfg)) sim.stb = cfg;
 }
 
 // .HB f0 nharm
@@ -658,28 +642,10 @@ void NetlistParser::hbCard(const Statement& st)
 void NetlistParser::pacCard(const Statement& st)
 {
     const auto& t = st.tokens;
-    const std::string sweep = t.size() > 1 ? toLower(t[1]) : std::string();
-    if ((t.size() != 5 && t.size() != 6) || (sweep != "lin" && sweep != "oct" && sweep != "dec")) {
-        std::cerr << "Line " << st.lineNo << ": invalid .PAC syntax: " << st.raw << "\n";
-        return;
-    }
     PacConfig cfg;
-    cfg.sweepType = sweep == "lin" ? AcSweepType::LIN : (sweep == "oct" ? AcSweepType::OCT : AcSweepType::DEC);
-    try {
-        cfg.nPoints = std::stoi(t[2]);
-        cfg.fstart  = parseSpiceNumber(t[3]);
-        cfg.fstop   = parseSpiceNumber(t[4]);
-        if (t.size() == 6) {
-            std::size_t used = 0;
-            cfg.nSide = std::stoi(t[5], &used);
-            if (used != t[5].size() || cfg.nSide < 0) throw std::invalid_argument("nside must be a whole number >= 0");
-        }
-    } catch (const std::exception& e) {
-        std::cerr << "Line " << st.lineNo << ": cannot parse .PAC arguments: " << e.what()
-                  << " in '" << st.raw << "'\n";
-        return;
-    }
-    cfg.enabled = true;
+    if ((t.size() != 5 && t.size() != 6) || !sweepWord(t[1], true, cfg.sweepType)) return invalidSyntax(st, ".PAC");
+    if (!sweepGrid(st, t, 2, ".PAC", cfg)) return;
+    if (t.size() == 6 && !sideCount(st, t[5], ".PAC", cfg.nSide)) return;
     sim.pac = cfg;
 }
 
@@ -687,46 +653,12 @@ void NetlistParser::pacCard(const Statement& st)
 // nside of .PAC (nside defaults to 1; any other token count is an error)
 void NetlistParser::pnoiseCard(const Statement& st)
 {
-    // the output may be written with blanks inside its parentheses: join tokens up to the closing one
-    std::vector<std::string> t;
-    for (std::size_t i = 0; i < st.tokens.size(); ++i) {
-        if (i >= 2 && t.size() == 2 && t[1].find('(') != std::string::npos && t[1].find(')') == std::string::npos)
-            t[1] += st.tokens[i];
-        else
-            t.push_back(st.tokens[i]);
-    }
-    auto isSweep = [](const std::string& s) { const std::string l = toLower(s); return l == "dec" || l == "oct" || l == "lin"; };
-    const std::size_t at = t.size() > 2 && isSweep(t[2]) ? 2 : 3;      // the source may be left out
-    if ((t.size() != at + 4 && t.size() != at + 5) || !isSweep(t[at])) {
-        std::cerr << "Line " << st.lineNo << ": invalid .PNOISE syntax: " << st.raw << "\n";
-        return;
-    }
-    const ProbeSpec out = probeFromToken(t[1]);
-    if ((out.kind != ProbeKind::NodeVoltage && out.kind != ProbeKind::DiffVoltage) || out.node1.empty()) {
-        std::cerr << "Line " << st.lineNo << ": .PNOISE output must be V(node) or V(node,ref): " << st.raw << "\n";
-        return;
-    }
+    const std::vector<std::string> t = joinOutput(st.tokens);
+    const std::size_t at = sweepAfterOutput(t);
     PnoiseConfig cfg;
-    cfg.outNode = out.node1;
-    cfg.refNode = out.node2;
-    if (at == 3) cfg.srcName = t[2];
-    const std::string sweep = toLower(t[at]);
-    cfg.sweepType = sweep == "lin" ? AcSweepType::LIN : (sweep == "oct" ? AcSweepType::OCT : AcSweepType::DEC);
-    try {
-        cfg.nPoints = std::stoi(t[at + 1]);
-        cfg.fstart  = parseSpiceNumber(t[at + 2]);
-        cfg.fstop   = parseSpiceNumber(t[at + 3]);
-        if (t.size() == at + 5) {
-            std::size_t used = 0;
-            cfg.nSide = std::stoi(t[at + 4], &used);
-            if (used != t[at + 4].size() || cfg.nSide < 0) throw std::invalid_argument("nside must be a whole number >= 0");
-        }
-    } catch (const std::exception& e) {
-        std::cerr << "Line " << st.lineNo << ": cannot parse .PNOISE arguments: " << e.what()
-                  << " in '" << st.raw << "'\n";
-        return;
-    }
-    cfg.enabled = true;
+    if ((t.size() != at + 4 && t.size() != at + 5) || !sweepWord(t[at], true, cfg.sweepType)) return invalidSyntax(st, ".PNOISE");
+    if (!outputPair(st, t, at, ".PNOISE", cfg) || !sweepGrid(st, t, at + 1, ".PNOISE", cfg)) return;
+    if (t.size() == at + 5 && !sideCount(st, t[at + 4], ".PNOISE", cfg.nSide)) return;
     sim.pnoise = cfg;
 }
 

@@ -61,6 +61,19 @@ private:
     void plotNcCard(const Statement& st);
 
     static ProbeSpec probeFromToken(const std::string& token);
+
+    // what the sweep cards share: the two diagnostics, the sweep word, `npoints fstart fstop`, nside, the joined
+    // V(out[,ref]) token, its check and the optional source behind it
+    static void invalidSyntax(const Statement& st, const char* card);
+    static bool cannotParse(const Statement& st, const char* card, const char* what);
+    static bool sweepWord(const std::string& token, bool strict, AcSweepType& out);
+    static bool sweepGrid(const Statement& st, const std::vector<std::string>& t, std::size_t at, const char* card,
+                          AcConfig& grid);
+    static bool sideCount(const Statement& st, const std::string& token, const char* card, int& nSide);
+    static std::vector<std::string> joinOutput(const std::vector<std::string>& tokens);
+    static std::size_t sweepAfterOutput(const std::vector<std::string>& t);
+    static bool outputPair(const Statement& st, const std::vector<std::string>& t, std::size_t at, const char* card,
+                           OutputPair& out);
 };
 
 inline bool parseNetlist(const std::string& filename, Circuit& ckt, SimulationConfig& sim)

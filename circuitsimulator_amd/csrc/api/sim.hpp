@@ -146,41 +146,30 @@ struct AcConfig {
     double fstart = 0.0, fstop = 0.0;
 };
 
-// .NOISE V(out[,ref]) [src] {DEC|OCT|LIN} n fstart fstop -- names as written; netlist_capi.cpp resolves them
-struct NoiseConfig {
-    bool enabled = false;
+// The one sweep grid: every card below carries it by deriving from AcConfig.  The engine's number of a sweep type
+// (csim_ac_freqs: 0 DEC, 1 OCT, 2 LIN):
+inline int acSweepCode(AcSweepType t) { return t == AcSweepType::DEC ? 0 : (t == AcSweepType::OCT ? 1 : 2); }
+
+// V(out[,ref]) [src] of .NOISE, .DISTO and .PNOISE -- names as written; netlist_capi.cpp resolves them
+struct OutputPair {
     std::string outNode, refNode;   // refNode empty or "0": ground
-    std::string srcName;            // input source for the gain, empty: none
-    AcSweepType sweepType = AcSweepType::DEC;
-    int nPoints = 0;
-    double fstart = 0.0, fstop = 0.0;
+    std::string srcName;            // input source for the gain, empty: none (.DISTO has none)
 };
+
+// .NOISE V(out[,ref]) [src] {DEC|OCT|LIN} n fstart fstop
+struct NoiseConfig : AcConfig, OutputPair {};
 
 // .SP {DEC|OCT|LIN} n fstart fstop [0|1]
-struct SpConfig {
-    bool enabled = false;
+struct SpConfig : AcConfig {
     bool doNoise = false;           // the trailing 1 (ngspice's donoise): two-port noise wanted with the sweep
-    AcSweepType sweepType = AcSweepType::DEC;
-    int nPoints = 0;
-    double fstart = 0.0, fstop = 0.0;
 };
 
-// .DISTO V(out[,ref]) {DEC|OCT|LIN} n fstart fstop -- names as written; netlist_capi.cpp resolves them
-struct DistoConfig {
-    bool enabled = false;
-    std::string outNode, refNode;   // refNode empty or "0": ground
-    AcSweepType sweepType = AcSweepType::DEC;
-    int nPoints = 0;
-    double fstart = 0.0, fstop = 0.0;
-};
+// .DISTO V(out[,ref]) {DEC|OCT|LIN} n fstart fstop
+struct DistoConfig : AcConfig, OutputPair {};
 
 // .STB Vprobe {DEC|OCT|LIN} n fstart fstop -- the probe's name as written; netlist_capi.cpp resolves it
-struct StbConfig {
-    bool enabled = false;
+struct StbConfig : AcConfig {
     std::string probeName;          // a V source in series in the loop, + on the driving side
-    AcSweepType sweepType = AcSweepType::DEC;
-    int nPoints = 0;
-    double fstart = 0.0, fstop = 0.0;
 };
 
 struct HbConfig {
@@ -190,24 +179,12 @@ struct HbConfig {
 };
 
 // .PAC {DEC|OCT|LIN} n fstart fstop [nside]
-struct PacConfig {
-    bool enabled = false;
-    AcSweepType sweepType = AcSweepType::DEC;
-    int nPoints = 0;
-    double fstart = 0.0, fstop = 0.0;
-    int nSide = 1;                  // sidebands -nSide .. nSide around the input frequency
+struct PacConfig : AcConfig {
+    int nSide = 1;                  // sidebands -nSide .. nSide around the input (.PNOISE: the output) frequency
 };
 
-// .PNOISE V(out[,ref]) [src] {DEC|OCT|LIN} n fstart fstop [nside] -- names as written; netlist_capi.cpp resolves them
-struct PnoiseConfig {
-    bool enabled = false;
-    std::string outNode, refNode;   // refNode empty or "0": ground
-    std::string srcName;            // input source for the conversion gain, empty: none
-    AcSweepType sweepType = AcSweepType::DEC;
-    int nPoints = 0;
-    double fstart = 0.0, fstop = 0.0;
-    int nSide = 1;                  // sidebands -nSide .. nSide around the output frequency
-};
+// .PNOISE V(out[,ref]) [src] {DEC|OCT|LIN} n fstart fstop [nside]: the output and source of .NOISE, the grid and nside of .PAC
+struct PnoiseConfig : PacConfig, OutputPair {};
 
 struct ProbeSpec {
     ProbeKind kind = ProbeKind::NodeVoltage;

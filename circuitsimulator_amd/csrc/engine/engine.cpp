@@ -323,6 +323,7 @@ int csim_engine_create(const csim_netlist* nl, int32_t device, csim_engine** out
     eng->cir = nl->cir;
     eng->cir.view();
     eng->netlistProbes = nl->probeEq;
+    eng->cards = nl->cards;
     eng->plan = csim::buildAssemblyPlan(*eng->cir.view());
     eng->big = ir->n_unknowns > 63;
 
@@ -353,12 +354,6 @@ int csim_engine_create(const csim_netlist* nl, int32_t device, csim_engine** out
         }
         rc = upload(eng, re, &eng->dAcRe);
         if (!rc) rc = upload(eng, im, &eng->dAcIm);
-        const AcConfig& a = nl->sim.ac;
-        eng->acEnabled = a.enabled ? 1 : 0;
-        eng->acSweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
-        eng->acPoints = a.nPoints;
-        eng->acFstart = a.fstart;
-        eng->acFstop = a.fstop;
     }
     if (!rc) {
         const std::vector<csim::NoiseSource> src = csim::noiseSources(c);
@@ -368,15 +363,6 @@ int csim_engine_create(const csim_netlist* nl, int32_t device, csim_engine** out
         rc = upload(eng, el, &eng->dNoiseElem);
         if (!rc) rc = upload(eng, ta, &eng->dNoiseA);
         if (!rc) rc = upload(eng, tb, &eng->dNoiseB);
-        const NoiseConfig& nc = nl->sim.noise;
-        eng->noiseEnabled = nc.enabled ? 1 : 0;
-        eng->noiseOutP = nl->noiseOutP;
-        eng->noiseOutM = nl->noiseOutM;
-        eng->noiseSrcElem = nl->noiseSrcElem;
-        eng->noiseSweep = nc.sweepType == AcSweepType::DEC ? 0 : (nc.sweepType == AcSweepType::OCT ? 1 : 2);
-        eng->noisePoints = nc.nPoints;
-        eng->noiseFstart = nc.fstart;
-        eng->noiseFstop = nc.fstop;
     }
     if (!rc) {
         const std::vector<csim::DistoDevice> dev = csim::distoDevices(c);
@@ -387,55 +373,10 @@ int csim_engine_create(const csim_netlist* nl, int32_t device, csim_engine** out
         if (!rc) rc = upload(eng, td, &eng->dDistoD);
         if (!rc) rc = upload(eng, tg, &eng->dDistoG);
         if (!rc) rc = upload(eng, ts, &eng->dDistoS);
-        const DistoConfig& dc = nl->sim.disto;
-        eng->distoEnabled = dc.enabled ? 1 : 0;
-        eng->distoOutP = nl->distoOutP;
-        eng->distoOutM = nl->distoOutM;
-        eng->distoSweep = dc.sweepType == AcSweepType::DEC ? 0 : (dc.sweepType == AcSweepType::OCT ? 1 : 2);
-        eng->distoPoints = dc.nPoints;
-        eng->distoFstart = dc.fstart;
-        eng->distoFstop = dc.fstop;
-    }
-    if (!rc) {
-        const StbConfig& tc = nl->sim.stb;
-        eng->stbEnabled = tc.enabled ? 1 : 0;
-        eng->stbElem = nl->stbElem;
-        eng->stbSweep = tc.sweepType == AcSweepType::DEC ? 0 : (tc.sweepType == AcSweepType::OCT ? 1 : 2);
-        eng->stbPoints = tc.nPoints;
-        eng->stbFstart = tc.fstart;
-        eng->stbFstop = tc.fstop;
-        eng->hbEnabled = nl->sim.hb.enabled ? 1 : 0;
-        eng->hbF0 = nl->sim.hb.f0;
-        eng->hbNHarm = nl->sim.hb.nHarm;
-        eng->tranEnabled = nl->sim.tran.enabled ? 1 : 0;
-        eng->tranTstep = nl->sim.tran.tstep;
-        const PacConfig& pc = nl->sim.pac;
-        eng->pacEnabled = pc.enabled ? 1 : 0;
-        eng->pacSweep = pc.sweepType == AcSweepType::DEC ? 0 : (pc.sweepType == AcSweepType::OCT ? 1 : 2);
-        eng->pacPoints = pc.nPoints;
-        eng->pacFstart = pc.fstart;
-        eng->pacFstop = pc.fstop;
-        eng->pacNSide = pc.nSide;
-        const PnoiseConfig& pn = nl->sim.pnoise;
-        eng->pnoiseEnabled = pn.enabled ? 1 : 0;
-        eng->pnoiseOutP = nl->pnoiseOutP;
-        eng->pnoiseOutM = nl->pnoiseOutM;
-        eng->pnoiseSrcElem = nl->pnoiseSrcElem;
-        eng->pnoiseSweep = pn.sweepType == AcSweepType::DEC ? 0 : (pn.sweepType == AcSweepType::OCT ? 1 : 2);
-        eng->pnoisePoints = pn.nPoints;
-        eng->pnoiseFstart = pn.fstart;
-        eng->pnoiseFstop = pn.fstop;
-        eng->pnoiseNSide = pn.nSide;
     }
     if (!rc) {
         for (const csim::Port& p : nl->ports) { eng->spPortEq.push_back(p.branchEq); eng->spZ0.push_back(p.z0); }
         eng->spPortError = nl->portError;
-        const SpConfig& sc = nl->sim.sp;
-        eng->spEnabled = sc.enabled ? 1 : 0;
-        eng->spSweep = sc.sweepType == AcSweepType::DEC ? 0 : (sc.sweepType == AcSweepType::OCT ? 1 : 2);
-        eng->spPoints = sc.nPoints;
-        eng->spFstart = sc.fstart;
-        eng->spFstop = sc.fstop;
     }
     if (!rc) rc = fillGenPlan(eng, eng->plan.dc, eng->gpDc);
     if (!rc) rc = fillGenPlan(eng, eng->plan.tran, eng->gpTran);

@@ -85,17 +85,17 @@ int noiseTemperature(double temp_k, const char* who, double* kT4)
 }
 
 // no frequency list given: the sweep of the netlist's card
-int cardFreqs(int enabled, int sweep, int points, double fstart, double fstop, const char* who, const char* cardName,
-              std::vector<double>& card, const double** freqs, int32_t* F)
+int cardFreqs(const csim::SweepGrid& g, const char* who, const char* cardName, std::vector<double>& card,
+              const double** freqs, int32_t* F)
 {
-    if (!enabled) {
+    if (!g.enabled) {
         setError(std::string(who) + ": no frequencies given and the netlist has no " + cardName + " card");
         return CSIM_ERR_CONFIG;
     }
-    const int64_t n = csim_ac_num_freqs(sweep, points, fstart, fstop);
+    const int64_t n = csim_ac_num_freqs(g.sweep, g.points, g.fstart, g.fstop);
     if (n < 0) return static_cast<int>(n);
     card.resize((size_t)n);
-    if (const int rc = csim_ac_freqs(sweep, points, fstart, fstop, card.data())) return rc;
+    if (const int rc = csim_ac_freqs(g.sweep, g.points, g.fstart, g.fstop, card.data())) return rc;
     *freqs = card.data();
     *F = static_cast<int32_t>(n);
     return CSIM_OK;
@@ -386,8 +386,8 @@ int stbSetup(const csim_engine* eng, int probe_elem, csim::StbArgs& a)
     if (const int rc = acBlockRefused(eng, "loop-gain analysis")) return rc;
     if (N > 63) { setError("loop-gain analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
     if (probe_elem == -1) {
-        if (!eng->stbEnabled) { setError("loop-gain analysis: no probe given and the netlist has no .STB card"); return CSIM_ERR_CONFIG; }
-        probe_elem = eng->stbElem;
+        if (!eng->cards.stb.enabled) { setError("loop-gain analysis: no probe given and the netlist has no .STB card"); return CSIM_ERR_CONFIG; }
+        probe_elem = eng->cards.stbElem;
     }
     const csim::CircuitIR& c = eng->cir;
     if (probe_elem < 0 || probe_elem >= c.ir.n_elems) { setError("loop-gain analysis: the probe is not an element of the netlist"); return CSIM_ERR_CONFIG; }
@@ -576,8 +576,7 @@ int csim_ac_batch(csim_engine* eng, const double* params, int32_t B, const doubl
     if (const int rc = acCheck(eng)) return rc;
     std::vector<double> card;
     if (!freqs)
-        if (const int rc = cardFreqs(eng->acEnabled, eng->acSweep, eng->acPoints, eng->acFstart, eng->acFstop, "csim_ac_batch",
-                                     ".AC", card, &freqs, &F)) return rc;
+        if (const int rc = cardFreqs(eng->cards.ac, "csim_ac_batch", ".AC", card, &freqs, &F)) return rc;
     if (F < 0 || (B > 0 && F > 0 && !out)) { setError("csim_ac_batch: bad argument"); return CSIM_ERR_ARG; }
     if (B == 0) return CSIM_OK;
     HIPCHK(hipSetDevice(eng->device));
@@ -629,13 +628,12 @@ int csim_noise_batch(csim_engine* eng, const double* params, int32_t B, const do
     if (const int rc = acSizeCheck(eng, "noise analysis")) return rc;
     std::vector<double> card;
     if (!freqs)
-        if (const int rc = cardFreqs(eng->noiseEnabled, eng->noiseSweep, eng->noisePoints, eng->noiseFstart, eng->noiseFstop,
-                                     "noise analysis", ".NOISE", card, &freqs, &F)) return rc;
+        if (const int rc = cardFreqs(eng->cards.noise, "noise analysis", ".NOISE", card, &freqs, &F)) return rc;
     if (out_p_eq == -2) {
-        if (!eng->noiseEnabled) { setError("csim_noise_batch: no output given and the netlist has no .NOISE card"); return CSIM_ERR_CONFIG; }
-        out_p_eq = eng->noiseOutP;
-        out_m_eq = eng->noiseOutM;
-        src_elem = eng->noiseSrcElem;
+        if (!eng->cards.noise.enabled) { setError("csim_noise_batch: no output given and the netlist has no .NOISE card"); return CSIM_ERR_CONFIG; }
+        out_p_eq = eng->cards.noiseOut.outP;
+        out_m_eq = eng->cards.noiseOut.outM;
+        src_elem = eng->cards.noiseOut.srcElem;
     }
     if (F < 0 || (B > 0 && F > 0 && !onoise)) { setError("csim_noise_batch: bad argument"); return CSIM_ERR_ARG; }
     {
@@ -691,8 +689,7 @@ int csim_sp_batch(csim_engine* eng, const double* params, int32_t B, const doubl
     }
     std::vector<double> card;
     if (!freqs)
-        if (const int rc = cardFreqs(eng->spEnabled, eng->spSweep, eng->spPoints, eng->spFstart, eng->spFstop, "csim_sp_batch",
-                                     ".SP", card, &freqs, &F)) return rc;
+        if (const int rc = cardFreqs(eng->cards.sp, "csim_sp_batch", ".SP", card, &freqs, &F)) return rc;
     if (F < 0 || (B > 0 && F > 0 && !y)) { setError("csim_sp_batch: bad argument"); return CSIM_ERR_ARG; }
     if (B == 0) return CSIM_OK;
     HIPCHK(hipSetDevice(eng->device));
@@ -752,8 +749,7 @@ int csim_spnoise_batch(csim_engine* eng, const double* params, int32_t B, const 
     }
     std::vector<double> card;
     if (!freqs)
-        if (const int rc = cardFreqs(eng->spEnabled, eng->spSweep, eng->spPoints, eng->spFstart, eng->spFstop,
-                                     "csim_spnoise_batch", ".SP", card, &freqs, &F)) return rc;
+        if (const int rc = cardFreqs(eng->cards.sp, "csim_spnoise_batch", ".SP", card, &freqs, &F)) return rc;
     if (F < 0 || (B > 0 && F > 0 && !cy)) { setError("csim_spnoise_batch: bad argument"); return CSIM_ERR_ARG; }
     if (B == 0) return CSIM_OK;
     HIPCHK(hipSetDevice(eng->device));
@@ -812,12 +808,11 @@ int csim_disto_batch(csim_engine* eng, const double* params, int32_t B, const do
     if (!eng || B < 0) { setError("csim_disto_batch: bad argument"); return CSIM_ERR_ARG; }
     std::vector<double> card;
     if (!freqs)
-        if (const int rc = cardFreqs(eng->distoEnabled, eng->distoSweep, eng->distoPoints, eng->distoFstart, eng->distoFstop,
-                                     "distortion analysis", ".DISTO", card, &freqs, &F)) return rc;
+        if (const int rc = cardFreqs(eng->cards.disto, "distortion analysis", ".DISTO", card, &freqs, &F)) return rc;
     if (out_p_eq == -2) {
-        if (!eng->distoEnabled) { setError("csim_disto_batch: no output given and the netlist has no .DISTO card"); return CSIM_ERR_CONFIG; }
-        out_p_eq = eng->distoOutP;
-        out_m_eq = eng->distoOutM;
+        if (!eng->cards.disto.enabled) { setError("csim_disto_batch: no output given and the netlist has no .DISTO card"); return CSIM_ERR_CONFIG; }
+        out_p_eq = eng->cards.distoOut.outP;
+        out_m_eq = eng->cards.distoOut.outM;
     }
     if (F < 0 || (B > 0 && F > 0 && !hd)) { setError("csim_disto_batch: bad argument"); return CSIM_ERR_ARG; }
     {
@@ -888,8 +883,7 @@ int csim_stb_batch(csim_engine* eng, const double* params, int32_t B, const doub
     if (!eng || B < 0 || (found && !margins)) { setError("csim_stb_batch: bad argument"); return CSIM_ERR_ARG; }
     std::vector<double> card;
     if (!freqs)
-        if (const int rc = cardFreqs(eng->stbEnabled, eng->stbSweep, eng->stbPoints, eng->stbFstart, eng->stbFstop,
-                                     "loop-gain analysis", ".STB", card, &freqs, &F)) return rc;
+        if (const int rc = cardFreqs(eng->cards.stb, "loop-gain analysis", ".STB", card, &freqs, &F)) return rc;
     if (F < 0 || (B > 0 && F > 0 && !t)) { setError("csim_stb_batch: bad argument"); return CSIM_ERR_ARG; }
     if (margins && B > 0 && !stbFreqsIncrease(freqs, F)) {
         setError("csim_stb_batch: margins need strictly increasing positive frequencies");

@@ -51,11 +51,10 @@ int pssChunk(const csim_engine* eng, int B);
 // the messages.
 int periodResolveSteps(const csim_engine* eng, const std::string& who, bool cardDefaults, double& tstep, double f0, int64_t& K);
 
-// the sweep of a .PAC or .PNOISE card (`card` names it in the message)
-struct PeriodSweepCard { const char* card; int enabled, sweep, points; double fstart, fstop; };
-// the frequencies of a call: the caller's F, or with F == 0 the card's; every one finite and positive
-int periodResolveFreqs(const std::string& who, bool cardDefaults, const PeriodSweepCard& card, const double* freqs, int F,
-                       std::vector<double>& out);
+// the frequencies of a call: the caller's F, or with F == 0 those of the .PAC or .PNOISE card (`card`, named
+// `cardName` in the message); every one finite and positive
+int periodResolveFreqs(const std::string& who, bool cardDefaults, const SweepGrid& card, const char* cardName,
+                       const double* freqs, int F, std::vector<double>& out);
 
 // The W_K launch of the analyses that follow a steady state: the periodic steady state's period kernel on a status word
 // of its own, no harmonics, no update.  Holds on the device its scratch, the twiddle table (args.twc, args.tws) and

@@ -7,6 +7,7 @@
 
 #include "../api/circuit.hpp"
 #include "device_common.hpp"
+#include "netlist_internal.hpp"
 #include "plan.hpp"
 
 // Run-time options of one engine.  The environment is read ONCE, in csim_engine_create (defaults of
@@ -114,10 +115,12 @@ struct csim_engine {
     // Gauss-Seidel DC: off-diagonal structure of the DC system per row (uploaded on first use)
     const int32_t *dGsRowPtr = nullptr, *dGsRowCol = nullptr;
 
-    // AC analysis: the netlist's .AC card, the excitation per element (re, im; element order), and the sweep's
-    // device tables (uploaded when they change, cached by content) and per-chunk system scratch
-    int acEnabled = 0, acSweep = 0, acPoints = 0;
-    double acFstart = 0.0, acFstop = 0.0;
+    // the netlist's analysis cards, resolved: a copy (an engine may outlive its netlist handle); the defaults of the
+    // host-pointer entries
+    csim::Cards cards;
+
+    // AC analysis: the excitation per element (re, im; element order), and the sweep's device tables (uploaded when
+    // they change, cached by content) and per-chunk system scratch
     bool acAnySource = false;
     const double *dAcRe = nullptr, *dAcIm = nullptr;
     // A sweep that is still enqueued reads the list it was launched with, so a changed list never overwrites the
@@ -134,44 +137,22 @@ struct csim_engine {
     double* dAcWork = nullptr;             // ac_kernel=block: the planes of every chunk instance
     int acWorkCap = 0;                     // instances
 
-    // Noise analysis: the netlist's .NOISE card (resolved), the generator list (element, terminals; uploaded once) and
-    // the PSD scratch of one chunk, used when the caller does not ask for the PSDs
-    int noiseEnabled = 0, noiseOutP = -2, noiseOutM = -1, noiseSrcElem = -1, noiseSweep = 0, noisePoints = 0;
-    double noiseFstart = 0.0, noiseFstop = 0.0;
+    // Noise analysis: the generator list (element, terminals; uploaded once) and the PSD scratch of one chunk, used
+    // when the caller does not ask for the PSDs
     int nNoiseSrc = 0;
     const int32_t *dNoiseElem = nullptr, *dNoiseA = nullptr, *dNoiseB = nullptr;
     double* dNoisePsd = nullptr;
     size_t noisePsdCap = 0;                // doubles
 
-    // Distortion analysis: the netlist's .DISTO card (resolved), the MOSFET list (element, drain, gate, source
-    // equations; uploaded once) and the coefficient scratch of one chunk, used when the caller does not ask for them
-    int distoEnabled = 0, distoOutP = -2, distoOutM = -1, distoSweep = 0, distoPoints = 0;
-    double distoFstart = 0.0, distoFstop = 0.0;
+    // Distortion analysis: the MOSFET list (element, drain, gate, source equations; uploaded once) and the coefficient
+    // scratch of one chunk, used when the caller does not ask for them
     int nDistoDev = 0;
     const int32_t *dDistoElem = nullptr, *dDistoD = nullptr, *dDistoG = nullptr, *dDistoS = nullptr;
     double* dDistoCoef = nullptr;
     size_t distoCoefCap = 0;               // doubles
 
-    // Loop-gain analysis: the netlist's .STB card; stbElem is its probe element (-2: a name the netlist does not have)
-    int stbEnabled = 0, stbElem = -2, stbSweep = 0, stbPoints = 0;
-    double stbFstart = 0.0, stbFstop = 0.0;
-
-    // Periodic steady state: the netlist's .HB card and the step of its .TRAN card (the defaults of csim_pss_batch)
-    int hbEnabled = 0, hbNHarm = 0, tranEnabled = 0;
-    double hbF0 = 0.0, tranTstep = 0.0;
-
-    // Periodic AC analysis: the netlist's .PAC card (the defaults of csim_pac_batch)
-    int pacEnabled = 0, pacSweep = 0, pacPoints = 0, pacNSide = 1;
-    double pacFstart = 0.0, pacFstop = 0.0;
-
-    // Periodic noise analysis: the netlist's .PNOISE card, resolved (the defaults of csim_pnoise_batch)
-    int pnoiseEnabled = 0, pnoiseOutP = -2, pnoiseOutM = -1, pnoiseSrcElem = -1, pnoiseSweep = 0, pnoisePoints = 0, pnoiseNSide = 1;
-    double pnoiseFstart = 0.0, pnoiseFstop = 0.0;
-
-    // S-parameter analysis: the netlist's .SP card and its ports in port order (branch equation, Z0); spPortError
-    // says what is wrong with the PORTNUM numbering, if anything
-    int spEnabled = 0, spSweep = 0, spPoints = 0;
-    double spFstart = 0.0, spFstop = 0.0;
+    // S-parameter analysis: the netlist's ports in port order (branch equation, Z0); spPortError says what is wrong
+    // with the PORTNUM numbering, if anything
     std::vector<int32_t> spPortEq;
     std::vector<double> spZ0;
     std::string spPortError;

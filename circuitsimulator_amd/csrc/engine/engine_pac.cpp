@@ -36,11 +36,10 @@ int pacResolve(const csim_engine* eng, const char* who, bool cardDefaults, doubl
     }
     if ((probe_eq && n_probe < 0) || F < 0 || (F > 0 && !freqs)) { setError(w + ": bad argument"); return CSIM_ERR_ARG; }
     if (n_side < 0) { setError(w + ": n_side must be >= 0"); return CSIM_ERR_ARG; }
-    const csim::PeriodSweepCard card{".PAC", eng->pacEnabled, eng->pacSweep, eng->pacPoints, eng->pacFstart, eng->pacFstop};
-    if (const int rc = csim::periodResolveFreqs(w, cardDefaults, card, freqs, F, p.freqs)) return rc;
+    if (const int rc = csim::periodResolveFreqs(w, cardDefaults, eng->cards.pac, ".PAC", freqs, F, p.freqs)) return rc;
     if (cardDefaults && !(f0 > 0.0)) {
-        if (!eng->hbEnabled) { setError(w + ": no f0 given and the netlist has no .HB card"); return CSIM_ERR_CONFIG; }
-        f0 = eng->hbF0;
+        if (!eng->cards.hb.enabled) { setError(w + ": no f0 given and the netlist has no .HB card"); return CSIM_ERR_CONFIG; }
+        f0 = eng->cards.hb.f0;
     }
     int64_t K = 0;
     if (const int rc = csim::periodResolveSteps(eng, w, cardDefaults, tstep, f0, K)) return rc;

@@ -37,18 +37,16 @@ int pnoiseResolve(const csim_engine* eng, const char* who, bool cardDefaults, do
     }
     if (F < 0 || (F > 0 && !freqs)) { setError(w + ": bad argument"); return CSIM_ERR_ARG; }
     if (n_side < 0) { setError(w + ": n_side must be >= 0"); return CSIM_ERR_ARG; }
-    const csim::PeriodSweepCard card{".PNOISE", eng->pnoiseEnabled, eng->pnoiseSweep, eng->pnoisePoints, eng->pnoiseFstart,
-                                     eng->pnoiseFstop};
-    if (const int rc = csim::periodResolveFreqs(w, cardDefaults, card, freqs, F, p.freqs)) return rc;
+    if (const int rc = csim::periodResolveFreqs(w, cardDefaults, eng->cards.pnoise, ".PNOISE", freqs, F, p.freqs)) return rc;
     if (cardDefaults && out_p == -2) {
-        if (!eng->pnoiseEnabled) { setError(w + ": no output given and the netlist has no .PNOISE card"); return CSIM_ERR_CONFIG; }
-        out_p = eng->pnoiseOutP;
-        out_m = eng->pnoiseOutM;
-        src_elem = eng->pnoiseSrcElem;
+        if (!eng->cards.pnoise.enabled) { setError(w + ": no output given and the netlist has no .PNOISE card"); return CSIM_ERR_CONFIG; }
+        out_p = eng->cards.pnoiseOut.outP;
+        out_m = eng->cards.pnoiseOut.outM;
+        src_elem = eng->cards.pnoiseOut.srcElem;
     }
     if (cardDefaults && !(f0 > 0.0)) {
-        if (!eng->hbEnabled) { setError(w + ": no f0 given and the netlist has no .HB card"); return CSIM_ERR_CONFIG; }
-        f0 = eng->hbF0;
+        if (!eng->cards.hb.enabled) { setError(w + ": no f0 given and the netlist has no .HB card"); return CSIM_ERR_CONFIG; }
+        f0 = eng->cards.hb.f0;
     }
     int64_t K = 0;
     if (const int rc = csim::periodResolveSteps(eng, w, cardDefaults, tstep, f0, K)) return rc;

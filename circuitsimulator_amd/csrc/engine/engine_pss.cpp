@@ -39,9 +39,9 @@ int pssResolve(const csim_engine* eng, const char* who, bool cardDefaults, doubl
     const bool fromCard = cardDefaults && !(f0 > 0.0);      // then n_harm is the card's too
     if (!fromCard && n_harm < 0) { setError(w + ": n_harm must be >= 0"); return CSIM_ERR_ARG; }
     if (fromCard) {
-        if (!eng->hbEnabled) { setError(w + ": no f0 given and the netlist has no .HB card"); return CSIM_ERR_CONFIG; }
-        f0 = eng->hbF0;
-        n_harm = eng->hbNHarm;
+        if (!eng->cards.hb.enabled) { setError(w + ": no f0 given and the netlist has no .HB card"); return CSIM_ERR_CONFIG; }
+        f0 = eng->cards.hb.f0;
+        n_harm = eng->cards.hb.nHarm;
         if (n_harm < 0) { setError(w + ": the .HB card's harmonic count is negative"); return CSIM_ERR_CONFIG; }
     }
     int64_t K = 0;
@@ -76,8 +76,8 @@ int csim::pssChunk(const csim_engine* eng, int B)
 int csim::periodResolveSteps(const csim_engine* eng, const std::string& w, bool cardDefaults, double& tstep, double f0, int64_t& K)
 {
     if (cardDefaults && !(tstep > 0.0)) {
-        if (!eng->tranEnabled) { setError(w + ": no tstep given and the netlist has no .TRAN card"); return CSIM_ERR_CONFIG; }
-        tstep = eng->tranTstep;
+        if (!eng->cards.tran.enabled) { setError(w + ": no tstep given and the netlist has no .TRAN card"); return CSIM_ERR_CONFIG; }
+        tstep = eng->cards.tran.tstep;
     }
     if (!(f0 > 0.0)) { setError(w + ": no f0 given"); return CSIM_ERR_CONFIG; }
     K = csim::pss_num_steps(tstep, f0);
@@ -88,12 +88,12 @@ int csim::periodResolveSteps(const csim_engine* eng, const std::string& w, bool 
     return CSIM_OK;
 }
 
-int csim::periodResolveFreqs(const std::string& w, bool cardDefaults, const PeriodSweepCard& card, const double* freqs, int F,
-                             std::vector<double>& out)
+int csim::periodResolveFreqs(const std::string& w, bool cardDefaults, const SweepGrid& card, const char* cardName,
+                             const double* freqs, int F, std::vector<double>& out)
 {
     if (F == 0) {
         if (!cardDefaults || freqs || !card.enabled) {
-            setError(w + ": no frequencies given and no " + card.card + " card to take them from");
+            setError(w + ": no frequencies given and no " + cardName + " card to take them from");
             return CSIM_ERR_ARG;
         }
         const int64_t n = csim_ac_num_freqs(card.sweep, card.points, card.fstart, card.fstop);

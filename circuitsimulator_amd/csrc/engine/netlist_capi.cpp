@@ -21,6 +21,60 @@ void setError(const std::string& msg) { g_lastError = msg; }
 
 namespace {
 
+csim::SweepGrid gridOf(const AcConfig& a)
+{
+    return {a.enabled ? 1 : 0, acSweepCode(a.sweepType), a.nPoints, a.fstart, a.fstop};
+}
+
+// V(out[,ref]) [src] of an enabled card; no source is -1
+csim::OutputEqs outputOf(const Circuit& ckt, bool enabled, const OutputPair& o)
+{
+    if (!enabled) return {};
+    return {csim::cardNodeEquation(ckt, o.outNode), csim::cardNodeEquation(ckt, o.refNode),
+            o.srcName.empty() ? -1 : csim::elementIndex(ckt, o.srcName, -1)};
+}
+
+// the cards of the front-end -> what the getters report and an engine keeps
+csim::Cards resolveCards(const Circuit& ckt, const SimulationConfig& sim)
+{
+    csim::Cards c;
+    c.ac = gridOf(sim.ac);
+    c.noise = gridOf(sim.noise);
+    c.sp = gridOf(sim.sp);
+    c.disto = gridOf(sim.disto);
+    c.stb = gridOf(sim.stb);
+    c.pac = {gridOf(sim.pac), sim.pac.nSide};
+    c.pnoise = {gridOf(sim.pnoise), sim.pnoise.nSide};
+    c.noiseOut = outputOf(ckt, sim.noise.enabled, sim.noise);
+    c.distoOut = outputOf(ckt, sim.disto.enabled, sim.disto);
+    c.pnoiseOut = outputOf(ckt, sim.pnoise.enabled, sim.pnoise);
+    if (sim.stb.enabled) c.stbElem = csim::elementIndex(ckt, sim.stb.probeName, -2);
+    c.spNoise = sim.sp.enabled && sim.sp.doNoise;
+    c.hb.enabled = sim.hb.enabled ? 1 : 0;
+    c.hb.f0 = sim.hb.f0;
+    c.hb.nHarm = sim.hb.nHarm;
+    c.tran.enabled = sim.tran.enabled ? 1 : 0;
+    c.tran.tstep = sim.tran.tstep;
+    return c;
+}
+
+// what every card getter reports of a grid
+void putGrid(const csim::SweepGrid& g, int32_t* enabled, int32_t* sweep, int32_t* n_points, double* fstart, double* fstop)
+{
+    if (enabled)  *enabled = g.enabled;
+    if (sweep)    *sweep = g.sweep;
+    if (n_points) *n_points = g.points;
+    if (fstart)   *fstart = g.fstart;
+    if (fstop)    *fstop = g.fstop;
+}
+
+void putOutput(const csim::OutputEqs& o, int32_t* out_p_eq, int32_t* out_m_eq, int32_t* src_elem)
+{
+    if (out_p_eq) *out_p_eq = o.outP;
+    if (out_m_eq) *out_m_eq = o.outM;
+    if (src_elem) *src_elem = o.srcElem;
+}
+
 int finishNetlist(csim_netlist* nl)
 {
     nl->sim.ensureDefaultOp();
@@ -32,9 +86,7 @@ int finishNetlist(csim_netlist* nl)
     for (const PrintCommand& pc : nl->sim.printCommands) {
         for (const ProbeSpec& p : pc.probes) {
             if (p.kind != ProbeKind::NodeVoltage || p.node1.empty()) continue;
-            const auto hit = nl->ckt.nodeNameToId.find(p.node1);
-            if (hit == nl->ckt.nodeNameToId.end()) continue;
-            const int eq = nl->ckt.nodes[static_cast<std::size_t>(hit->second)].eqIndex;
+            const int eq = csim::nodeEquation(nl->ckt, p.node1);
             if (eq < 0) continue;
             bool seen = false;
             for (int q : nl->probeEq) seen = seen || (q == eq);
@@ -42,50 +94,7 @@ int finishNetlist(csim_netlist* nl)
         }
     }
 
-    // .NOISE card: names -> equation / element indices
-    if (nl->sim.noise.enabled) {
-        const NoiseConfig& nc = nl->sim.noise;
-        auto eqOf = [&](const std::string& name) {
-            if (name == "0") return -1;
-            const auto hit = nl->ckt.nodeNameToId.find(name);
-            return hit == nl->ckt.nodeNameToId.end() ? -2 : nl->ckt.nodes[static_cast<std::size_t>(hit->second)].eqIndex;
-        };
-        nl->noiseOutP = eqOf(nc.outNode);
-        nl->noiseOutM = nc.refNode.empty() ? -1 : eqOf(nc.refNode);
-        for (std::size_t e = 0; e < nl->ckt.elements.size() && !nc.srcName.empty(); ++e)
-            if (toLower(nl->ckt.elements[e]->getName()) == toLower(nc.srcName)) { nl->noiseSrcElem = static_cast<int>(e); break; }
-    }
-
-    // .PNOISE card: names -> equation / element indices, as .NOISE
-    if (nl->sim.pnoise.enabled) {
-        const PnoiseConfig& nc = nl->sim.pnoise;
-        auto eqOf = [&](const std::string& name) {
-            if (name == "0") return -1;
-            const auto hit = nl->ckt.nodeNameToId.find(name);
-            return hit == nl->ckt.nodeNameToId.end() ? -2 : nl->ckt.nodes[static_cast<std::size_t>(hit->second)].eqIndex;
-        };
-        nl->pnoiseOutP = eqOf(nc.outNode);
-        nl->pnoiseOutM = nc.refNode.empty() ? -1 : eqOf(nc.refNode);
-        for (std::size_t e = 0; e < nl->ckt.elements.size() && !nc.srcName.empty(); ++e)
-            if (toLower(nl->ckt.elements[e]->getName()) == toLower(nc.srcName)) { nl->pnoiseSrcElem = static_cast<int>(e); break; }
-    }
-
-    // .DISTO card: names -> equation indices
-    if (nl->sim.disto.enabled) {
-        const DistoConfig& dc = nl->sim.disto;
-        auto eqOf = [&](const std::string& name) {
-            if (name == "0") return -1;
-            const auto hit = nl->ckt.nodeNameToId.find(name);
-            return hit == nl->ckt.nodeNameToId.end() ? -2 : nl->ckt.nodes[static_cast<std::size_t>(hit->second)].eqIndex;
-        };
-        nl->distoOutP = eqOf(dc.outNode);
-        nl->distoOutM = dc.refNode.empty() ? -1 : eqOf(dc.refNode);
-    }
-
-    // .STB card: the probe's name -> element index
-    if (nl->sim.stb.enabled)
-        for (std::size_t e = 0; e < nl->ckt.elements.size(); ++e)
-            if (toLower(nl->ckt.elements[e]->getName()) == toLower(nl->sim.stb.probeName)) { nl->stbElem = static_cast<int>(e); break; }
+    nl->cards = resolveCards(nl->ckt, nl->sim);
 
     // PORTNUM tokens: the ports in port order
     nl->portError = csim::portList(nl->cir, nl->ports);
@@ -169,10 +178,7 @@ const char* csim_netlist_eq_name(const csim_netlist* nl, int32_t eq)
 
 int csim_netlist_node_eq(const csim_netlist* nl, const char* node_name)
 {
-    if (!nl || !node_name) return -2;
-    const auto hit = nl->ckt.nodeNameToId.find(node_name);
-    if (hit == nl->ckt.nodeNameToId.end()) return -2;
-    return nl->ckt.nodes[static_cast<std::size_t>(hit->second)].eqIndex;
+    return nl && node_name ? csim::nodeEquation(nl->ckt, node_name) : -2;
 }
 
 int csim_netlist_tran(const csim_netlist* nl, int32_t* enabled, double* tstep, double* tstop, double* tstart)
@@ -189,12 +195,7 @@ int csim_netlist_ac(const csim_netlist* nl, int32_t* enabled, int32_t* sweep, in
                     double* fstop)
 {
     if (!nl) return CSIM_ERR_ARG;
-    const AcConfig& a = nl->sim.ac;
-    if (enabled)  *enabled = a.enabled ? 1 : 0;
-    if (sweep)    *sweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
-    if (n_points) *n_points = a.nPoints;
-    if (fstart)   *fstart = a.fstart;
-    if (fstop)    *fstop = a.fstop;
+    putGrid(nl->cards.ac, enabled, sweep, n_points, fstart, fstop);
     return CSIM_OK;
 }
 
@@ -210,15 +211,8 @@ int csim_netlist_noise(const csim_netlist* nl, int32_t* enabled, int32_t* out_p_
                        int32_t* sweep, int32_t* n_points, double* fstart, double* fstop)
 {
     if (!nl) return CSIM_ERR_ARG;
-    const NoiseConfig& a = nl->sim.noise;
-    if (enabled)  *enabled = a.enabled ? 1 : 0;
-    if (out_p_eq) *out_p_eq = nl->noiseOutP;
-    if (out_m_eq) *out_m_eq = nl->noiseOutM;
-    if (src_elem) *src_elem = nl->noiseSrcElem;
-    if (sweep)    *sweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
-    if (n_points) *n_points = a.nPoints;
-    if (fstart)   *fstart = a.fstart;
-    if (fstop)    *fstop = a.fstop;
+    putGrid(nl->cards.noise, enabled, sweep, n_points, fstart, fstop);
+    putOutput(nl->cards.noiseOut, out_p_eq, out_m_eq, src_elem);
     return CSIM_OK;
 }
 
@@ -239,14 +233,8 @@ int csim_netlist_disto(const csim_netlist* nl, int32_t* enabled, int32_t* out_p_
                        int32_t* n_points, double* fstart, double* fstop)
 {
     if (!nl) return CSIM_ERR_ARG;
-    const DistoConfig& a = nl->sim.disto;
-    if (enabled)  *enabled = a.enabled ? 1 : 0;
-    if (out_p_eq) *out_p_eq = nl->distoOutP;
-    if (out_m_eq) *out_m_eq = nl->distoOutM;
-    if (sweep)    *sweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
-    if (n_points) *n_points = a.nPoints;
-    if (fstart)   *fstart = a.fstart;
-    if (fstop)    *fstop = a.fstop;
+    putGrid(nl->cards.disto, enabled, sweep, n_points, fstart, fstop);
+    putOutput(nl->cards.distoOut, out_p_eq, out_m_eq, nullptr);
     return CSIM_OK;
 }
 
@@ -268,28 +256,22 @@ int csim_netlist_stb(const csim_netlist* nl, int32_t* enabled, int32_t* elem, in
                      int32_t* sweep, int32_t* n_points, double* fstart, double* fstop)
 {
     if (!nl) return CSIM_ERR_ARG;
-    const StbConfig& a = nl->sim.stb;
-    const int e = a.enabled ? nl->stbElem : -2;
+    const int e = nl->cards.stbElem;
     const bool isV = e >= 0 && nl->cir.kind[static_cast<std::size_t>(e)] == CSIM_V;
-    if (enabled)  *enabled = a.enabled ? 1 : 0;
+    putGrid(nl->cards.stb, enabled, sweep, n_points, fstart, fstop);
     if (elem)     *elem = e;
     if (eq_p)     *eq_p = isV ? nl->cir.eq[4 * static_cast<std::size_t>(e) + 0] : -2;
     if (eq_m)     *eq_m = isV ? nl->cir.eq[4 * static_cast<std::size_t>(e) + 1] : -2;
     if (eq_br)    *eq_br = isV ? nl->cir.branchEq[static_cast<std::size_t>(e)] : -2;
-    if (sweep)    *sweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
-    if (n_points) *n_points = a.nPoints;
-    if (fstart)   *fstart = a.fstart;
-    if (fstop)    *fstop = a.fstop;
     return CSIM_OK;
 }
 
 int csim_netlist_hb(const csim_netlist* nl, int32_t* enabled, double* f0, int32_t* n_harm)
 {
     if (!nl) return CSIM_ERR_ARG;
-    const HbConfig& a = nl->sim.hb;
-    if (enabled) *enabled = a.enabled ? 1 : 0;
-    if (f0)      *f0 = a.f0;
-    if (n_harm)  *n_harm = a.nHarm;
+    if (enabled) *enabled = nl->cards.hb.enabled;
+    if (f0)      *f0 = nl->cards.hb.f0;
+    if (n_harm)  *n_harm = nl->cards.hb.nHarm;
     return CSIM_OK;
 }
 
@@ -297,13 +279,9 @@ int csim_netlist_pac(const csim_netlist* nl, int32_t* enabled, int32_t* sweep, i
                      double* fstop, int32_t* n_side)
 {
     if (!nl) return CSIM_ERR_ARG;
-    const PacConfig& a = nl->sim.pac;
-    if (enabled)  *enabled = a.enabled ? 1 : 0;
-    if (sweep)    *sweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
-    if (n_points) *n_points = a.nPoints;
-    if (fstart)   *fstart = a.fstart;
-    if (fstop)    *fstop = a.fstop;
-    if (n_side)   *n_side = a.enabled ? a.nSide : 0;
+    const csim::SidebandGrid& a = nl->cards.pac;
+    putGrid(a, enabled, sweep, n_points, fstart, fstop);
+    if (n_side) *n_side = a.enabled ? a.nSide : 0;
     return CSIM_OK;
 }
 
@@ -311,16 +289,10 @@ int csim_netlist_pnoise(const csim_netlist* nl, int32_t* enabled, int32_t* out_p
                         int32_t* sweep, int32_t* n_points, double* fstart, double* fstop, int32_t* n_side)
 {
     if (!nl) return CSIM_ERR_ARG;
-    const PnoiseConfig& a = nl->sim.pnoise;
-    if (enabled)  *enabled = a.enabled ? 1 : 0;
-    if (out_p_eq) *out_p_eq = nl->pnoiseOutP;
-    if (out_m_eq) *out_m_eq = nl->pnoiseOutM;
-    if (src_elem) *src_elem = nl->pnoiseSrcElem;
-    if (sweep)    *sweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
-    if (n_points) *n_points = a.nPoints;
-    if (fstart)   *fstart = a.fstart;
-    if (fstop)    *fstop = a.fstop;
-    if (n_side)   *n_side = a.enabled ? a.nSide : 0;
+    const csim::SidebandGrid& a = nl->cards.pnoise;
+    putGrid(a, enabled, sweep, n_points, fstart, fstop);
+    putOutput(nl->cards.pnoiseOut, out_p_eq, out_m_eq, src_elem);
+    if (n_side) *n_side = a.enabled ? a.nSide : 0;
     return CSIM_OK;
 }
 
@@ -344,19 +316,14 @@ int csim_netlist_port(const csim_netlist* nl, int32_t i, int32_t* elem, int32_t*
 int csim_netlist_sp(const csim_netlist* nl, int32_t* enabled, int32_t* sweep, int32_t* n_points, double* fstart, double* fstop)
 {
     if (!nl) return CSIM_ERR_ARG;
-    const SpConfig& a = nl->sim.sp;
-    if (enabled)  *enabled = a.enabled ? 1 : 0;
-    if (sweep)    *sweep = a.sweepType == AcSweepType::DEC ? 0 : (a.sweepType == AcSweepType::OCT ? 1 : 2);
-    if (n_points) *n_points = a.nPoints;
-    if (fstart)   *fstart = a.fstart;
-    if (fstop)    *fstop = a.fstop;
+    putGrid(nl->cards.sp, enabled, sweep, n_points, fstart, fstop);
     return CSIM_OK;
 }
 
 int csim_netlist_sp_noise(const csim_netlist* nl, int32_t* donoise)
 {
     if (!nl) return CSIM_ERR_ARG;
-    if (donoise) *donoise = (nl->sim.sp.enabled && nl->sim.sp.doNoise) ? 1 : 0;
+    if (donoise) *donoise = nl->cards.spNoise ? 1 : 0;
     return CSIM_OK;
 }
 
@@ -406,10 +373,7 @@ int csim_netlist_dc_sweep(const csim_netlist* nl, int32_t i, int32_t* src_elem,
 {
     if (!nl || i < 0 || i >= static_cast<int32_t>(nl->sim.dcSweeps.size())) return CSIM_ERR_ARG;
     const DCSweepConfig& dc = nl->sim.dcSweeps[static_cast<std::size_t>(i)];
-    int found = -1;
-    for (std::size_t e = 0; e < nl->ckt.elements.size(); ++e)
-        if (toLower(nl->ckt.elements[e]->getName()) == toLower(dc.sourceName)) { found = static_cast<int>(e); break; }
-    if (src_elem) *src_elem = found;
+    if (src_elem) *src_elem = csim::elementIndex(nl->ckt, dc.sourceName, -1);
     if (start) *start = dc.start;
     if (stop)  *stop = dc.stop;
     if (step)  *step = dc.step;

@@ -11,6 +11,28 @@
 
 namespace csim {
 struct Port { int32_t elem, branchEq; double z0; };     // a V source with PORTNUM k, its branch equation and Z0
+
+// The analysis cards as the engine needs them: names resolved to indices, sweep words to the numbers of csim_ac_freqs.
+// finishNetlist (netlist_capi.cpp) fills one per netlist, the csim_netlist_* getters report it, an engine keeps a copy
+// and takes a call's defaults from it.  Without a card every field keeps its default.
+struct SweepGrid {                                      // {DEC|OCT|LIN} n fstart fstop
+    int enabled = 0, sweep = 0, points = 0;             // sweep: 0 DEC, 1 OCT, 2 LIN
+    double fstart = 0.0, fstop = 0.0;
+};
+struct SidebandGrid : SweepGrid { int nSide = 1; };     // ... [nside]: sidebands -nSide .. nSide
+struct OutputEqs {                                      // V(out[,ref]) [src]
+    int outP = -2, outM = -1;                           // equations: -1 ground, -2 a node the netlist does not have
+    int srcElem = -1;                                   // input source element, -1 none
+};
+struct Cards {
+    SweepGrid ac, noise, sp, disto, stb;
+    SidebandGrid pac, pnoise;
+    OutputEqs noiseOut, distoOut, pnoiseOut;
+    int stbElem = -2;                                   // the .STB probe's element, -2: a name the netlist does not have
+    bool spNoise = false;                               // .SP ... 1
+    struct { int enabled = 0; double f0 = 0.0; int nHarm = 0; } hb;
+    struct { int enabled = 0; double tstep = 0.0; } tran;
+};
 }
 
 struct csim_netlist {
@@ -19,14 +41,7 @@ struct csim_netlist {
     csim::CircuitIR cir;
     std::vector<int> probeEq;      // .PLOTNV / .PRINT node-voltage probes
     std::string csvHeader;
-    // .NOISE card resolved to indices: output equations (-1 ground, -2 unknown node), input source element (-1 none)
-    int noiseOutP = -2, noiseOutM = -1, noiseSrcElem = -1;
-    // .PNOISE card resolved the same way
-    int pnoiseOutP = -2, pnoiseOutM = -1, pnoiseSrcElem = -1;
-    // .DISTO card resolved to indices: output equations (-1 ground, -2 unknown node)
-    int distoOutP = -2, distoOutM = -1;
-    // .STB card resolved: the probe's element index (-2: a name the netlist does not have)
-    int stbElem = -2;
+    csim::Cards cards;             // the analysis cards, resolved
     // the ports (PORTNUM) in port order, or what is wrong with their numbering
     std::vector<csim::Port> ports;
     std::string portError;

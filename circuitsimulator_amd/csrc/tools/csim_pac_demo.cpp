@@ -25,7 +25,7 @@ int main(int argc, char** argv)
         return 1;
     }
     ckt.assignEquationIndices();
-    const int sweep = sim.pac.sweepType == AcSweepType::DEC ? 0 : (sim.pac.sweepType == AcSweepType::OCT ? 1 : 2);
+    const int sweep = acSweepCode(sim.pac.sweepType);
     const int64_t nF = csim_ac_num_freqs(sweep, sim.pac.nPoints, sim.pac.fstart, sim.pac.fstop);
     if (nF <= 0) { std::cerr << "csim_pac_demo: " << csim_last_error() << "\n"; return 1; }
     std::vector<double> freqs((size_t)nF);

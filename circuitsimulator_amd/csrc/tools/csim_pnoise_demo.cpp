@@ -27,16 +27,9 @@ int main(int argc, char** argv)
         return 1;
     }
     ckt.assignEquationIndices();
-    auto eqOf = [&](const std::string& name) {
-        if (name.empty() || name == "0") return -1;
-        const auto hit = ckt.nodeNameToId.find(name);
-        return hit == ckt.nodeNameToId.end() ? -2 : ckt.nodes[static_cast<std::size_t>(hit->second)].eqIndex;
-    };
-    const int outP = eqOf(sim.pnoise.outNode), outM = eqOf(sim.pnoise.refNode);
-    int src = -1;
-    for (std::size_t e = 0; e < ckt.elements.size() && !sim.pnoise.srcName.empty(); ++e)
-        if (toLower(ckt.elements[e]->getName()) == toLower(sim.pnoise.srcName)) { src = static_cast<int>(e); break; }
-    const int sweep = sim.pnoise.sweepType == AcSweepType::DEC ? 0 : (sim.pnoise.sweepType == AcSweepType::OCT ? 1 : 2);
+    const int outP = csim::cardNodeEquation(ckt, sim.pnoise.outNode), outM = csim::cardNodeEquation(ckt, sim.pnoise.refNode);
+    const int src = sim.pnoise.srcName.empty() ? -1 : csim::elementIndex(ckt, sim.pnoise.srcName, -1);
+    const int sweep = acSweepCode(sim.pnoise.sweepType);
     const int64_t nF = csim_ac_num_freqs(sweep, sim.pnoise.nPoints, sim.pnoise.fstart, sim.pnoise.fstop);
     if (nF <= 0) { std::cerr << "csim_pnoise_demo: " << csim_last_error() << "\n"; return 1; }
     std::vector<double> freqs((size_t)nF);

@@ -71,27 +71,96 @@ class Netlist:
         capi.check(L.csim_netlist_nominal_params(self._h, self.nominal_params.ctypes.data))
         self.mc_kinds = np.zeros(self.n_params, dtype=np.int32)
         capi.check(L.csim_netlist_mc_kinds(self._h, self.mc_kinds.ctypes.data))
-        en, sw, npt, f0, f1 = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double(), C.c_double()
-        capi.check(L.csim_netlist_ac(self._h, C.byref(en), C.byref(sw), C.byref(npt), C.byref(f0), C.byref(f1)))
         # the .AC card: None, or (sweep "dec" | "oct" | "lin", n_points, fstart, fstop)
-        self.ac = (AC_SWEEPS[sw.value], npt.value, f0.value, f1.value) if en.value else None
+        self.ac = self._card("ac")
+
+    # -- the sweep cards: one reader, one grid; a card is None when the netlist has none ---------------------------
+    def _card(self, name, lead=0, tail=0):
+        """What csim_netlist_<name> reports: None, or (`lead` resolved indices, sweep "dec" | "oct" | "lin", n_points,
+        fstart, fstop, `tail` further ints) -- the order of the getter's arguments after `enabled`."""
+        ints = [C.c_int32() for _ in range(1 + lead + 2)]
+        grid = [C.c_double(), C.c_double()]
+        more = [C.c_int32() for _ in range(tail)]
+        capi.check(getattr(capi.lib(), "csim_netlist_" + name)(self._h, *[C.byref(x) for x in ints + grid + more]))
+        if not ints[0].value:
+            return None
+        return (tuple(x.value for x in ints[1:1 + lead]) + (AC_SWEEPS[ints[-2].value], ints[-1].value)
+                + tuple(x.value for x in grid + more))
+
+    @staticmethod
+    def _card_freqs(name, card, grid):
+        """Frequency grid of a card (numpy, Hz); `grid` is the slice of its tuple that holds sweep .. fstop."""
+        if card is None:
+            raise capi.CsimError(capi.CSIM_ERR_CONFIG, "the netlist has no .%s card" % name)
+        return ac_freqs(*card[grid])
 
     @property
     def noise(self):
         """The .NOISE card: None, or (out_p_eq, out_m_eq, src_elem, sweep, n_points, fstart, fstop); out_m_eq -1 =
         ground, src_elem -1 = no input source."""
-        v = [C.c_int32() for _ in range(6)]
-        f0, f1 = C.c_double(), C.c_double()
-        capi.check(capi.lib().csim_netlist_noise(self._h, *[C.byref(x) for x in v], C.byref(f0), C.byref(f1)))
-        en, op, om, src, sw, npt = [x.value for x in v]
-        return (op, om, src, AC_SWEEPS[sw], npt, f0.value, f1.value) if en else None
+        return self._card("noise", lead=3)
+
+    @property
+    def disto(self):
+        """The .DISTO card: None, or (out_p_eq, out_m_eq, sweep, n_points, fstart, fstop); out_m_eq -1 = ground."""
+        return self._card("disto", lead=2)
+
+    @property
+    def stb(self):
+        """The .STB card: None, or (probe element, eq_p, eq_m, eq_br, sweep, n_points, fstart, fstop).  The element is -2
+        for a name the netlist does not have; the equations are -2 when the probe is not a V source, -1 = ground."""
+        return self._card("stb", lead=4)
+
+    @property
+    def pac(self):
+        """The .PAC card: None, or (sweep "dec" | "oct" | "lin", n_points, fstart, fstop, n_side)."""
+        return self._card("pac", tail=1)
+
+    @property
+    def pnoise(self):
+        """The .PNOISE card: None, or (out_p_eq, out_m_eq, src_elem, sweep, n_points, fstart, fstop, n_side); out_m_eq
+        -1 = ground, src_elem -1 = no input source."""
+        return self._card("pnoise", lead=3, tail=1)
+
+    @property
+    def sp(self):
+        """The .SP card: None, or (sweep "dec" | "oct" | "lin", n_points, fstart, fstop)."""
+        return self._card("sp")
+
+    def ac_freqs(self):
+        """Frequency grid of the .AC card (numpy, Hz)."""
+        return self._card_freqs("AC", self.ac, slice(0, 4))
 
     def noise_freqs(self):
         """Frequency grid of the .NOISE card (numpy, Hz)."""
-        card = self.noise
-        if card is None:
-            raise capi.CsimError(capi.CSIM_ERR_CONFIG, "the netlist has no .NOISE card")
-        return ac_freqs(*card[3:])
+        return self._card_freqs("NOISE", self.noise, slice(3, 7))
+
+    def sp_freqs(self):
+        """Frequency grid of the .SP card (numpy, Hz)."""
+        return self._card_freqs("SP", self.sp, slice(0, 4))
+
+    def disto_freqs(self):
+        """Frequency grid of the .DISTO card (numpy, Hz)."""
+        return self._card_freqs("DISTO", self.disto, slice(2, 6))
+
+    def stb_freqs(self):
+        """Frequency grid of the .STB card (numpy, Hz)."""
+        return self._card_freqs("STB", self.stb, slice(4, 8))
+
+    def pac_freqs(self):
+        """Frequency grid of the .PAC card (numpy, Hz)."""
+        return self._card_freqs("PAC", self.pac, slice(0, 4))
+
+    def pnoise_freqs(self):
+        """Frequency grid of the .PNOISE card (numpy, Hz)."""
+        return self._card_freqs("PNOISE", self.pnoise, slice(3, 7))
+
+    @property
+    def hb(self):
+        """The .HB card: None, or (f0 in Hz, n_harm)."""
+        en, f0, nh = C.c_int32(), C.c_double(), C.c_int32()
+        capi.check(capi.lib().csim_netlist_hb(self._h, C.byref(en), C.byref(f0), C.byref(nh)))
+        return (f0.value, nh.value) if en.value else None
 
     @property
     def noise_sources(self):
@@ -105,22 +174,6 @@ class Netlist:
         return out
 
     @property
-    def disto(self):
-        """The .DISTO card: None, or (out_p_eq, out_m_eq, sweep, n_points, fstart, fstop); out_m_eq -1 = ground."""
-        v = [C.c_int32() for _ in range(5)]
-        f0, f1 = C.c_double(), C.c_double()
-        capi.check(capi.lib().csim_netlist_disto(self._h, *[C.byref(x) for x in v], C.byref(f0), C.byref(f1)))
-        en, op, om, sw, npt = [x.value for x in v]
-        return (op, om, AC_SWEEPS[sw], npt, f0.value, f1.value) if en else None
-
-    def disto_freqs(self):
-        """Frequency grid of the .DISTO card (numpy, Hz)."""
-        card = self.disto
-        if card is None:
-            raise capi.CsimError(capi.CSIM_ERR_CONFIG, "the netlist has no .DISTO card")
-        return ac_freqs(*card[2:])
-
-    @property
     def disto_devices(self):
         """The non-linear devices (MOSFETs) in element order: [(element index, eq_d, eq_g, eq_s)], -1 = ground."""
         L = capi.lib()
@@ -130,63 +183,6 @@ class Netlist:
             capi.check(L.csim_netlist_disto_device(self._h, i, C.byref(e), C.byref(d), C.byref(g), C.byref(s)))
             out.append((e.value, d.value, g.value, s.value))
         return out
-
-    @property
-    def stb(self):
-        """The .STB card: None, or (probe element, eq_p, eq_m, eq_br, sweep, n_points, fstart, fstop).  The element is -2
-        for a name the netlist does not have; the equations are -2 when the probe is not a V source, -1 = ground."""
-        v = [C.c_int32() for _ in range(7)]
-        f0, f1 = C.c_double(), C.c_double()
-        capi.check(capi.lib().csim_netlist_stb(self._h, *[C.byref(x) for x in v], C.byref(f0), C.byref(f1)))
-        en, el, ep, em, eb, sw, npt = [x.value for x in v]
-        return (el, ep, em, eb, AC_SWEEPS[sw], npt, f0.value, f1.value) if en else None
-
-    @property
-    def hb(self):
-        """The .HB card: None, or (f0 in Hz, n_harm)."""
-        en, f0, nh = C.c_int32(), C.c_double(), C.c_int32()
-        capi.check(capi.lib().csim_netlist_hb(self._h, C.byref(en), C.byref(f0), C.byref(nh)))
-        return (f0.value, nh.value) if en.value else None
-
-    @property
-    def pac(self):
-        """The .PAC card: None, or (sweep "dec" | "oct" | "lin", n_points, fstart, fstop, n_side)."""
-        en, sw, npt, ns = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
-        f0, f1 = C.c_double(), C.c_double()
-        capi.check(capi.lib().csim_netlist_pac(self._h, C.byref(en), C.byref(sw), C.byref(npt), C.byref(f0), C.byref(f1),
-                                               C.byref(ns)))
-        return (AC_SWEEPS[sw.value], npt.value, f0.value, f1.value, ns.value) if en.value else None
-
-    def pac_freqs(self):
-        """Frequency grid of the .PAC card (numpy, Hz)."""
-        card = self.pac
-        if card is None:
-            raise capi.CsimError(capi.CSIM_ERR_CONFIG, "the netlist has no .PAC card")
-        return ac_freqs(*card[:4])
-
-    @property
-    def pnoise(self):
-        """The .PNOISE card: None, or (out_p_eq, out_m_eq, src_elem, sweep, n_points, fstart, fstop, n_side); out_m_eq
-        -1 = ground, src_elem -1 = no input source."""
-        v = [C.c_int32() for _ in range(6)]
-        f0, f1, ns = C.c_double(), C.c_double(), C.c_int32()
-        capi.check(capi.lib().csim_netlist_pnoise(self._h, *[C.byref(x) for x in v], C.byref(f0), C.byref(f1), C.byref(ns)))
-        en, op, om, src, sw, npt = [x.value for x in v]
-        return (op, om, src, AC_SWEEPS[sw], npt, f0.value, f1.value, ns.value) if en else None
-
-    def pnoise_freqs(self):
-        """Frequency grid of the .PNOISE card (numpy, Hz)."""
-        card = self.pnoise
-        if card is None:
-            raise capi.CsimError(capi.CSIM_ERR_CONFIG, "the netlist has no .PNOISE card")
-        return ac_freqs(*card[3:7])
-
-    def stb_freqs(self):
-        """Frequency grid of the .STB card (numpy, Hz)."""
-        card = self.stb
-        if card is None:
-            raise capi.CsimError(capi.CSIM_ERR_CONFIG, "the netlist has no .STB card")
-        return ac_freqs(*card[4:])
 
     @property
     def ports(self):
@@ -204,32 +200,11 @@ class Netlist:
         return out
 
     @property
-    def sp(self):
-        """The .SP card: None, or (sweep "dec" | "oct" | "lin", n_points, fstart, fstop)."""
-        en, sw, npt = C.c_int32(), C.c_int32(), C.c_int32()
-        f0, f1 = C.c_double(), C.c_double()
-        capi.check(capi.lib().csim_netlist_sp(self._h, C.byref(en), C.byref(sw), C.byref(npt), C.byref(f0), C.byref(f1)))
-        return (AC_SWEEPS[sw.value], npt.value, f0.value, f1.value) if en.value else None
-
-    @property
     def sp_noise(self):
         """True when the .SP card carries the trailing 1 (ngspice's donoise): two-port noise wanted with the sweep."""
         v = C.c_int32()
         capi.check(capi.lib().csim_netlist_sp_noise(self._h, C.byref(v)))
         return bool(v.value)
-
-    def sp_freqs(self):
-        """Frequency grid of the .SP card (numpy, Hz)."""
-        card = self.sp
-        if card is None:
-            raise capi.CsimError(capi.CSIM_ERR_CONFIG, "the netlist has no .SP card")
-        return ac_freqs(*card)
-
-    def ac_freqs(self):
-        """Frequency grid of the .AC card (numpy, Hz)."""
-        if self.ac is None:
-            raise capi.CsimError(capi.CSIM_ERR_CONFIG, "the netlist has no .AC card")
-        return ac_freqs(*self.ac)
 
     def ac_source(self, elem):
         """(mag, phase_deg) of element elem's `AC mag [phase]` (0, 0 without one)."""
@@ -471,6 +446,17 @@ class Engine:
                                             f.ctypes.data, len(f), pe, n_probe, out.ctypes.data, st.ctypes.data))
         return out[..., 0] + 1j * out[..., 1], st
 
+    @staticmethod
+    def _out_pair(out, card, card_name):
+        """out: an equation, (out_p, out_m) or None = the card's (its first two entries) -> (out_p, out_m)"""
+        if out is None:
+            if card is None:
+                raise capi.CsimError(capi.CSIM_ERR_CONFIG, "no output given and the netlist has no %s card" % card_name)
+            return card[0], card[1]
+        if isinstance(out, (tuple, list)):
+            return int(out[0]), int(out[1])
+        return int(out), -1
+
     def _noise_args(self, freqs, out, src):
         """-> (freqs, out_p, out_m, src_elem); None takes the .NOISE card's value (src: -1 without a card)"""
         card = self.netlist.noise
@@ -478,14 +464,7 @@ class Engine:
             f = self.netlist.noise_freqs()
         else:
             f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
-        if out is None:
-            if card is None:
-                raise capi.CsimError(capi.CSIM_ERR_CONFIG, "no output given and the netlist has no .NOISE card")
-            out_p, out_m = card[0], card[1]
-        elif isinstance(out, (tuple, list)):
-            out_p, out_m = int(out[0]), int(out[1])
-        else:
-            out_p, out_m = int(out), -1
+        out_p, out_m = self._out_pair(out, card, ".NOISE")
         if src is None:
             src = card[2] if card is not None else -1
         return f, out_p, out_m, int(src)
@@ -540,15 +519,7 @@ class Engine:
             f = self.netlist.disto_freqs()
         else:
             f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
-        if out is None:
-            if card is None:
-                raise capi.CsimError(capi.CSIM_ERR_CONFIG, "no output given and the netlist has no .DISTO card")
-            out_p, out_m = card[0], card[1]
-        elif isinstance(out, (tuple, list)):
-            out_p, out_m = int(out[0]), int(out[1])
-        else:
-            out_p, out_m = int(out), -1
-        return f, out_p, out_m
+        return (f,) + self._out_pair(out, card, ".DISTO")
 
     def disto(self, params, x_op, freqs=None, out=None, want_h=True, coef=False, status=None):
         """Single-tone distortion sweep of the batch around the operating points x_op (device [N][B], from dc());
@@ -763,14 +734,7 @@ class Engine:
         f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
         if n_side is None:
             n_side = card[7] if card is not None else 1
-        if out is None:
-            if card is None:
-                raise capi.CsimError(capi.CSIM_ERR_CONFIG, "no output given and the netlist has no .PNOISE card")
-            out_p, out_m = card[0], card[1]
-        elif isinstance(out, (tuple, list)):
-            out_p, out_m = int(out[0]), int(out[1])
-        else:
-            out_p, out_m = int(out), -1
+        out_p, out_m = self._out_pair(out, card, ".PNOISE")
         if src is None:
             src = card[2] if card is not None else -1
         return f, int(n_side), tstep, f0, out_p, out_m, int(src)
