@@ -68,6 +68,11 @@ PROTOTYPES = {
     "csim_noise_solve_batch": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32,
                                          _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "csim_netlist_disto": (C.c_int, [_vp, _pi32, _pi32, _pi32, _pi32, _pi32, _pdbl, _pdbl]),
+    "csim_netlist_imd": (C.c_int, [_vp, _pi32, _pi32, _pi32, _pi32, _pi32, _pdbl, _pdbl, _pdbl]),
+    "csim_imd_batch_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "csim_imd_batch": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _dbl, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "csim_imd_solve_batch": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp,
+                                       _i32, _i32, _vp, _vp, _vp]),
     "csim_netlist_num_disto_devices": (C.c_int, [_vp]),
     "csim_netlist_disto_device": (C.c_int, [_vp, _i32, _pi32, _pi32, _pi32, _pi32]),
     "csim_disto_batch_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),

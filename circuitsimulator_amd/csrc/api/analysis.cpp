@@ -121,6 +121,26 @@ BatchDistoResult BatchEngine::disto(const std::vector<double>& params, int B, co
     return r;
 }
 
+BatchImdResult BatchEngine::imd(const std::vector<double>& params, int B, const std::vector<double>& freqs, double f2, int outP,
+                                int outM, bool wantPhasors)
+{
+    BatchImdResult r;
+    r.freqs = freqs;
+    r.f2 = f2;
+    r.nDevices = csim_netlist_num_disto_devices(nl_);
+    const std::size_t FB = static_cast<std::size_t>(B) * freqs.size();
+    if (wantPhasors) r.h.assign(FB * 6 * static_cast<std::size_t>(numUnknowns()), std::complex<double>());
+    r.im.assign(FB * 3, 0.0);
+    r.status.assign(static_cast<std::size_t>(B), 0);
+    // an empty list is no sweep, not the card's (a null pointer would ask for the card)
+    static const double none = 0.0;
+    if (csim_imd_batch(eng_, params.empty() ? nullptr : params.data(), B, freqs.empty() ? &none : freqs.data(),
+                       static_cast<int>(freqs.size()), f2, outP, outM, wantPhasors ? reinterpret_cast<double*>(r.h.data()) : nullptr,
+                       r.im.data(), nullptr, r.status.data()) != CSIM_OK)
+        fail("csim_imd_batch");
+    return r;
+}
+
 BatchStbResult BatchEngine::stb(const std::vector<double>& params, int B, const std::vector<double>& freqs, int probeElem,
                                 bool wantMargins)
 {

@@ -74,6 +74,15 @@ struct BatchDistoResult {
     std::vector<uint32_t> status;                 // DC and LU bits (CSIM_ST_LU_TINY_PIVOT: a singular order)
 };
 
+struct BatchImdResult {
+    std::vector<double> freqs;                    // [F] Hz: the first tone
+    double f2 = 0.0;                              // Hz: the second tone
+    int nDevices = 0;                             // M non-linear devices (csim_netlist_disto_device order)
+    std::vector<std::complex<double>> h;          // [B][F][6][N]: the solutions at f1, f2, f1 + f2, f1 - f2, 2 f1, 2 f1 - f2 (empty unless asked for)
+    std::vector<double> im;                       // [B][F][3]: IM2+, IM2-, IM3 at the output
+    std::vector<uint32_t> status;                 // DC and LU bits (CSIM_ST_LU_TINY_PIVOT: a singular solve)
+};
+
 struct BatchStbResult {
     std::vector<double> freqs;                    // [F] Hz
     std::vector<std::complex<double>> t;          // [B][F]: the loop gain
@@ -158,6 +167,11 @@ public:
     // per frequency, at w, 2 w and 3 w.  Output V(outP) - V(outM) (equations; outM = -1: ground).
     BatchDistoResult disto(const std::vector<double>& params, int B, const std::vector<double>& freqs, int outP,
                            int outM = -1, bool wantPhasors = false);
+
+    // Two-tone intermodulation (csim_imd_batch, include/csim.h): DC operating point, then six factorisations per point;
+    // the first tone runs over freqs, the second stays at f2 (Hz).  Output V(outP) - V(outM) (equations; outM = -1: ground).
+    BatchImdResult imd(const std::vector<double>& params, int B, const std::vector<double>& freqs, double f2, int outP,
+                       int outM = -1, bool wantPhasors = false);
 
     // Loop gain at a V source in series in the loop (csim_stb_batch, include/csim.h): DC operating point, then one
     // factorisation with two right-hand sides per frequency.  probeElem -1: the .STB card's probe; margins need

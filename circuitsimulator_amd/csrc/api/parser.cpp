@@ -3,8 +3,8 @@
 //   whose first non-blank is '*' or ';' is a comment; a leading '+' continues
 //   the previous logical line; tokens split on blanks.
 //   Devices by first letter (any case): R C L V I M.   Cards: .MODEL (read in
-//   a first pass, so it may follow its users) .TRAN .OP .DC .AC .NOISE .SP .DISTO .STB .HB .PAC
-//   .PNOISE .PRINT .PLOTNV .PLOTNC; anything else is reported and skipped.
+//   a first pass, so it may follow its users) .TRAN .OP .DC .AC .NOISE .SP .DISTO .IMD .STB .HB
+//   .PAC .PNOISE .PRINT .PLOTNV .PLOTNC; anything else is reported and skipped.
 #include "parser.hpp"
 
 #include <algorithm>
@@ -425,6 +425,7 @@ void NetlistParser::dotCard(const Statement& st)
     else if (head == ".noise")  noiseCard(st);
     else if (head == ".sp")     spCard(st);
     else if (head == ".disto")  distoCard(st);
+    else if (head == ".imd")    imdCard(st);
     else if (head == ".stb")    stbCard(st);
     else if (head == ".print")  printCard(st);
     else if (head == ".model")  modelCard(st);
@@ -605,6 +606,24 @@ void NetlistParser::distoCard(const Statement& st)
     DistoConfig cfg;
     if (t.size() != 6 || !sweepWord(t[2], true, cfg.sweepType)) return invalidSyntax(st, ".DISTO");
     if (outputPair(st, t, 2, ".DISTO", cfg) && sweepGrid(st, t, 3, ".DISTO", cfg)) sim.disto = cfg;
+}
+
+// .IMD V(out[,ref]) {LIN|DEC|OCT} npoints fstart fstop f2overf1   (two tones: f1 sweeps the grid, f2 = f2overf1 * fstart;
+// 0 < f2overf1 < 1; any other token count is an error)
+void NetlistParser::imdCard(const Statement& st)
+{
+    const std::vector<std::string> t = joinOutput(st.tokens);
+    ImdConfig cfg;
+    if (t.size() != 7 || !sweepWord(t[2], true, cfg.sweepType)) return invalidSyntax(st, ".IMD");
+    if (!outputPair(st, t, 2, ".IMD", cfg) || !sweepGrid(st, t, 3, ".IMD", cfg)) return;
+    try {
+        cfg.f2overf1 = parseSpiceNumber(t[6]);
+        if (!(cfg.f2overf1 > 0.0 && cfg.f2overf1 < 1.0)) throw std::invalid_argument("f2overf1 must lie between 0 and 1");
+    } catch (const std::exception& e) {
+        cannotParse(st, ".IMD", e.what());
+        return;
+    }
+    sim.imd = cfg;
 }
 
 // .STB Vprobe {LIN|DEC|OCT} npoints fstart fstop   (any other token count is an error)

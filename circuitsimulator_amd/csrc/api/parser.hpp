@@ -51,6 +51,7 @@ private:
     void acCard(const Statement& st);
     void noiseCard(const Statement& st);
     void distoCard(const Statement& st);
+    void imdCard(const Statement& st);
     void stbCard(const Statement& st);
     void spCard(const Statement& st);
     void hbCard(const Statement& st);

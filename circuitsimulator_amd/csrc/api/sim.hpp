@@ -150,10 +150,10 @@ struct AcConfig {
 // (csim_ac_freqs: 0 DEC, 1 OCT, 2 LIN):
 inline int acSweepCode(AcSweepType t) { return t == AcSweepType::DEC ? 0 : (t == AcSweepType::OCT ? 1 : 2); }
 
-// V(out[,ref]) [src] of .NOISE, .DISTO and .PNOISE -- names as written; netlist_capi.cpp resolves them
+// V(out[,ref]) [src] of .NOISE, .DISTO, .IMD and .PNOISE -- names as written; netlist_capi.cpp resolves them
 struct OutputPair {
     std::string outNode, refNode;   // refNode empty or "0": ground
-    std::string srcName;            // input source for the gain, empty: none (.DISTO has none)
+    std::string srcName;            // input source for the gain, empty: none (.DISTO and .IMD have none)
 };
 
 // .NOISE V(out[,ref]) [src] {DEC|OCT|LIN} n fstart fstop
@@ -166,6 +166,11 @@ struct SpConfig : AcConfig {
 
 // .DISTO V(out[,ref]) {DEC|OCT|LIN} n fstart fstop
 struct DistoConfig : AcConfig, OutputPair {};
+
+// .IMD V(out[,ref]) {DEC|OCT|LIN} n fstart fstop f2overf1: the grid is the first tone's, the second stays at f2overf1 * fstart
+struct ImdConfig : DistoConfig {
+    double f2overf1 = 0.0;          // 0 < f2overf1 < 1
+};
 
 // .STB Vprobe {DEC|OCT|LIN} n fstart fstop -- the probe's name as written; netlist_capi.cpp resolves it
 struct StbConfig : AcConfig {
@@ -207,6 +212,7 @@ public:
     NoiseConfig noise;
     SpConfig sp;
     DistoConfig disto;
+    ImdConfig imd;
     StbConfig stb;
     HbConfig hb;
     PacConfig pac;

@@ -1,9 +1,10 @@
-// ac_sweep.hpp -- what the sweep kernels of the AC, noise, S-parameter, two-port noise, distortion and loop-gain analyses
-// (kernels_ac.hip, kernels_noise.hip, kernels_sp.hip, kernels_spnoise.hip, kernels_disto.hip, kernels_stb.hip) share: the
+// ac_sweep.hpp -- what the sweep kernels of the AC, noise, S-parameter, two-port noise, distortion, intermodulation and
+// loop-gain analyses (kernels_ac.hip, kernels_noise.hip, kernels_sp.hip, kernels_spnoise.hip, kernels_disto.hip,
+// kernels_imd.hip, kernels_stb.hip) share: the
 // factorisation and back substitution with K right-hand sides -- ac_lu.hpp's primitives applied in the order of
 // ac_lu_solve_multi(), by one wavefront on a system in LDS, or by 32 lanes on a system in registers -- and the
-// scaffolding around it (LDS carve-up, the G + jwC load, instance indexing, launch dispatch).  AC, noise and distortion
-// are K = 1, loop gain is K = 2.  Included by those six files only.
+// scaffolding around it (LDS carve-up, the G + jwC load, instance indexing, launch dispatch).  AC, noise, distortion
+// and intermodulation are K = 1, loop gain is K = 2.  Included by those seven files only.
 // A third shape, one 256-thread workgroup per system for N <= 1024 (AC and noise only), is ac_block.hpp.
 #pragma once
 

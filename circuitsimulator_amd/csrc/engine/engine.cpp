@@ -373,6 +373,9 @@ int csim_engine_create(const csim_netlist* nl, int32_t device, csim_engine** out
         if (!rc) rc = upload(eng, td, &eng->dDistoD);
         if (!rc) rc = upload(eng, tg, &eng->dDistoG);
         if (!rc) rc = upload(eng, ts, &eng->dDistoS);
+        eng->distoD = td;
+        eng->distoG = tg;
+        eng->distoS = ts;
     }
     if (!rc) {
         for (const csim::Port& p : nl->ports) { eng->spPortEq.push_back(p.branchEq); eng->spZ0.push_back(p.z0); }

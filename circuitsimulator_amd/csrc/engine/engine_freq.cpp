@@ -1,6 +1,6 @@
-// engine_freq.cpp -- C-ABI of the frequency-domain analyses: AC, noise, S-parameters, two-port noise, distortion and loop
-// gain, each as csim_*_batch_dev (device pointers, enqueue only), csim_*_batch (host pointers, DC operating point
-// included) and csim_*_solve_batch (any system, no engine).  What the six share is written once: kernel choice, the chunk
+// engine_freq.cpp -- C-ABI of the frequency-domain analyses: AC, noise, S-parameters, two-port noise, distortion,
+// intermodulation and loop gain, each as csim_*_batch_dev (device pointers, enqueue only), csim_*_batch (host pointers, DC operating point
+// included) and csim_*_solve_batch (any system, no engine).  What they share is written once: kernel choice, the chunk
 // driver, scratch growth, the card's frequencies, the operating point and the output list of the host-pointer forms.
 // A new analysis supplies its setup function, its ...Args and its sweep launch.
 #include <hip/hip_runtime.h>
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "ac_disto.hpp"
+#include "ac_imd.hpp"
 #include "ac_noise.hpp"
 #include "ac_port.hpp"
 #include "ac_stb.hpp"
@@ -359,17 +360,20 @@ int spNoiseSetup(const csim_engine* eng, double temp_k, bool wantParams, csim::S
     return CSIM_OK;
 }
 
-// output pair of a distortion call -> the kernels' numbers (include/csim.h "Distortion analysis")
-int distoSetup(const csim_engine* eng, int out_p, int out_m, csim::DistoArgs& a)
+// output pair of a distortion or intermodulation call -> the kernels' numbers (include/csim.h "Distortion analysis",
+// "Intermodulation analysis"); `what` names the analysis in a refusal
+template <class Args>
+int distoSetup(const csim_engine* eng, const char* what, int out_p, int out_m, Args& a)
 {
     const int N = eng->plan.N;
-    if (acBlock(eng)) { setError("distortion analysis: ac_kernel=block covers AC and noise analysis only"); return CSIM_ERR_UNSUPPORTED; }
-    if (N > 63) { setError("distortion analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
+    const std::string who(what);
+    if (acBlock(eng)) { setError(who + ": ac_kernel=block covers AC and noise analysis only"); return CSIM_ERR_UNSUPPORTED; }
+    if (N > 63) { setError(who + " covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
     if (out_p < 0 || out_p >= N || out_m < -1 || out_m >= N || out_p == out_m) {
-        setError("distortion analysis: the output needs two different equations, out_p >= 0 (out_m = -1: ground)");
+        setError(who + ": the output needs two different equations, out_p >= 0 (out_m = -1: ground)");
         return CSIM_ERR_ARG;
     }
-    if (!eng->acAnySource) { setError("distortion analysis: no source carries an AC magnitude (V/I ... AC mag [phase])"); return CSIM_ERR_CONFIG; }
+    if (!eng->acAnySource) { setError(who + ": no source carries an AC magnitude (V/I ... AC mag [phase])"); return CSIM_ERR_CONFIG; }
     a.outP = out_p;
     a.outM = out_m;
     a.M = eng->nDistoDev;
@@ -779,7 +783,7 @@ int csim_disto_batch_dev(csim_engine* eng, const double* d_params, int32_t B, co
         return CSIM_ERR_ARG;
     }
     csim::DistoArgs a{};
-    if (const int rc = distoSetup(eng, out_p_eq, out_m_eq, a)) return rc;
+    if (const int rc = distoSetup(eng, "distortion analysis", out_p_eq, out_m_eq, a)) return rc;
     int which;
     if (const int rc = acPickKernel(eng->cfg.acKernel, eng->plan.N, nullptr, &which)) return rc;
     if (B == 0 || F == 0) return CSIM_OK;
@@ -817,7 +821,7 @@ int csim_disto_batch(csim_engine* eng, const double* params, int32_t B, const do
     if (F < 0 || (B > 0 && F > 0 && !hd)) { setError("csim_disto_batch: bad argument"); return CSIM_ERR_ARG; }
     {
         csim::DistoArgs probe{};
-        if (const int rc = distoSetup(eng, out_p_eq, out_m_eq, probe)) return rc;
+        if (const int rc = distoSetup(eng, "distortion analysis", out_p_eq, out_m_eq, probe)) return rc;
     }
     if (B == 0) return CSIM_OK;
     HIPCHK(hipSetDevice(eng->device));
@@ -829,6 +833,79 @@ int csim_disto_batch(csim_engine* eng, const double* params, int32_t B, const do
     int rc = opPointSolve(eng, params, B, outs, op);
     if (!rc) rc = csim_disto_batch_dev(eng, op.params.as<double>(), B, op.x.as<double>(), freqs, F, out_p_eq, out_m_eq, dH, dHd,
                                        dCoef, op.status.as<uint32_t>(), nullptr);
+    return rc ? rc : outs.finish(op.status, status);
+}
+
+// ---- intermodulation analysis -------------------------------------------------
+
+int csim_imd_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const double* d_xop, const double* freqs,
+                       int32_t F, double f2, int32_t out_p_eq, int32_t out_m_eq, double* d_h, double* d_im, double* d_coef,
+                       uint32_t* d_status, void* stream)
+{
+    if (!eng || B < 0 || F < 0 || !std::isfinite(f2) ||
+        (B > 0 && F > 0 && (!d_params || !d_xop || !freqs || !d_im || !d_status))) {
+        setError("csim_imd_batch_dev: bad argument");
+        return CSIM_ERR_ARG;
+    }
+    csim::ImdArgs a{};
+    if (const int rc = distoSetup(eng, "intermodulation analysis", out_p_eq, out_m_eq, a)) return rc;
+    int which;
+    if (const int rc = acPickKernel(eng->cfg.acKernel, eng->plan.N, nullptr, &which)) return rc;
+    if (B == 0 || F == 0) return CSIM_OK;
+    HIPCHK(hipSetDevice(eng->device));
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    // the coefficients: the caller's [M][7][B] table, or the engine's scratch of one chunk
+    const int M = eng->nDistoDev, chunk = acChunk(eng, B);
+    if (!d_coef)
+        if (const int rc = growDevice(eng->dDistoCoef, eng->distoCoefCap, (size_t)csim::DISTO_NCOEF * M * (size_t)chunk, sizeof(double))) return rc;
+    a.h = d_h;
+    a.im = d_im;
+    a.j2 = nullptr;                                         // both tones drive the same AC sources
+    // one list for the sweep driver: the first tone's F frequencies, then the second tone's
+    std::vector<double> tones((size_t)2 * F, f2);
+    std::copy(freqs, freqs + F, tones.begin());
+    return acSweepChunks(eng, d_params, B, d_xop, tones.data(), 2 * F, which, hs, nullptr, d_status, a, [&](const double*, size_t, size_t) {
+        double* const dCoef = d_coef ? d_coef : eng->dDistoCoef;
+        a.F = F;
+        a.omega2 = a.omega + F;
+        a.coef = dCoef;
+        a.coefStride = d_coef ? (size_t)B : (size_t)chunk;
+        a.coefOff = d_coef ? (size_t)a.b0 : 0;
+        const hipError_t e = csim::launchDistoCoef(eng->gpTran, eng->dDistoElem, M, d_params, B, a.b0, a.Bc, d_xop, dCoef,
+                                                   a.coefStride, a.coefOff, hs);
+        return e != hipSuccess ? e : csim::launchImdSweep(which, a, eng->distoD.data(), eng->distoG.data(), eng->distoS.data(), hs);
+    });
+}
+
+int csim_imd_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F, double f2,
+                   int32_t out_p_eq, int32_t out_m_eq, double* h, double* im, double* coef, uint32_t* status)
+{
+    if (!eng || B < 0) { setError("csim_imd_batch: bad argument"); return CSIM_ERR_ARG; }
+    std::vector<double> card;
+    if (!freqs) {
+        if (const int rc = cardFreqs(eng->cards.imd, "intermodulation analysis", ".IMD", card, &freqs, &F)) return rc;
+        f2 = eng->cards.imdF2overF1 * eng->cards.imd.fstart;
+    }
+    if (out_p_eq == -2) {
+        if (!eng->cards.imd.enabled) { setError("csim_imd_batch: no output given and the netlist has no .IMD card"); return CSIM_ERR_CONFIG; }
+        out_p_eq = eng->cards.imdOut.outP;
+        out_m_eq = eng->cards.imdOut.outM;
+    }
+    if (F < 0 || !std::isfinite(f2) || (B > 0 && F > 0 && !im)) { setError("csim_imd_batch: bad argument"); return CSIM_ERR_ARG; }
+    {
+        csim::ImdArgs probe{};
+        if (const int rc = distoSetup(eng, "intermodulation analysis", out_p_eq, out_m_eq, probe)) return rc;
+    }
+    if (B == 0) return CSIM_OK;
+    HIPCHK(hipSetDevice(eng->device));
+    OpPoint op;
+    HostOutputs outs(F, B);
+    double* dH = outs.add(h, csim::IMD_NSOLVE * eng->plan.N, 2);
+    double* dIm = outs.add(im, csim::IMD_NRATIO, 1);
+    double* dCoef = outs.add(F ? coef : nullptr, csim::DISTO_NCOEF * eng->nDistoDev, 1, false, true);   // no frequency: no sweep writes it
+    int rc = opPointSolve(eng, params, B, outs, op);
+    if (!rc) rc = csim_imd_batch_dev(eng, op.params.as<double>(), B, op.x.as<double>(), freqs, F, f2, out_p_eq, out_m_eq, dH, dIm,
+                                     dCoef, op.status.as<uint32_t>(), nullptr);
     return rc ? rc : outs.finish(op.status, status);
 }
 
@@ -1127,6 +1204,80 @@ int csim_disto_solve_batch(int32_t device, int32_t n, int32_t B, const double* G
     a.h = outs.add(h, 3 * n, 2);
     if (outs.rc) return outs.rc;
     HIPCHK(csim::launchDistoSweep(fr.which, a, nullptr));
+    return outs.finish(fr.dF, flags);
+}
+
+// the intermodulation kernels: any system, any device table, any finite tone pairs; J2 null: the second tone is
+// excited as the first
+int csim_imd_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* Cm, const double* J,
+                         const double* J2, int32_t M, const int32_t* dev_d, const int32_t* dev_g, const int32_t* dev_s,
+                         const double* coef, int32_t out_p, int32_t out_m, const double* omega1, const double* omega2,
+                         int32_t F, int32_t kernel, double* h, double* im, uint32_t* flags)
+{
+    const bool work = n > 0 && B > 0 && F > 0;
+    if (n < 0 || B < 0 || F < 0 || M < 0 || !acKernelValid(kernel) ||
+        (work && (!G || !Cm || !J || !omega1 || !omega2 || !im || (M > 0 && (!dev_d || !dev_g || !dev_s || !coef))))) {
+        setError("csim_imd_solve_batch: bad argument");
+        return CSIM_ERR_ARG;
+    }
+    if (n > 0) {
+        bool ok = out_p >= 0 && out_p < n && out_m >= -1 && out_m < n && out_p != out_m;
+        for (int m = 0; m < M && ok && dev_d && dev_g && dev_s; ++m)
+            ok = dev_d[m] >= -1 && dev_d[m] < n && dev_g[m] >= -1 && dev_g[m] < n && dev_s[m] >= -1 && dev_s[m] < n;
+        if (!ok) { setError("csim_imd_solve_batch: equation index out of range (or out_p == out_m)"); return CSIM_ERR_ARG; }
+    }
+    std::vector<double> tones;                              // the first tone's F frequencies, then the second tone's
+    if (work) {
+        tones.assign(omega1, omega1 + F);
+        tones.insert(tones.end(), omega2, omega2 + F);
+        for (double w : tones)
+            if (!std::isfinite(w)) { setError("csim_imd_solve_batch: the tone frequencies must be finite"); return CSIM_ERR_ARG; }
+    }
+    AcSolveFront fr;
+    if (const int rc = acSolveFront("csim_imd_solve_batch", device, n, B, G, Cm, J, tones.data(), 2 * F, kernel, work, fr)) return rc;
+    if (!work) return CSIM_OK;
+    // device table [M] and coefficients [B][M][7] -> [M][7][B]; J2 [B][n] complex -> [B][re [n], im [n]]
+    const size_t MK = (size_t)M * csim::DISTO_NCOEF;
+    std::vector<double> coefT(MK * (size_t)B);
+    for (int b = 0; b < B; ++b)
+        for (size_t q = 0; q < MK; ++q) coefT[q * (size_t)B + b] = coef[(size_t)b * MK + q];
+    DevBuf dD, dG, dS, dCoef, dJ2;
+    HIPCHK(dD.alloc(sizeof(int32_t) * (size_t)M));
+    HIPCHK(dG.alloc(sizeof(int32_t) * (size_t)M));
+    HIPCHK(dS.alloc(sizeof(int32_t) * (size_t)M));
+    HIPCHK(dCoef.alloc(sizeof(double) * coefT.size()));
+    if (M > 0) {
+        HIPCHK(hipMemcpy(dD.p, dev_d, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dG.p, dev_g, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dS.p, dev_s, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dCoef.p, coefT.data(), sizeof(double) * coefT.size(), hipMemcpyHostToDevice));
+    }
+    if (J2) {
+        std::vector<double> planar((size_t)2 * n * B);
+        for (int b = 0; b < B; ++b)
+            for (int i = 0; i < n; ++i) {
+                planar[((size_t)b * 2) * n + i] = J2[((size_t)b * n + i) * 2];
+                planar[((size_t)b * 2 + 1) * n + i] = J2[((size_t)b * n + i) * 2 + 1];
+            }
+        HIPCHK(dJ2.alloc(sizeof(double) * planar.size()));
+        HIPCHK(hipMemcpy(dJ2.p, planar.data(), sizeof(double) * planar.size(), hipMemcpyHostToDevice));
+    }
+    HostOutputs outs(F, B);
+    csim::ImdArgs a{};
+    fr.fill(a, n, F, B);
+    a.omega2 = a.omega + F;
+    a.j2 = J2 ? dJ2.as<double>() : nullptr;
+    a.M = M;
+    a.outP = out_p; a.outM = out_m;
+    a.devD = dD.as<int32_t>();
+    a.devG = dG.as<int32_t>();
+    a.devS = dS.as<int32_t>();
+    a.coef = dCoef.as<double>();
+    a.coefStride = (size_t)B;
+    a.im = outs.add(im, csim::IMD_NRATIO, 1);
+    a.h = outs.add(h, csim::IMD_NSOLVE * n, 2);
+    if (outs.rc) return outs.rc;
+    HIPCHK(csim::launchImdSweep(fr.which, a, dev_d, dev_g, dev_s, nullptr));
     return outs.finish(fr.dF, flags);
 }
 

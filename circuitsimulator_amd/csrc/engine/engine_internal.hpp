@@ -150,6 +150,7 @@ struct csim_engine {
     const int32_t *dDistoElem = nullptr, *dDistoD = nullptr, *dDistoG = nullptr, *dDistoS = nullptr;
     double* dDistoCoef = nullptr;
     size_t distoCoefCap = 0;               // doubles
+    std::vector<int32_t> distoD, distoG, distoS;   // the host's copy of the terminals: the intermodulation launcher checks them
 
     // S-parameter analysis: the netlist's ports in port order (branch equation, Z0); spPortError says what is wrong
     // with the PORTNUM numbering, if anything

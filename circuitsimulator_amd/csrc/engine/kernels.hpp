@@ -210,6 +210,28 @@ hipError_t launchDistoCoef(const GenPlan& pl, const int32_t* dDevElem, int M, co
                            const double* dXop, double* dCoef, size_t coefStride, size_t coefOff, hipStream_t stream);
 hipError_t launchDistoSweep(int which, const DistoArgs& a, hipStream_t stream);
 
+// Intermodulation analysis (kernels_imd.hip) on the systems launchAcAssemble leaves: six factorisations per (instance,
+// tone pair), at w1, w2, w1 + w2, w1 - w2, 2 w1 and 2 w1 - w2 (ac_imd.hpp).  Coefficients as DistoArgs.  The output
+// pair and the device terminals (hostD, hostG, hostS: the host's copy of the table) are checked by the launcher: they
+// index LDS.  Wave and packed shapes only.
+struct ImdArgs {
+    int N, F, M, B, b0, Bc;
+    int outP, outM;                     // v = x[outP] - x[outM] (-1: ground)
+    double eps;
+    const double* sys;
+    const double* omega;                // [F] first tone
+    const double* omega2;               // [F] second tone
+    const double* j2;                   // [Bc][2 N] (re [N], im [N]) excitation of the second tone, or null: that of the first
+    const int32_t *devD, *devG, *devS;  // [M] drain, gate, source equations (-1 ground)
+    const double* coef;
+    size_t coefStride, coefOff;
+    double* h;                          // [F][6][N][B] complex or null: x0 .. x5
+    double* im;                         // [F][3][B]: IM2+, IM2-, IM3
+    uint32_t* status;                   // [B], OR-ed
+};
+hipError_t launchImdSweep(int which, const ImdArgs& a, const int32_t* hostD, const int32_t* hostG, const int32_t* hostS,
+                          hipStream_t stream);
+
 // Loop-gain analysis (kernels_stb.hip) on the systems launchAcAssemble leaves (their J is not read): one factorisation
 // with two right-hand sides per (instance, frequency), T formed on the device.  The probe's equations are checked by
 // the launcher: they index LDS.  Wave and packed shapes only.

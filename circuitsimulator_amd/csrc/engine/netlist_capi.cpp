@@ -42,11 +42,14 @@ csim::Cards resolveCards(const Circuit& ckt, const SimulationConfig& sim)
     c.noise = gridOf(sim.noise);
     c.sp = gridOf(sim.sp);
     c.disto = gridOf(sim.disto);
+    c.imd = gridOf(sim.imd);
     c.stb = gridOf(sim.stb);
     c.pac = {gridOf(sim.pac), sim.pac.nSide};
     c.pnoise = {gridOf(sim.pnoise), sim.pnoise.nSide};
     c.noiseOut = outputOf(ckt, sim.noise.enabled, sim.noise);
     c.distoOut = outputOf(ckt, sim.disto.enabled, sim.disto);
+    c.imdOut = outputOf(ckt, sim.imd.enabled, sim.imd);
+    c.imdF2overF1 = sim.imd.f2overf1;
     c.pnoiseOut = outputOf(ckt, sim.pnoise.enabled, sim.pnoise);
     if (sim.stb.enabled) c.stbElem = csim::elementIndex(ckt, sim.stb.probeName, -2);
     c.spNoise = sim.sp.enabled && sim.sp.doNoise;
@@ -235,6 +238,16 @@ int csim_netlist_disto(const csim_netlist* nl, int32_t* enabled, int32_t* out_p_
     if (!nl) return CSIM_ERR_ARG;
     putGrid(nl->cards.disto, enabled, sweep, n_points, fstart, fstop);
     putOutput(nl->cards.distoOut, out_p_eq, out_m_eq, nullptr);
+    return CSIM_OK;
+}
+
+int csim_netlist_imd(const csim_netlist* nl, int32_t* enabled, int32_t* out_p_eq, int32_t* out_m_eq, int32_t* sweep,
+                     int32_t* n_points, double* fstart, double* fstop, double* f2overf1)
+{
+    if (!nl) return CSIM_ERR_ARG;
+    putGrid(nl->cards.imd, enabled, sweep, n_points, fstart, fstop);
+    putOutput(nl->cards.imdOut, out_p_eq, out_m_eq, nullptr);
+    if (f2overf1) *f2overf1 = nl->cards.imdF2overF1;
     return CSIM_OK;
 }
 

@@ -25,9 +25,10 @@ struct OutputEqs {                                      // V(out[,ref]) [src]
     int srcElem = -1;                                   // input source element, -1 none
 };
 struct Cards {
-    SweepGrid ac, noise, sp, disto, stb;
+    SweepGrid ac, noise, sp, disto, imd, stb;
     SidebandGrid pac, pnoise;
-    OutputEqs noiseOut, distoOut, pnoiseOut;
+    OutputEqs noiseOut, distoOut, imdOut, pnoiseOut;
+    double imdF2overF1 = 0.0;                           // .IMD: the second tone stays at imdF2overF1 * fstart
     int stbElem = -2;                                   // the .STB probe's element, -2: a name the netlist does not have
     bool spNoise = false;                               // .SP ... 1
     struct { int enabled = 0; double f0 = 0.0; int nHarm = 0; } hb;

@@ -75,12 +75,13 @@ class Netlist:
         self.ac = self._card("ac")
 
     # -- the sweep cards: one reader, one grid; a card is None when the netlist has none ---------------------------
-    def _card(self, name, lead=0, tail=0):
+    def _card(self, name, lead=0, tail=0, dtail=0):
         """What csim_netlist_<name> reports: None, or (`lead` resolved indices, sweep "dec" | "oct" | "lin", n_points,
-        fstart, fstop, `tail` further ints) -- the order of the getter's arguments after `enabled`."""
+        fstart, fstop, `tail` further ints or `dtail` further doubles) -- the order of the getter's arguments after
+        `enabled`."""
         ints = [C.c_int32() for _ in range(1 + lead + 2)]
         grid = [C.c_double(), C.c_double()]
-        more = [C.c_int32() for _ in range(tail)]
+        more = [C.c_int32() for _ in range(tail)] + [C.c_double() for _ in range(dtail)]
         capi.check(getattr(capi.lib(), "csim_netlist_" + name)(self._h, *[C.byref(x) for x in ints + grid + more]))
         if not ints[0].value:
             return None
@@ -104,6 +105,11 @@ class Netlist:
     def disto(self):
         """The .DISTO card: None, or (out_p_eq, out_m_eq, sweep, n_points, fstart, fstop); out_m_eq -1 = ground."""
         return self._card("disto", lead=2)
+
+    @property
+    def imd(self):
+        """The .IMD card: None, or (out_p_eq, out_m_eq, sweep, n_points, fstart, fstop, f2overf1); out_m_eq -1 = ground."""
+        return self._card("imd", lead=2, dtail=1)
 
     @property
     def stb(self):
@@ -142,6 +148,11 @@ class Netlist:
     def disto_freqs(self):
         """Frequency grid of the .DISTO card (numpy, Hz)."""
         return self._card_freqs("DISTO", self.disto, slice(2, 6))
+
+    def imd_freqs(self):
+        """The tones of the .IMD card (Hz): (f1 numpy [F], the card's grid; f2 = f2overf1 * fstart)."""
+        f1 = self._card_freqs("IMD", self.imd, slice(2, 6))
+        return f1, self.imd[6] * self.imd[4]
 
     def stb_freqs(self):
         """Frequency grid of the .STB card (numpy, Hz)."""
@@ -558,6 +569,57 @@ class Engine:
         capi.check(capi.lib().csim_disto_batch(self._h, ptr(params), B, f.ctypes.data, len(f), out_p, out_m, ptr(h),
                                                hd.ctypes.data, ptr(cf), st.ctypes.data))
         return dict(freqs=f, h=h, hd=hd, coef=cf, status=st)
+
+    def _imd_args(self, freqs, f2, out):
+        """-> (f1, f2, out_p, out_m); freqs None takes both tones from the .IMD card, out None its output"""
+        card = self.netlist.imd
+        if freqs is None:
+            f, card_f2 = self.netlist.imd_freqs()
+            f2 = card_f2 if f2 is None else f2
+        else:
+            f = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1)
+            if f2 is None:
+                raise capi.CsimError(capi.CSIM_ERR_CONFIG, "imd: freqs given without f2")
+        return (f, float(f2)) + self._out_pair(out, card, ".IMD")
+
+    def imd(self, params, x_op, freqs=None, f2=None, out=None, want_h=True, coef=False, status=None):
+        """Two-tone intermodulation sweep of the batch around the operating points x_op (device [N][B], from dc());
+        csim_imd_batch_dev.  freqs: the first tone, Hz; f2: the second tone, Hz; out: equation or (out_p, out_m), -1 =
+        ground -- None takes each from the .IMD card.
+        -> dict(freqs, f2, h complex [F][6][N][B] (the solutions at f1, f2, f1 + f2, f1 - f2, 2 f1, 2 f1 - f2) or None,
+                im [F][3][B] (IM2+, IM2-, IM3), coef [M][7][B] or None, status [B]); device tensors; status is OR-ed
+                into `status` when given."""
+        torch = _torch()
+        B = params.shape[1]
+        f, f2, out_p, out_m = self._imd_args(freqs, f2, out)
+        M = len(self.netlist.disto_devices)
+        dev = self._dev()
+        h = torch.zeros((len(f), 6, self.N, B, 2), dtype=torch.float64, device=dev) if want_h else None
+        im = torch.zeros((len(f), 3, B), dtype=torch.float64, device=dev)
+        cf = torch.zeros((M, 7, B), dtype=torch.float64, device=dev) if coef else None
+        st = status if status is not None else torch.zeros(B, dtype=torch.int32, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None     # noqa: E731
+        capi.check(capi.lib().csim_imd_batch_dev(self._h, params.data_ptr(), B, x_op.data_ptr(), f.ctypes.data, len(f), f2,
+                                                 out_p, out_m, ptr(h), im.data_ptr(), ptr(cf), st.data_ptr(),
+                                                 self._stream()))
+        return dict(freqs=f, f2=f2, h=torch.view_as_complex(h) if h is not None else None, im=im, coef=cf, status=st)
+
+    def imd_host(self, params=None, B=1, freqs=None, f2=None, out=None, want_h=True, coef=False):
+        """DC operating point + intermodulation sweep (csim_imd_batch): numpy, instance-major.
+        -> dict(freqs, f2, h complex [B][F][6][N] or None, im [B][F][3], coef [B][M][7] or None, status [B])"""
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=np.float64)
+            B = params.shape[0]
+        f, f2, out_p, out_m = self._imd_args(freqs, f2, out)
+        M = len(self.netlist.disto_devices)
+        h = np.zeros((B, len(f), 6, self.N), dtype=np.complex128) if want_h else None
+        im = np.zeros((B, len(f), 3))
+        cf = np.zeros((B, M, 7)) if coef else None
+        st = np.zeros(B, dtype=np.uint32)
+        ptr = lambda a: a.ctypes.data if a is not None else None    # noqa: E731
+        capi.check(capi.lib().csim_imd_batch(self._h, ptr(params), B, f.ctypes.data, len(f), f2, out_p, out_m, ptr(h),
+                                             im.ctypes.data, ptr(cf), st.ctypes.data))
+        return dict(freqs=f, f2=f2, h=h, im=im, coef=cf, status=st)
 
     def _stb_args(self, freqs, probe):
         """-> (freqs, probe element); None takes the .STB card's value (-1 tells the library to)"""
@@ -1157,6 +1219,52 @@ def disto_solve_batch(G, Cm, J, dev_d, dev_g, dev_s, coef, out, omega, kernel="a
         dev_s.ctypes.data, coef.ctypes.data, int(out[0]), int(out[1]), omega.ctypes.data, F, _AC_KERNELS[kernel],
         h.ctypes.data if h is not None else None, hd.ctypes.data, flags.ctypes.data))
     return dict(h=h, hd=hd, flags=flags)
+
+
+def imd_solve_batch(G, Cm, J, dev_d, dev_g, dev_s, coef, out, omega1, omega2, J2=None, kernel="auto", device=0,
+                    want_h=True):
+    """The intermodulation kernels on systems and device tables given directly (csim_imd_solve_batch): six solves per
+    tone pair, at w1, w2, w1 + w2, w1 - w2, 2 w1 and 2 w1 - w2.  G, Cm [B][n][n] real; J [B][n] complex excites the
+    first tone, J2 the second (None: J); devices dev_d, dev_g, dev_s [M] (equations, -1 = ground) with coef [B][M][7];
+    out = (out_p, out_m), -1 = ground; omega1, omega2 [F] rad/s, any finite values; kernel auto | wave | packed (block
+    is refused: CSIM_ERR_UNSUPPORTED).
+    -> dict(h complex [B][F][6][n] or None, im [B][F][3] (IM2+, IM2-, IM3), flags [B])"""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    Cm = np.ascontiguousarray(Cm, dtype=np.float64)
+    J = np.ascontiguousarray(J, dtype=np.complex128)
+    J2 = np.ascontiguousarray(J2, dtype=np.complex128) if J2 is not None else None
+    omega1 = np.ascontiguousarray(omega1, dtype=np.float64).reshape(-1)
+    omega2 = np.ascontiguousarray(omega2, dtype=np.float64).reshape(-1)
+    dev_d = np.ascontiguousarray(dev_d, dtype=np.int32).reshape(-1)
+    dev_g = np.ascontiguousarray(dev_g, dtype=np.int32).reshape(-1)
+    dev_s = np.ascontiguousarray(dev_s, dtype=np.int32).reshape(-1)
+    B, n = J.shape
+    M, F = len(dev_d), len(omega1)
+    if len(dev_g) != M or len(dev_s) != M:
+        raise ValueError("dev_d, dev_g and dev_s differ in length")
+    if len(omega2) != F:
+        raise ValueError("omega1 and omega2 differ in length")
+    if J2 is not None and J2.shape != J.shape:
+        raise ValueError("J and J2 differ in shape")
+    coef = np.ascontiguousarray(coef, dtype=np.float64).reshape(B, M, 7)
+    h = np.zeros((B, F, 6, n), dtype=np.complex128) if want_h else None
+    im = np.zeros((B, F, 3))
+    flags = np.zeros(B, dtype=np.uint32)
+    capi.check(capi.lib().csim_imd_solve_batch(
+        device, n, B, G.ctypes.data, Cm.ctypes.data, J.ctypes.data, J2.ctypes.data if J2 is not None else None, M,
+        dev_d.ctypes.data, dev_g.ctypes.data, dev_s.ctypes.data, coef.ctypes.data, int(out[0]), int(out[1]),
+        omega1.ctypes.data, omega2.ctypes.data, F, _AC_KERNELS[kernel], h.ctypes.data if h is not None else None,
+        im.ctypes.data, flags.ctypes.data))
+    return dict(h=h, im=im, flags=flags)
+
+
+def oip3(h_or_v0, im3):
+    """Output-referred third-order intercept amplitude |v0| sqrt(|v0| / |v5|) = |v0| / sqrt(IM3), from the fundamental
+    at the output (complex phasor or magnitude; numpy or torch) and IM3; inf where IM3 is 0."""
+    if hasattr(im3, "sqrt"):                                  # torch
+        return abs(h_or_v0) / im3.sqrt()
+    with np.errstate(divide="ignore"):
+        return np.abs(h_or_v0) / np.sqrt(np.asarray(im3, dtype=np.float64))
 
 
 def stb_solve_batch(G, Cm, probe, omega, kernel="auto", device=0, want_x=True, freqs=None):

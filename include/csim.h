@@ -527,6 +527,51 @@ int  csim_disto_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, i
 int  csim_disto_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F,
                       int32_t out_p_eq, int32_t out_m_eq, double* h, double* hd, double* coef, uint32_t* status);
 
+/* ---- Intermodulation analysis (.IMD; two-tone IM2 and IM3 by a Volterra series at the operating point: six
+ *      factorisations per tone pair) ----
+ * Card: `.IMD V(out[,ref]) DEC|OCT|LIN n fstart fstop f2overf1`, the output as on .DISTO.  f1 sweeps the grid of
+ *   csim_ac_freqs; f2 stays at f2overf1 * fstart (ngspice's rule), 0 < f2overf1 < 1, so f1 > f2 > 0 at every point.
+ *   Any other token count or an f2overf1 outside (0, 1) is a card error, reported, the statement dropped.
+ * System, devices, coefficients c, complex arithmetic, right-hand side accumulation: those of "Distortion analysis".
+ *   x(t) = Re sum X e^{jwt}, peak amplitudes.  Both tones drive the netlist's `AC mag [phase]` sources (J2 = J1, the
+ *   equal-amplitude two-tone test); distinct excitations exist only in csim_imd_solve_batch.
+ * Forms.  A "pair" U = (Ug, Ud) of a solution x and a device is (x[g] - x[s], x[d] - x[s]); * is the conjugate.
+ *     Q(A, B)    = 0.5 * ( (c_gg * (Ag Bg) + c_gd * ((Ag Bd) + (Ad Bg))) + c_dd * (Ad Bd) )
+ *     T(A, A, B) = ( ((c_ggg * (GG Bg) + c_ggd * ((GG Bd) + 2.0 * (GD Bg))) + c_gdd * (2.0 * (GD Bd) + (DD Bg)))
+ *                    + c_ddd * (DD Bd) ) / 6.0,        GG = Ag Ag, GD = Ag Ad, DD = Ad Ad
+ * Six solves per point, in this order; Ua, Ub, Vd, Vh are the pairs of x0, x1, x3, x4.  The current of each device is
+ *   subtracted at d and added at s, the devices in ascending order.
+ *     k  frequency                right-hand side
+ *     0  w1                       J1
+ *     1  w2                       J2
+ *     2  ws = w1 + w2             Q(Ua, Ub)
+ *     3  wd = w1 - w2             Q(Ua, Ub*)
+ *     4  wh = 2.0 * w1            0.5 * Q(Ua, Ua), computed as I2 of "Distortion analysis"
+ *     5  w3 = wh - w2             (0.75 * T(Ua, Ua, Ub*) + Q(Ua, Vd)) + Q(Ub*, Vh)
+ *   A(-w) = G - j w C is ordinary arithmetic: any finite (w1, w2) is legal in the direct entry.
+ * Outputs.  The six solutions, and v_k = x_k[out_p] - x_k[out_m]: IM2+ = |v2| / |v0|, IM2- = |v3| / |v0|,
+ *   IM3 = |v5| / |v0|, |.| and the division as HD2, HD3: +0.0 where |v0| == 0.  The output intercept amplitude
+ *   OIP3 = |v0| * sqrt(|v0| / |v5|) is left to the caller.
+ * Failures.  All six factorisations are attempted; a failed solve makes itself and every later one +0.0 and sets
+ *   CSIM_ST_LU_TINY_PIVOT.  M == 0 is legal.
+ * Sizes and kernels as "Distortion analysis"; both kernel shapes give bit-identical results.  The exact order of every
+ * operation: engine/ac_imd.hpp, written once for host and device.
+ *
+ * Enqueues the sweep; never waits for it; frequency lists as csim_ac_batch_dev.  freqs [F]: f1 in Hz; f2 in Hz, finite.
+ *   d_h [F][6][N][B] complex (re, im): x0 .. x5, or NULL      d_im [F][3][B]: IM2+, IM2-, IM3
+ *   d_coef [M][7][B] or NULL: the coefficients                d_status [B], OR-ed                                  */
+/* .IMD card: as csim_netlist_disto, then f2overf1 */
+int  csim_netlist_imd(const csim_netlist* nl, int32_t* enabled, int32_t* out_p_eq, int32_t* out_m_eq, int32_t* sweep,
+                      int32_t* n_points, double* fstart, double* fstop, double* f2overf1);
+int  csim_imd_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int32_t B, const double* d_xop,
+                        const double* freqs, int32_t F, double f2, int32_t out_p_eq, int32_t out_m_eq, double* d_h,
+                        double* d_im, double* d_coef, uint32_t* d_status, void* stream);
+/* DC operating point, then the sweep.  params [B][P] or NULL (nominal); freqs NULL = the grid and the f2 of the
+ * netlist's .IMD card (F and f2 ignored); out_p_eq == -2 = the card's output (out_m_eq ignored); no card:
+ * CSIM_ERR_CONFIG.  h [B][F][6][N] complex or NULL; im [B][F][3]; coef [B][M][7] or NULL.                           */
+int  csim_imd_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F, double f2,
+                    int32_t out_p_eq, int32_t out_m_eq, double* h, double* im, double* coef, uint32_t* status);
+
 /* ---- Loop-gain analysis (.STB; the loop gain T of a feedback loop by Middlebrook's double injection at a V source in
  *      series in the loop, one factorisation with two right-hand sides per frequency; phase and gain margins) ----
  * Card: `.STB Vprobe DEC|OCT|LIN n fstart fstop`, the grid of csim_ac_freqs.  Any other token count is a card error,
@@ -843,6 +888,15 @@ int  csim_disto_solve_batch(int32_t device, int32_t n, int32_t B, const double* 
                             int32_t M, const int32_t* dev_d, const int32_t* dev_g, const int32_t* dev_s,
                             const double* coef, int32_t out_p, int32_t out_m, const double* omega, int32_t F,
                             int32_t kernel, double* h, double* hd, uint32_t* flags);
+
+/* The intermodulation kernels on systems and device tables given directly (host pointers; lu_eps = 1e-15), the
+ * counterpart of csim_disto_solve_batch for "Intermodulation analysis".  J [B][n] complex excites the first tone, J2 the
+ * second (NULL: J); omega1, omega2 [F] rad/s, any finite values (else CSIM_ERR_ARG).  im [B][F][3]; h [B][F][6][n]
+ * complex (zeros from the failed solve on) and flags [B] are optional.  Kernels and refusals as csim_disto_solve_batch. */
+int  csim_imd_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* C, const double* J,
+                          const double* J2, int32_t M, const int32_t* dev_d, const int32_t* dev_g, const int32_t* dev_s,
+                          const double* coef, int32_t out_p, int32_t out_m, const double* omega1, const double* omega2,
+                          int32_t F, int32_t kernel, double* h, double* im, uint32_t* flags);
 
 /* The loop-gain kernels on systems given directly (host pointers; lu_eps = 1e-15), the counterpart of
  * csim_ac_solve_batch for "Loop-gain analysis".  G, C [B][n][n] row-major; eq_p, eq_m, eq_br the probe's + node, - node
