@@ -97,6 +97,10 @@ PROTOTYPES = {
                                         _vp, _vp, _vp]),
     "csim_pnoise_batch": (C.c_int, [_vp, _vp, _i32, _dbl, _dbl, _vp, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp]),
+    "csim_netlist_pz": (C.c_int, [_vp, _pi32, _pdbl, _pdbl]),
+    "csim_pz_batch_dev": (C.c_int, [_vp, _vp, _i32, _vp, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "csim_pz_batch": (C.c_int, [_vp, _vp, _i32, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp]),
+    "csim_pz_solve_batch": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp]),
     "csim_netlist_num_ports": (C.c_int, [_vp]),
     "csim_netlist_port": (C.c_int, [_vp, _i32, _pi32, _pi32, _pdbl]),
     "csim_netlist_sp": (C.c_int, [_vp, _pi32, _pi32, _pi32, _pdbl, _pdbl]),

@@ -159,6 +159,25 @@ BatchStbResult BatchEngine::stb(const std::vector<double>& params, int B, const 
     return r;
 }
 
+BatchPzResult BatchEngine::pz(const std::vector<double>& params, int B, double fmax, double sigma0)
+{
+    // a BatchEngine has no cards: fmax NaN would ask csim_pz_batch for one
+    if (!(fmax > 0.0) || B < 1)
+        throw std::invalid_argument("BatchEngine::pz: fmax must be positive, B >= 1 (pass the .PZ card's numbers from "
+                                    "SimulationConfig)");
+    BatchPzResult r;
+    const std::size_t n = static_cast<std::size_t>(numUnknowns());
+    r.poles.assign(static_cast<std::size_t>(B) * n, std::complex<double>());
+    r.nPoles.assign(static_cast<std::size_t>(B), 0);
+    r.nRhp.assign(static_cast<std::size_t>(B), 0);
+    r.maxRe.assign(static_cast<std::size_t>(B), 0.0);
+    r.status.assign(static_cast<std::size_t>(B), 0);
+    if (csim_pz_batch(eng_, params.empty() ? nullptr : params.data(), B, fmax, sigma0, reinterpret_cast<double*>(r.poles.data()),
+                      r.nPoles.data(), r.nRhp.data(), r.maxRe.data(), r.status.data()) != CSIM_OK)
+        fail("csim_pz_batch");
+    return r;
+}
+
 BatchPssResult BatchEngine::pss(const std::vector<double>& params, int B, double tstep, double f0, int nHarm,
                                 const std::vector<int32_t>& probeEq, double tol, int maxRounds)
 {

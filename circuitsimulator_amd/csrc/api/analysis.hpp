@@ -91,6 +91,13 @@ struct BatchStbResult {
     std::vector<uint32_t> status;                 // DC and LU bits (CSIM_ST_LU_TINY_PIVOT: a singular frequency, or den == 0)
 };
 
+struct BatchPzResult {
+    std::vector<std::complex<double>> poles;      // [B][N]: dominant pole first, NaN beyond nPoles
+    std::vector<int32_t> nPoles, nRhp;            // [B]: finite poles, and those with Re s > 0
+    std::vector<double> maxRe;                    // [B]: the largest Re s, NaN without a pole
+    std::vector<uint32_t> status;                 // DC bits, CSIM_ST_PZ_SINGULAR, CSIM_ST_PZ_NONCONV
+};
+
 struct BatchPssResult {
     int nHarm = 0, nProbe = 0;
     std::vector<double> x0;                       // [B][N]: the state the period starts and ends at
@@ -178,6 +185,11 @@ public:
     // strictly increasing positive frequencies.
     BatchStbResult stb(const std::vector<double>& params, int B, const std::vector<double>& freqs, int probeElem = -1,
                        bool wantMargins = true);
+
+    // Poles of every instance's linearisation at its operating point (csim_pz_batch, include/csim.h "Pole analysis"):
+    // eigenvalues slower than 1 / (2 pi fmax) are poles at infinity; sigma0 shifts G + sigma0 C.  fmax must be positive
+    // (std::invalid_argument otherwise): a BatchEngine has no cards, pass the .PZ card's numbers from SimulationConfig.
+    BatchPzResult pz(const std::vector<double>& params, int B, double fmax, double sigma0 = 0.0);
 
     // Periodic steady state of the backward-Euler transient by shooting Newton (csim_pss_batch, include/csim.h): DC
     // operating point, then rounds of one period each; harmonics 0 .. nHarm of probeEq (empty = every unknown).

@@ -3,7 +3,7 @@
 //   whose first non-blank is '*' or ';' is a comment; a leading '+' continues
 //   the previous logical line; tokens split on blanks.
 //   Devices by first letter (any case): R C L V I M.   Cards: .MODEL (read in
-//   a first pass, so it may follow its users) .TRAN .OP .DC .AC .NOISE .SP .DISTO .IMD .STB .HB
+//   a first pass, so it may follow its users) .TRAN .OP .DC .AC .NOISE .SP .DISTO .IMD .STB .PZ .HB
 //   .PAC .PNOISE .PRINT .PLOTNV .PLOTNC; anything else is reported and skipped.
 #include "parser.hpp"
 
@@ -427,6 +427,7 @@ void NetlistParser::dotCard(const Statement& st)
     else if (head == ".disto")  distoCard(st);
     else if (head == ".imd")    imdCard(st);
     else if (head == ".stb")    stbCard(st);
+    else if (head == ".pz")     pzCard(st);
     else if (head == ".print")  printCard(st);
     else if (head == ".model")  modelCard(st);
     else if (head == ".hb")     hbCard(st);
@@ -634,6 +635,28 @@ void NetlistParser::stbCard(const Statement& st)
     if (t.size() != 6 || !sweepWord(t[2], true, cfg.sweepType)) return invalidSyntax(st, ".STB");
     cfg.probeName = t[1];
     if (sweepGrid(st, t, 3, ".STB", cfg)) sim.stb = cfg;
+}
+
+// .PZ POL fmax [sigma0]   (poles only: ZER and PZ are refused by name; any other token count is an error)
+void NetlistParser::pzCard(const Statement& st)
+{
+    const auto& t = st.tokens;
+    const std::string what = t.size() > 1 ? toLower(t[1]) : std::string();
+    if (what == "zer" || what == "pz") {
+        std::cerr << "Line " << st.lineNo << ": .PZ supports POL only: " << st.raw << "\n";
+        return;
+    }
+    if ((t.size() != 3 && t.size() != 4) || what != "pol") return invalidSyntax(st, ".PZ");
+    PzConfig cfg;
+    try {
+        cfg.fmax = parseSpiceNumber(t[2]);
+        if (t.size() == 4) cfg.sigma0 = parseSpiceNumber(t[3]);
+    } catch (const std::exception& e) {
+        cannotParse(st, ".PZ", e.what());
+        return;
+    }
+    cfg.enabled = true;
+    sim.pz = cfg;
 }
 
 // .HB f0 nharm

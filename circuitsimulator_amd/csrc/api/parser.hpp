@@ -53,6 +53,7 @@ private:
     void distoCard(const Statement& st);
     void imdCard(const Statement& st);
     void stbCard(const Statement& st);
+    void pzCard(const Statement& st);
     void spCard(const Statement& st);
     void hbCard(const Statement& st);
     void pacCard(const Statement& st);

@@ -177,6 +177,13 @@ struct StbConfig : AcConfig {
     std::string probeName;          // a V source in series in the loop, + on the driving side
 };
 
+// .PZ POL fmax [sigma0]: poles only (ZER and PZ are refused by the parser)
+struct PzConfig {
+    bool enabled = false;
+    double fmax = 0.0;              // Hz: eigenvalues below 1 / (2 pi fmax) are poles at infinity
+    double sigma0 = 0.0;            // rad/s: the shift of G + sigma0 C
+};
+
 struct HbConfig {
     bool enabled = false;
     double f0 = 0.0;
@@ -214,6 +221,7 @@ public:
     DistoConfig disto;
     ImdConfig imd;
     StbConfig stb;
+    PzConfig pz;
     HbConfig hb;
     PacConfig pac;
     PnoiseConfig pnoise;

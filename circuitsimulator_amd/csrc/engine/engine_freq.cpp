@@ -1,5 +1,5 @@
 // engine_freq.cpp -- C-ABI of the frequency-domain analyses: AC, noise, S-parameters, two-port noise, distortion,
-// intermodulation and loop gain, each as csim_*_batch_dev (device pointers, enqueue only), csim_*_batch (host pointers, DC operating point
+// intermodulation, loop gain and poles, each as csim_*_batch_dev (device pointers, enqueue only), csim_*_batch (host pointers, DC operating point
 // included) and csim_*_solve_batch (any system, no engine).  What they share is written once: kernel choice, the chunk
 // driver, scratch growth, the card's frequencies, the operating point and the output list of the host-pointer forms.
 // A new analysis supplies its setup function, its ...Args and its sweep launch.
@@ -19,6 +19,7 @@
 #include "csim.h"
 #include "engine_host.hpp"
 #include "kernels.hpp"
+#include "pz.hpp"
 
 using csim::setError;
 
@@ -412,6 +413,32 @@ bool stbFreqsIncrease(const double* freqs, int F)
     for (int f = 0; f < F; ++f)
         if (!(freqs[f] > (f ? freqs[f - 1] : 0.0)) || !std::isfinite(freqs[f])) return false;
     return true;
+}
+
+// fmax and sigma0 of a pole call and the engine's refusals, in the order include/csim.h "Pole analysis" states;
+// fmax NaN: the card's pair
+int pzSetup(const csim_engine* eng, const char* who, double& fmax, double& sigma0)
+{
+    const bool fromCard = fmax != fmax;
+    if ((!fromCard && (!std::isfinite(fmax) || !(fmax > 0.0))) || !std::isfinite(sigma0)) {
+        setError(std::string(who) + ": fmax must be finite and > 0 (NaN: the .PZ card's), sigma0 finite");
+        return CSIM_ERR_ARG;
+    }
+    if (acBlock(eng) || eng->cfg.acKernel == csim::AC_KERNEL_PACKED) {
+        setError("pole analysis: there is one kernel, ac_kernel=block and ac_kernel=packed do not cover it");
+        return CSIM_ERR_UNSUPPORTED;
+    }
+    if (eng->plan.N > csim::PZ_MAX_N) { setError("pole analysis covers circuits of up to 63 unknowns"); return CSIM_ERR_UNSUPPORTED; }
+    if (fromCard) {
+        if (!eng->cards.pz.enabled) { setError(std::string(who) + ": no fmax given and the netlist has no .PZ card"); return CSIM_ERR_CONFIG; }
+        fmax = eng->cards.pz.fmax;
+        sigma0 = eng->cards.pz.sigma0;
+        if (!std::isfinite(fmax) || !(fmax > 0.0) || !std::isfinite(sigma0)) {
+            setError(std::string(who) + ": the .PZ card needs fmax > 0 and a finite sigma0");
+            return CSIM_ERR_CONFIG;
+        }
+    }
+    return CSIM_OK;
 }
 
 // ---- engine-free forms -----------------------------------------------------------
@@ -987,6 +1014,69 @@ int csim_stb_batch(csim_engine* eng, const double* params, int32_t B, const doub
     return rc;
 }
 
+// ---- pole analysis ----------------------------------------------------------
+
+int csim_pz_batch_dev(csim_engine* eng, const double* d_params, int32_t B, const double* d_xop, double fmax, double sigma0,
+                      double* d_poles, int32_t* d_n_poles, int32_t* d_n_rhp, double* d_max_re, uint32_t* d_status, void* stream)
+{
+    if (!eng || B < 0 || (B > 0 && (!d_params || !d_xop || !d_poles || !d_n_poles || !d_n_rhp || !d_max_re || !d_status))) {
+        setError("csim_pz_batch_dev: bad argument");
+        return CSIM_ERR_ARG;
+    }
+    if (const int rc = pzSetup(eng, "csim_pz_batch_dev", fmax, sigma0)) return rc;
+    if (B == 0) return CSIM_OK;
+    HIPCHK(hipSetDevice(eng->device));
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    const int N = eng->plan.N;
+    const int chunk = acChunk(eng, B);
+    if (const int rc = growDevice(eng->dAcSys, eng->acSysCap, (size_t)chunk, sizeof(double) * csim::acSystemDoubles(N))) return rc;
+    csim::PzArgs a{};
+    a.N = N; a.B = B;
+    a.eps = eng->cir.ir.k.lu_eps;
+    a.sigma0 = sigma0;
+    a.wmax = csim::pz_wmax(fmax);
+    a.sys = eng->dAcSys;
+    a.poles = d_poles;
+    a.nPoles = d_n_poles;
+    a.nRhp = d_n_rhp;
+    a.maxRe = d_max_re;
+    a.status = d_status;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        a.b0 = b0;
+        a.Bc = std::min(chunk, B - b0);
+        HIPCHK(csim::launchAcAssemble(eng->gpTran, eng->dAcRe, eng->dAcIm, d_params, B, b0, a.Bc, d_xop, eng->dAcSys, hs,
+                                      csim::AC_KERNEL_WAVE));
+        HIPCHK(csim::launchPz(a, hs));
+    }
+    return CSIM_OK;
+}
+
+int csim_pz_batch(csim_engine* eng, const double* params, int32_t B, double fmax, double sigma0, double* poles,
+                  int32_t* n_poles, int32_t* n_rhp, double* max_re, uint32_t* status)
+{
+    if (!eng || B < 0 || (B > 0 && !poles)) { setError("csim_pz_batch: bad argument"); return CSIM_ERR_ARG; }
+    if (const int rc = pzSetup(eng, "csim_pz_batch", fmax, sigma0)) return rc;
+    if (B == 0) return CSIM_OK;
+    HIPCHK(hipSetDevice(eng->device));
+    const int N = eng->plan.N;
+    OpPoint op;
+    HostOutputs outs(1, B);
+    double* dPoles = outs.add(poles, N, 2, false, true);                        // [N][B] -> [B][N]
+    DevBuf dNp, dNr, dMx;
+    HIPCHK(dNp.alloc(sizeof(int32_t) * (size_t)B));
+    HIPCHK(dNr.alloc(sizeof(int32_t) * (size_t)B));
+    HIPCHK(dMx.alloc(sizeof(double) * (size_t)B));
+    int rc = opPointSolve(eng, params, B, outs, op);
+    if (!rc) rc = csim_pz_batch_dev(eng, op.params.as<double>(), B, op.x.as<double>(), fmax, sigma0, dPoles, dNp.as<int32_t>(),
+                                    dNr.as<int32_t>(), dMx.as<double>(), op.status.as<uint32_t>(), nullptr);
+    if (!rc) rc = outs.finish(op.status, status);
+    if (rc) return rc;
+    if (n_poles) HIPCHK(hipMemcpy(n_poles, dNp.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    if (n_rhp) HIPCHK(hipMemcpy(n_rhp, dNr.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    if (max_re) HIPCHK(hipMemcpy(max_re, dMx.p, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost));
+    return CSIM_OK;
+}
+
 // ---- engine-free forms: any system through the sweep kernels, without an engine or a netlist ----------------
 
 // the complex counterpart of csim_lu_solve_batch: any (G + jwC) x = J through the AC sweep kernels
@@ -1322,6 +1412,53 @@ int csim_stb_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, 
     }
     if (const int rc = outs.finish(fr.dF, flags)) return rc;
     if (margins && found) HIPCHK(hipMemcpy(found, dFound.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    return CSIM_OK;
+}
+
+// the pole kernel: any (G, C)
+int csim_pz_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* Cm, double fmax, double sigma0,
+                        double* poles, int32_t* n_poles, int32_t* n_rhp, double* max_re, uint32_t* flags)
+{
+    const bool work = n > 0 && B > 0;
+    if (n < 0 || B < 0 || !std::isfinite(fmax) || !(fmax > 0.0) || !std::isfinite(sigma0) || (work && (!G || !Cm || !poles))) {
+        setError("csim_pz_solve_batch: bad argument");
+        return CSIM_ERR_ARG;
+    }
+    if (n > csim::PZ_MAX_N) { setError("csim_pz_solve_batch covers n <= 63"); return CSIM_ERR_UNSUPPORTED; }
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
+        setError("csim_pz_solve_batch: no usable HIP device (this library has no CPU path)");
+        return CSIM_ERR_NO_DEVICE;
+    }
+    if (!work) return CSIM_OK;
+    HIPCHK(hipSetDevice(device));
+    const std::vector<double> sys = packAcSystems(n, B, G, Cm, nullptr);
+    DevBuf dSys, dF, dNp, dNr, dMx;
+    HIPCHK(dSys.alloc(sizeof(double) * sys.size()));
+    HIPCHK(dF.alloc(sizeof(uint32_t) * (size_t)B));
+    HIPCHK(dNp.alloc(sizeof(int32_t) * (size_t)B));
+    HIPCHK(dNr.alloc(sizeof(int32_t) * (size_t)B));
+    HIPCHK(dMx.alloc(sizeof(double) * (size_t)B));
+    HIPCHK(hipMemcpy(dSys.p, sys.data(), sizeof(double) * sys.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(dF.p, 0, sizeof(uint32_t) * (size_t)B));
+    HostOutputs outs(1, B);
+    csim::PzArgs a{};
+    a.N = n; a.B = B; a.b0 = 0; a.Bc = B;
+    a.eps = 1e-15;
+    a.sigma0 = sigma0;
+    a.wmax = csim::pz_wmax(fmax);
+    a.sys = dSys.as<double>();
+    a.poles = outs.add(poles, n, 2, false, true);                               // [n][B] -> [B][n]
+    a.nPoles = dNp.as<int32_t>();
+    a.nRhp = dNr.as<int32_t>();
+    a.maxRe = dMx.as<double>();
+    a.status = dF.as<uint32_t>();
+    if (outs.rc) return outs.rc;
+    HIPCHK(csim::launchPz(a, nullptr));
+    if (const int rc = outs.finish(dF, flags)) return rc;
+    if (n_poles) HIPCHK(hipMemcpy(n_poles, dNp.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    if (n_rhp) HIPCHK(hipMemcpy(n_rhp, dNr.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    if (max_re) HIPCHK(hipMemcpy(max_re, dMx.p, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost));
     return CSIM_OK;
 }
 

@@ -251,6 +251,22 @@ hipError_t launchStbSweep(int which, const StbArgs& a, hipStream_t stream);
 hipError_t launchStbMargins(int F, int B, const double* dFreqs, const double* dT, double* dMargins, int32_t* dFound,
                             hipStream_t stream);
 
+// Pole analysis (kernels_pz.hip) on the systems launchAcAssemble leaves (their J is not read): per instance the
+// eigenvalues of -(G + sigma0 C)^-1 C, the cut at wmax, the ordered poles and their summary.  One wave per instance,
+// N <= 63 (checked by the launcher: N sizes the LDS).
+struct PzArgs {
+    int N, B, b0, Bc;
+    double eps, sigma0, wmax;
+    const double* sys;
+    double* poles;                      // [N][B] complex: slot k of instance b
+    int32_t* nPoles;                    // [B]
+    int32_t* nRhp;                      // [B]
+    double* maxRe;                      // [B]
+    uint32_t* status;                   // [B], OR-ed
+};
+size_t pzLdsBytes(int N);
+hipError_t launchPz(const PzArgs& a, hipStream_t stream);
+
 // Periodic steady state (kernels_pss.hip): one shooting round of chunk instances b0 .. b0+Bc-1 of a batch of B -- the
 // period kernel (K steps of the general transient from x0, the sensitivity W_K, the harmonics of the probes), then the
 // update kernel (closure test, x0 += (I - W_K)^-1 (x_K - x0)).  Probe equations are checked by the caller: they index LDS.

@@ -52,6 +52,9 @@ csim::Cards resolveCards(const Circuit& ckt, const SimulationConfig& sim)
     c.imdF2overF1 = sim.imd.f2overf1;
     c.pnoiseOut = outputOf(ckt, sim.pnoise.enabled, sim.pnoise);
     if (sim.stb.enabled) c.stbElem = csim::elementIndex(ckt, sim.stb.probeName, -2);
+    c.pz.enabled = sim.pz.enabled ? 1 : 0;
+    c.pz.fmax = sim.pz.fmax;
+    c.pz.sigma0 = sim.pz.sigma0;
     c.spNoise = sim.sp.enabled && sim.sp.doNoise;
     c.hb.enabled = sim.hb.enabled ? 1 : 0;
     c.hb.f0 = sim.hb.f0;
@@ -276,6 +279,15 @@ int csim_netlist_stb(const csim_netlist* nl, int32_t* enabled, int32_t* elem, in
     if (eq_p)     *eq_p = isV ? nl->cir.eq[4 * static_cast<std::size_t>(e) + 0] : -2;
     if (eq_m)     *eq_m = isV ? nl->cir.eq[4 * static_cast<std::size_t>(e) + 1] : -2;
     if (eq_br)    *eq_br = isV ? nl->cir.branchEq[static_cast<std::size_t>(e)] : -2;
+    return CSIM_OK;
+}
+
+int csim_netlist_pz(const csim_netlist* nl, int32_t* enabled, double* fmax, double* sigma0)
+{
+    if (!nl) return CSIM_ERR_ARG;
+    if (enabled) *enabled = nl->cards.pz.enabled;
+    if (fmax)    *fmax = nl->cards.pz.fmax;
+    if (sigma0)  *sigma0 = nl->cards.pz.sigma0;
     return CSIM_OK;
 }
 

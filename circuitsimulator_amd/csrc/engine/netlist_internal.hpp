@@ -30,6 +30,7 @@ struct Cards {
     OutputEqs noiseOut, distoOut, imdOut, pnoiseOut;
     double imdF2overF1 = 0.0;                           // .IMD: the second tone stays at imdF2overF1 * fstart
     int stbElem = -2;                                   // the .STB probe's element, -2: a name the netlist does not have
+    struct { int enabled = 0; double fmax = 0.0, sigma0 = 0.0; } pz;   // .PZ POL fmax [sigma0]
     bool spNoise = false;                               // .SP ... 1
     struct { int enabled = 0; double f0 = 0.0; int nHarm = 0; } hb;
     struct { int enabled = 0; double tstep = 0.0; } tran;

@@ -174,6 +174,13 @@ class Netlist:
         return (f0.value, nh.value) if en.value else None
 
     @property
+    def pz(self):
+        """The .PZ card: None, or (fmax in Hz, sigma0 in rad/s)."""
+        en, fm, s0 = C.c_int32(), C.c_double(), C.c_double()
+        capi.check(capi.lib().csim_netlist_pz(self._h, C.byref(en), C.byref(fm), C.byref(s0)))
+        return (fm.value, s0.value) if en.value else None
+
+    @property
     def noise_sources(self):
         """The noise generators in element order: [(element index, eq_a, eq_b)], -1 = ground."""
         L = capi.lib()
@@ -672,6 +679,50 @@ class Engine:
         capi.check(capi.lib().csim_stb_batch(self._h, ptr(params), B, f.ctypes.data, len(f), probe, t.ctypes.data, ptr(x),
                                              ptr(mg), ptr(fd), st.ctypes.data))
         return self._stb_dict(f, t, x, mg, fd, st, 1)
+
+    @staticmethod
+    def _pz_args(fmax, sigma0):
+        """None for fmax takes both from the .PZ card (NaN tells the library to)"""
+        if fmax is None:
+            return float("nan"), 0.0
+        return float(fmax), 0.0 if sigma0 is None else float(sigma0)
+
+    def pz(self, params, x_op, fmax=None, sigma0=None, status=None):
+        """Poles of the batch's linearisations around the operating points x_op (device [N][B], from dc());
+        csim_pz_batch_dev.  fmax: Hz, eigenvalues slower than 1 / (2 pi fmax) are poles at infinity; sigma0: rad/s,
+        the shift of G + sigma0 C (default 0) -- fmax None takes both from the .PZ card.
+        -> dict(poles complex [N][B] (slot k of instance b: dominant first, NaN beyond n_poles), n_poles, n_rhp int32
+                [B], max_re [B], status [B]); device tensors; status is OR-ed into `status` when given."""
+        torch = _torch()
+        B = params.shape[1]
+        fmax, sigma0 = self._pz_args(fmax, sigma0)
+        dev = self._dev()
+        poles = torch.zeros((self.N, B, 2), dtype=torch.float64, device=dev)
+        n_poles = torch.zeros(B, dtype=torch.int32, device=dev)
+        n_rhp = torch.zeros(B, dtype=torch.int32, device=dev)
+        max_re = torch.zeros(B, dtype=torch.float64, device=dev)
+        st = status if status is not None else torch.zeros(B, dtype=torch.int32, device=dev)
+        capi.check(capi.lib().csim_pz_batch_dev(self._h, params.data_ptr(), B, x_op.data_ptr(), fmax, sigma0, poles.data_ptr(),
+                                                n_poles.data_ptr(), n_rhp.data_ptr(), max_re.data_ptr(), st.data_ptr(),
+                                                self._stream()))
+        return dict(poles=torch.view_as_complex(poles), n_poles=n_poles, n_rhp=n_rhp, max_re=max_re, status=st)
+
+    def pz_host(self, params=None, B=1, fmax=None, sigma0=None):
+        """DC operating point + poles (csim_pz_batch): numpy, instance-major.
+        -> dict(poles complex [B][N], n_poles, n_rhp [B], max_re [B], status [B])"""
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=np.float64)
+            B = params.shape[0]
+        fmax, sigma0 = self._pz_args(fmax, sigma0)
+        poles = np.zeros((B, self.N), dtype=np.complex128)
+        n_poles = np.zeros(B, dtype=np.int32)
+        n_rhp = np.zeros(B, dtype=np.int32)
+        max_re = np.zeros(B)
+        st = np.zeros(B, dtype=np.uint32)
+        capi.check(capi.lib().csim_pz_batch(self._h, params.ctypes.data if params is not None else None, B, fmax, sigma0,
+                                            poles.ctypes.data, n_poles.ctypes.data, n_rhp.ctypes.data, max_re.ctypes.data,
+                                            st.ctypes.data))
+        return dict(poles=poles, n_poles=n_poles, n_rhp=n_rhp, max_re=max_re, status=st)
 
     def _pss_args(self, tstep, f0, n_harm, probes, tol, max_rounds):
         """-> (tstep, f0, n_harm, probe array or None, n_probe, tol, max_rounds) with the cards' values filled in, so the
@@ -1295,6 +1346,24 @@ def stb_solve_batch(G, Cm, probe, omega, kernel="auto", device=0, want_x=True, f
     del r["freqs"], r["status"]
     r["flags"] = flags
     return r
+
+
+def pz_solve_batch(G, Cm, fmax, sigma0=0.0, device=0):
+    """The pole kernel on systems given directly (csim_pz_solve_batch): the finite poles of det(G + s C) = 0.  G, Cm
+    [B][n][n] real, n <= 63; fmax in Hz (the cut), sigma0 in rad/s (the shift).
+    -> dict(poles complex [B][n] (dominant first, NaN beyond n_poles), n_poles, n_rhp [B], max_re [B], flags [B])"""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    Cm = np.ascontiguousarray(Cm, dtype=np.float64)
+    B, n = G.shape[0], G.shape[1]
+    poles = np.zeros((B, n), dtype=np.complex128)
+    n_poles = np.zeros(B, dtype=np.int32)
+    n_rhp = np.zeros(B, dtype=np.int32)
+    max_re = np.zeros(B)
+    flags = np.zeros(B, dtype=np.uint32)
+    capi.check(capi.lib().csim_pz_solve_batch(device, n, B, G.ctypes.data, Cm.ctypes.data, float(fmax), float(sigma0),
+                                              poles.ctypes.data, n_poles.ctypes.data, n_rhp.ctypes.data, max_re.ctypes.data,
+                                              flags.ctypes.data))
+    return dict(poles=poles, n_poles=n_poles, n_rhp=n_rhp, max_re=max_re, flags=flags)
 
 
 def sp_solve_batch(G, Cm, J, omega, kernel="auto", device=0, port_eq=None, z0=None, want_s=True):

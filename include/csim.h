@@ -78,7 +78,7 @@ extern "C" {
 #define CSIM_ERR_HIP          -4   /* a HIP runtime call failed                    */
 #define CSIM_ERR_UNSUPPORTED  -5   /* circuit outside what the kernels cover       */
 #define CSIM_ERR_EMPTY        -6   /* circuit has no unknowns                      */
-#define CSIM_ERR_CONFIG       -7   /* invalid .TRAN / .AC / .NOISE / .DISTO / .STB numbers, no AC source, no port, no probe */
+#define CSIM_ERR_CONFIG       -7   /* invalid .TRAN / .AC / .NOISE / .DISTO / .STB / .PZ numbers, no AC source, no port, no probe */
 
 typedef struct csim_netlist csim_netlist;
 typedef struct csim_engine  csim_engine;
@@ -638,6 +638,64 @@ int  csim_stb_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int
 int  csim_stb_batch(csim_engine* eng, const double* params, int32_t B, const double* freqs, int32_t F, int32_t probe_elem,
                     double* t, double* x, double* margins, int32_t* found, uint32_t* status);
 
+/* ---- Pole analysis (.PZ POL; the natural frequencies of every instance's linearisation, without a frequency grid) ----
+ * Card: `.PZ POL fmax [sigma0]`, SPICE number suffixes, either case.  `.PZ ZER ...` and `.PZ PZ ...` are reported as
+ *   `Line n: .PZ supports POL only: <line>` and dropped: zeros need a deflation of the infinite structure that is not
+ *   here.  Any other token count is a card error, reported, the statement dropped.  A later valid card replaces an
+ *   earlier one.  The card changes nothing in the IR.
+ * System.  G and C of instance b exactly as in "AC analysis".  The poles are the s with det(G + s C) = 0.  Two real
+ *   scalars: fmax > 0 in Hz, sigma0 in rad/s (default 0.0).  All arithmetic is real; no FMA contraction; sqrt is the only
+ *   library function, so host and device compute the same bits.
+ * 1. A0 = G + sigma0 * C, one product and one sum per entry.
+ * 2. M = -A0^-1 C by a real LU with partial pivoting on [A0 | C], the N columns of C as right-hand sides: pivot = the
+ *    largest |a| of the column, the lowest row on ties, a NaN diagonal keeps the pivot; multiplier a / pivot; rows whose
+ *    entry in the pivot column is exactly zero are skipped; back substitution per column, the products U(i,l) x(l)
+ *    subtracted for l ascending, zero U(i,l) skipped, then the division by U(i,i); then the exact negation.  A column
+ *    maximum below lu_eps: CSIM_ST_PZ_SINGULAR, n_poles = 0, every pole slot NaN + NaN j.
+ * 3. The eigenvalues mu of M by the EISPACK chain:
+ *    balance  diagonal similarity by powers of two.  SWEEP ORDER: Gauss-Seidel -- the indices i = 0 .. N-1 in order,
+ *             each with c = sum |M(j,i)| and r = sum |M(i,j)| over j != i, j ascending, of the matrix as the indices
+ *             before it left it; c or r zero (or not finite): nothing; else f = 1, g = r / 2, while c < g: f *= 2,
+ *             c *= 4; g = r * 2, while c > g: f /= 2, c /= 4; if (c + r) / f < 0.95 * (c0 + r): row i times 1 / f, then
+ *             column i times f.  Sweeps repeat until one changes nothing, AT MOST 16 of them.
+ *    elmhes   for m = 1 .. N-2: pivot = the largest |a(j,m-1)|, j = m .. N-1, the lowest index on ties (all zero: the
+ *             column is skipped); rows, then columns, m and the pivot's exchanged; y(i) = a(i,m-1) / a(m,m-1) kept in
+ *             place (zero entries stay); first every a(i,j) -= y(i) a(m,j) (i > m, j >= m), then every
+ *             a(j,m) += y(i) a(j,i) (all j; i ascending; zero y(i) skipped).  Then +0.0 below the subdiagonal.
+ *    hqr      Francis double-shift QR with deflation, as EISPACK hqr: the exact tests |h(l,l-1)| + s == s with
+ *             s = |h(l-1,l-1)| + |h(l,l)| (anorm when that is zero; anorm = the sum over the rows, ascending, of each
+ *             row's sum of |h(i,j)|, j = max(i-1,0) .. N-1 ascending); exceptional shifts at iterations 10 and 20; at
+ *             most 30 iterations per eigenvalue, then CSIM_ST_PZ_NONCONV, n_poles = 0, NaN slots.  Per bulge step the
+ *             row phase (columns k .. nn) is finished before the column phase (rows l .. min(nn, k+3)) starts.  The
+ *             routine always terminates, after at most 30 N sweeps.
+ * 4. Cut.  wmax = 2 pi fmax (pi = 3.14159265358979323846).  An eigenvalue is a finite pole iff
+ *    (mur^2 + mui^2) * wmax^2 >= 1.0; everything else is a pole at infinity and dropped.  LIMIT: the cut is the only
+ *    thing that separates them.  Eigenvalues mu = 0 that belong to Jordan blocks come out near sqrt(eps) ||M||, not near
+ *    eps ||M||, so no rank rule finds them: choose fmax well above the fastest pole of interest and well below
+ *    1 / (2 pi sqrt(eps) ||M||); a true pole faster than fmax is dropped with them.
+ * 5. Pole s = sigma0 + conj(mu) / (mur^2 + mui^2): re = sigma0 + mur / m2, im = (0.0 - mui) / m2.  Order: descending
+ *    m2, then descending Im mu, then descending Re mu, then the eigenvalue's index.  The dominant (slowest) pole is
+ *    first; a conjugate pair is adjacent, the member with Im mu > 0 (Im s < 0) first.  Slots n_poles .. N-1 are
+ *    NaN + NaN j.
+ * 6. Summary per instance: n_poles; n_rhp, the count with Re s > 0.0; max_re, the largest Re s (NaN when n_poles == 0).
+ * Circuits of up to 63 unknowns (CSIM_ERR_UNSUPPORTED beyond).  One kernel, one wavefront per instance: ac_kernel=block
+ * and ac_kernel=packed are CSIM_ERR_UNSUPPORTED.  The exact order of every operation: engine/pz.hpp, written once for
+ * host and device.  Results do not depend on B or on how the batch is chunked.
+ * Order of the refusals of an engine's call: a bad argument (fmax not finite or <= 0, sigma0 not finite: CSIM_ERR_ARG);
+ *   ac_kernel=block or packed; more than 63 unknowns; no card where fmax was left to it (fmax NaN: CSIM_ERR_CONFIG).
+ *
+ * Enqueues and never waits.  fmax NaN: the .PZ card's fmax and sigma0.
+ *   d_poles [N][B] complex (re, im): slot k of instance b       d_n_poles, d_n_rhp [B] int32       d_max_re [B]
+ *   d_status [B], OR-ed                                                                                             */
+int  csim_netlist_pz(const csim_netlist* nl, int32_t* enabled, double* fmax, double* sigma0);
+int  csim_pz_batch_dev(csim_engine* eng, const double* d_params /*[P][B]*/, int32_t B, const double* d_xop, double fmax,
+                       double sigma0, double* d_poles, int32_t* d_n_poles, int32_t* d_n_rhp, double* d_max_re,
+                       uint32_t* d_status, void* stream);
+/* DC operating point, then the poles.  params [B][P] or NULL (nominal).  poles [B][N] complex; n_poles, n_rhp, max_re,
+ * status [B], each optional.                                                                                        */
+int  csim_pz_batch(csim_engine* eng, const double* params, int32_t B, double fmax, double sigma0, double* poles,
+                   int32_t* n_poles, int32_t* n_rhp, double* max_re, uint32_t* status);
+
 /* ---- Periodic steady state (.HB f0 nharm; the reference parses the card and its steady-state source is empty) ----
  * The periodic steady state of this engine's own backward-Euler transient, found by shooting Newton, and the harmonics
  * 0 .. n_harm of the probes, for every instance of the batch.
@@ -908,6 +966,13 @@ int  csim_imd_solve_batch(int32_t device, int32_t n, int32_t B, const double* G,
 int  csim_stb_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* C, int32_t eq_p, int32_t eq_m,
                           int32_t eq_br, const double* omega, int32_t F, int32_t kernel, double* T, double* x,
                           uint32_t* flags, const double* freqs_hz, double* margins, int32_t* found);
+
+/* The pole kernel on systems given directly (host pointers; lu_eps = 1e-15), "Pole analysis" on any (G, C).  G, C
+ * [B][n][n] row-major.  poles [B][n] complex; n_poles, n_rhp [B] int32, max_re [B] and flags [B] (CSIM_ST_PZ_*) are
+ * optional.  fmax not finite or <= 0, sigma0 not finite: CSIM_ERR_ARG; then n > 63: CSIM_ERR_UNSUPPORTED.  Nothing is
+ * written when n or B is 0.                                                                                         */
+int  csim_pz_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, const double* C, double fmax, double sigma0,
+                         double* poles, int32_t* n_poles, int32_t* n_rhp, double* max_re, uint32_t* flags);
 
 /* ---- Gauss-Seidel variant of the reference (never reached from its main(), kept as public API) ----
  * Batched Solver::solveLinearSystemGaussSeidel (include/solver.hpp:139-204): sweeps in row order with the

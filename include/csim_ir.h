@@ -157,6 +157,8 @@ static inline void csim_consts_default(csim_consts* k)
 #define CSIM_ST_PSS_NONCONV      0x0200u  /* periodic steady state: the round cap was reached before the period closed */
 #define CSIM_ST_PSS_SINGULAR     0x0400u  /* periodic steady state: tiny pivot in I - W_K (or in a step's sensitivity solve); instance stopped */
 #define CSIM_ST_PAC_SINGULAR     0x0800u  /* periodic AC analysis: tiny pivot in I - z_K W_K (or in a step's solve); instance stopped, zeros for that frequency chunk */
+#define CSIM_ST_PZ_SINGULAR      0x1000u  /* pole analysis: tiny pivot in G + sigma0 C; no poles, NaN slots */
+#define CSIM_ST_PZ_NONCONV       0x2000u  /* pole analysis: the QR iteration spent 30 iterations on one eigenvalue; no poles, NaN slots */
 
 #ifdef __cplusplus
 }
