@@ -4,7 +4,8 @@
 // factorisation and back substitution with K right-hand sides -- ac_lu.hpp's primitives applied in the order of
 // ac_lu_solve_multi(), by one wavefront on a system in LDS, or by 32 lanes on a system in registers -- and the
 // scaffolding around it (LDS carve-up, the G + jwC load, instance indexing, launch dispatch).  AC, noise, distortion
-// and intermodulation are K = 1, loop gain is K = 2.  Included by those seven files only.
+// and intermodulation are K = 1, loop gain is K = 2.  Included by those seven files only (by the distortion and
+// intermodulation ones through ac_chain.hpp, which holds their two kernel bodies).
 // A third shape, one 256-thread workgroup per system for N <= 1024 (AC and noise only), is ac_block.hpp.
 #pragma once
 

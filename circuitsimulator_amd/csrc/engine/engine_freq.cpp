@@ -363,8 +363,7 @@ int spNoiseSetup(const csim_engine* eng, double temp_k, bool wantParams, csim::S
 
 // output pair of a distortion or intermodulation call -> the kernels' numbers (include/csim.h "Distortion analysis",
 // "Intermodulation analysis"); `what` names the analysis in a refusal
-template <class Args>
-int distoSetup(const csim_engine* eng, const char* what, int out_p, int out_m, Args& a)
+int distoSetup(const csim_engine* eng, const char* what, int out_p, int out_m, csim::ChainArgs& a)
 {
     const int N = eng->plan.N;
     const std::string who(what);
@@ -382,6 +381,27 @@ int distoSetup(const csim_engine* eng, const char* what, int out_p, int out_m, A
     a.devG = eng->dDistoG;
     a.devS = eng->dDistoS;
     return CSIM_OK;
+}
+
+// What csim_disto_batch_dev and csim_imd_batch_dev share once `a` is set up: the coefficients go to the caller's
+// [M][7][B] table or to the engine's scratch of one chunk; per chunk the coefficient kernel, then the analysis's sweep
+// (`sweep(a)`, which may first set what only it knows of the chunk)
+template <class Sweep>
+int distoSweepChunks(csim_engine* eng, const double* d_params, int B, const double* d_xop, const double* freqs, int F, int which,
+                     hipStream_t hs, double* d_coef, uint32_t* d_status, csim::ChainArgs& a, Sweep sweep)
+{
+    const int M = eng->nDistoDev, chunk = acChunk(eng, B);
+    if (!d_coef)
+        if (const int rc = growDevice(eng->dDistoCoef, eng->distoCoefCap, (size_t)csim::DISTO_NCOEF * M * (size_t)chunk, sizeof(double))) return rc;
+    return acSweepChunks(eng, d_params, B, d_xop, freqs, F, which, hs, nullptr, d_status, a, [&](const double*, size_t, size_t) {
+        double* const dCoef = d_coef ? d_coef : eng->dDistoCoef;
+        a.coef = dCoef;
+        a.coefStride = d_coef ? (size_t)B : (size_t)chunk;
+        a.coefOff = d_coef ? (size_t)a.b0 : 0;
+        const hipError_t e = csim::launchDistoCoef(eng->gpTran, eng->dDistoElem, M, d_params, B, a.b0, a.Bc, d_xop, dCoef,
+                                                   a.coefStride, a.coefOff, hs);
+        return e != hipSuccess ? e : sweep(a);
+    });
 }
 
 // the probe of a loop-gain call -> the kernels' numbers (include/csim.h "Loop-gain analysis"); probe_elem -1: the card's
@@ -522,6 +542,48 @@ int uploadGenerators(int S, int B, const int32_t* src_a, const int32_t* src_b, c
         HIPCHK(hipMemcpy(g.b.p, src_b, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(g.psd.p, psdT.data(), sizeof(double) * psdT.size(), hipMemcpyHostToDevice));
     }
+    return CSIM_OK;
+}
+
+// the device table of the distortion and intermodulation kernels on the device: terminals [M], and the coefficients
+// [B][M][7] of the caller as [M][7][B]
+struct DeviceTable {
+    DevBuf d, g, s, coef;
+};
+// the equations of a *_solve_batch call that index LDS: the output pair and the device terminals
+int checkDeviceTable(const char* entry, int n, int M, const int32_t* dev_d, const int32_t* dev_g, const int32_t* dev_s, int out_p,
+                     int out_m)
+{
+    if (n <= 0) return CSIM_OK;
+    bool ok = out_p >= 0 && out_p < n && out_m >= -1 && out_m < n && out_p != out_m;
+    for (int m = 0; m < M && ok && dev_d && dev_g && dev_s; ++m)
+        ok = dev_d[m] >= -1 && dev_d[m] < n && dev_g[m] >= -1 && dev_g[m] < n && dev_s[m] >= -1 && dev_s[m] < n;
+    if (!ok) { setError(std::string(entry) + ": equation index out of range (or out_p == out_m)"); return CSIM_ERR_ARG; }
+    return CSIM_OK;
+}
+int uploadDevices(int M, int B, const int32_t* dev_d, const int32_t* dev_g, const int32_t* dev_s, const double* coef,
+                  DeviceTable& t, csim::ChainArgs& a)
+{
+    const size_t MK = (size_t)M * csim::DISTO_NCOEF;
+    std::vector<double> coefT(MK * (size_t)B);
+    for (int b = 0; b < B; ++b)
+        for (size_t q = 0; q < MK; ++q) coefT[q * (size_t)B + b] = coef[(size_t)b * MK + q];
+    HIPCHK(t.d.alloc(sizeof(int32_t) * (size_t)M));
+    HIPCHK(t.g.alloc(sizeof(int32_t) * (size_t)M));
+    HIPCHK(t.s.alloc(sizeof(int32_t) * (size_t)M));
+    HIPCHK(t.coef.alloc(sizeof(double) * coefT.size()));
+    if (M > 0) {
+        HIPCHK(hipMemcpy(t.d.p, dev_d, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(t.g.p, dev_g, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(t.s.p, dev_s, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(t.coef.p, coefT.data(), sizeof(double) * coefT.size(), hipMemcpyHostToDevice));
+    }
+    a.M = M;
+    a.devD = t.d.as<int32_t>();
+    a.devG = t.g.as<int32_t>();
+    a.devS = t.s.as<int32_t>();
+    a.coef = t.coef.as<double>();
+    a.coefStride = (size_t)B;
     return CSIM_OK;
 }
 
@@ -809,27 +871,17 @@ int csim_disto_batch_dev(csim_engine* eng, const double* d_params, int32_t B, co
         setError("csim_disto_batch_dev: bad argument");
         return CSIM_ERR_ARG;
     }
-    csim::DistoArgs a{};
+    csim::ChainArgs a{};
     if (const int rc = distoSetup(eng, "distortion analysis", out_p_eq, out_m_eq, a)) return rc;
     int which;
     if (const int rc = acPickKernel(eng->cfg.acKernel, eng->plan.N, nullptr, &which)) return rc;
     if (B == 0 || F == 0) return CSIM_OK;
     HIPCHK(hipSetDevice(eng->device));
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    // the coefficients: the caller's [M][7][B] table, or the engine's scratch of one chunk
-    const int M = eng->nDistoDev, chunk = acChunk(eng, B);
-    if (!d_coef)
-        if (const int rc = growDevice(eng->dDistoCoef, eng->distoCoefCap, (size_t)csim::DISTO_NCOEF * M * (size_t)chunk, sizeof(double))) return rc;
     a.h = d_h;
-    a.hd = d_hd;
-    return acSweepChunks(eng, d_params, B, d_xop, freqs, F, which, hs, nullptr, d_status, a, [&](const double*, size_t, size_t) {
-        double* const dCoef = d_coef ? d_coef : eng->dDistoCoef;
-        a.coef = dCoef;
-        a.coefStride = d_coef ? (size_t)B : (size_t)chunk;
-        a.coefOff = d_coef ? (size_t)a.b0 : 0;
-        const hipError_t e = csim::launchDistoCoef(eng->gpTran, eng->dDistoElem, M, d_params, B, a.b0, a.Bc, d_xop, dCoef,
-                                                   a.coefStride, a.coefOff, hs);
-        return e != hipSuccess ? e : csim::launchDistoSweep(which, a, hs);
+    a.ratio = d_hd;
+    return distoSweepChunks(eng, d_params, B, d_xop, freqs, F, which, hs, d_coef, d_status, a, [&](csim::ChainArgs& c) {
+        return csim::launchDistoSweep(which, c, eng->distoD.data(), eng->distoG.data(), eng->distoS.data(), hs);
     });
 }
 
@@ -847,7 +899,7 @@ int csim_disto_batch(csim_engine* eng, const double* params, int32_t B, const do
     }
     if (F < 0 || (B > 0 && F > 0 && !hd)) { setError("csim_disto_batch: bad argument"); return CSIM_ERR_ARG; }
     {
-        csim::DistoArgs probe{};
+        csim::ChainArgs probe{};
         if (const int rc = distoSetup(eng, "distortion analysis", out_p_eq, out_m_eq, probe)) return rc;
     }
     if (B == 0) return CSIM_OK;
@@ -874,33 +926,23 @@ int csim_imd_batch_dev(csim_engine* eng, const double* d_params, int32_t B, cons
         setError("csim_imd_batch_dev: bad argument");
         return CSIM_ERR_ARG;
     }
-    csim::ImdArgs a{};
+    csim::ChainArgs a{};
     if (const int rc = distoSetup(eng, "intermodulation analysis", out_p_eq, out_m_eq, a)) return rc;
     int which;
     if (const int rc = acPickKernel(eng->cfg.acKernel, eng->plan.N, nullptr, &which)) return rc;
     if (B == 0 || F == 0) return CSIM_OK;
     HIPCHK(hipSetDevice(eng->device));
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    // the coefficients: the caller's [M][7][B] table, or the engine's scratch of one chunk
-    const int M = eng->nDistoDev, chunk = acChunk(eng, B);
-    if (!d_coef)
-        if (const int rc = growDevice(eng->dDistoCoef, eng->distoCoefCap, (size_t)csim::DISTO_NCOEF * M * (size_t)chunk, sizeof(double))) return rc;
     a.h = d_h;
-    a.im = d_im;
+    a.ratio = d_im;
     a.j2 = nullptr;                                         // both tones drive the same AC sources
     // one list for the sweep driver: the first tone's F frequencies, then the second tone's
     std::vector<double> tones((size_t)2 * F, f2);
     std::copy(freqs, freqs + F, tones.begin());
-    return acSweepChunks(eng, d_params, B, d_xop, tones.data(), 2 * F, which, hs, nullptr, d_status, a, [&](const double*, size_t, size_t) {
-        double* const dCoef = d_coef ? d_coef : eng->dDistoCoef;
-        a.F = F;
-        a.omega2 = a.omega + F;
-        a.coef = dCoef;
-        a.coefStride = d_coef ? (size_t)B : (size_t)chunk;
-        a.coefOff = d_coef ? (size_t)a.b0 : 0;
-        const hipError_t e = csim::launchDistoCoef(eng->gpTran, eng->dDistoElem, M, d_params, B, a.b0, a.Bc, d_xop, dCoef,
-                                                   a.coefStride, a.coefOff, hs);
-        return e != hipSuccess ? e : csim::launchImdSweep(which, a, eng->distoD.data(), eng->distoG.data(), eng->distoS.data(), hs);
+    return distoSweepChunks(eng, d_params, B, d_xop, tones.data(), 2 * F, which, hs, d_coef, d_status, a, [&](csim::ChainArgs& c) {
+        c.F = F;
+        c.omega2 = c.omega + F;
+        return csim::launchImdSweep(which, c, eng->distoD.data(), eng->distoG.data(), eng->distoS.data(), hs);
     });
 }
 
@@ -920,7 +962,7 @@ int csim_imd_batch(csim_engine* eng, const double* params, int32_t B, const doub
     }
     if (F < 0 || !std::isfinite(f2) || (B > 0 && F > 0 && !im)) { setError("csim_imd_batch: bad argument"); return CSIM_ERR_ARG; }
     {
-        csim::ImdArgs probe{};
+        csim::ChainArgs probe{};
         if (const int rc = distoSetup(eng, "intermodulation analysis", out_p_eq, out_m_eq, probe)) return rc;
     }
     if (B == 0) return CSIM_OK;
@@ -1255,45 +1297,20 @@ int csim_disto_solve_batch(int32_t device, int32_t n, int32_t B, const double* G
         setError("csim_disto_solve_batch: bad argument");
         return CSIM_ERR_ARG;
     }
-    if (n > 0) {
-        bool ok = out_p >= 0 && out_p < n && out_m >= -1 && out_m < n && out_p != out_m;
-        for (int m = 0; m < M && ok && dev_d && dev_g && dev_s; ++m)
-            ok = dev_d[m] >= -1 && dev_d[m] < n && dev_g[m] >= -1 && dev_g[m] < n && dev_s[m] >= -1 && dev_s[m] < n;
-        if (!ok) { setError("csim_disto_solve_batch: equation index out of range (or out_p == out_m)"); return CSIM_ERR_ARG; }
-    }
+    if (const int rc = checkDeviceTable("csim_disto_solve_batch", n, M, dev_d, dev_g, dev_s, out_p, out_m)) return rc;
     AcSolveFront fr;
     if (const int rc = acSolveFront("csim_disto_solve_batch", device, n, B, G, Cm, J, omega, F, kernel, work, fr)) return rc;
     if (!work) return CSIM_OK;
-    // device table [M] and coefficients [B][M][7] -> [M][7][B]
-    const size_t MK = (size_t)M * csim::DISTO_NCOEF;
-    std::vector<double> coefT(MK * (size_t)B);
-    for (int b = 0; b < B; ++b)
-        for (size_t q = 0; q < MK; ++q) coefT[q * (size_t)B + b] = coef[(size_t)b * MK + q];
-    DevBuf dD, dG, dS, dCoef;
-    HIPCHK(dD.alloc(sizeof(int32_t) * (size_t)M));
-    HIPCHK(dG.alloc(sizeof(int32_t) * (size_t)M));
-    HIPCHK(dS.alloc(sizeof(int32_t) * (size_t)M));
-    HIPCHK(dCoef.alloc(sizeof(double) * coefT.size()));
-    if (M > 0) {
-        HIPCHK(hipMemcpy(dD.p, dev_d, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dG.p, dev_g, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dS.p, dev_s, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dCoef.p, coefT.data(), sizeof(double) * coefT.size(), hipMemcpyHostToDevice));
-    }
-    HostOutputs outs(F, B);
-    csim::DistoArgs a{};
+    csim::ChainArgs a{};
     fr.fill(a, n, F, B);
-    a.M = M;
+    DeviceTable dev;
+    if (const int rc = uploadDevices(M, B, dev_d, dev_g, dev_s, coef, dev, a)) return rc;
+    HostOutputs outs(F, B);
     a.outP = out_p; a.outM = out_m;
-    a.devD = dD.as<int32_t>();
-    a.devG = dG.as<int32_t>();
-    a.devS = dS.as<int32_t>();
-    a.coef = dCoef.as<double>();
-    a.coefStride = (size_t)B;
-    a.hd = outs.add(hd, 2, 1);
+    a.ratio = outs.add(hd, 2, 1);
     a.h = outs.add(h, 3 * n, 2);
     if (outs.rc) return outs.rc;
-    HIPCHK(csim::launchDistoSweep(fr.which, a, nullptr));
+    HIPCHK(csim::launchDistoSweep(fr.which, a, dev_d, dev_g, dev_s, nullptr));
     return outs.finish(fr.dF, flags);
 }
 
@@ -1310,12 +1327,7 @@ int csim_imd_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, 
         setError("csim_imd_solve_batch: bad argument");
         return CSIM_ERR_ARG;
     }
-    if (n > 0) {
-        bool ok = out_p >= 0 && out_p < n && out_m >= -1 && out_m < n && out_p != out_m;
-        for (int m = 0; m < M && ok && dev_d && dev_g && dev_s; ++m)
-            ok = dev_d[m] >= -1 && dev_d[m] < n && dev_g[m] >= -1 && dev_g[m] < n && dev_s[m] >= -1 && dev_s[m] < n;
-        if (!ok) { setError("csim_imd_solve_batch: equation index out of range (or out_p == out_m)"); return CSIM_ERR_ARG; }
-    }
+    if (const int rc = checkDeviceTable("csim_imd_solve_batch", n, M, dev_d, dev_g, dev_s, out_p, out_m)) return rc;
     std::vector<double> tones;                              // the first tone's F frequencies, then the second tone's
     if (work) {
         tones.assign(omega1, omega1 + F);
@@ -1326,22 +1338,11 @@ int csim_imd_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, 
     AcSolveFront fr;
     if (const int rc = acSolveFront("csim_imd_solve_batch", device, n, B, G, Cm, J, tones.data(), 2 * F, kernel, work, fr)) return rc;
     if (!work) return CSIM_OK;
-    // device table [M] and coefficients [B][M][7] -> [M][7][B]; J2 [B][n] complex -> [B][re [n], im [n]]
-    const size_t MK = (size_t)M * csim::DISTO_NCOEF;
-    std::vector<double> coefT(MK * (size_t)B);
-    for (int b = 0; b < B; ++b)
-        for (size_t q = 0; q < MK; ++q) coefT[q * (size_t)B + b] = coef[(size_t)b * MK + q];
-    DevBuf dD, dG, dS, dCoef, dJ2;
-    HIPCHK(dD.alloc(sizeof(int32_t) * (size_t)M));
-    HIPCHK(dG.alloc(sizeof(int32_t) * (size_t)M));
-    HIPCHK(dS.alloc(sizeof(int32_t) * (size_t)M));
-    HIPCHK(dCoef.alloc(sizeof(double) * coefT.size()));
-    if (M > 0) {
-        HIPCHK(hipMemcpy(dD.p, dev_d, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dG.p, dev_g, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dS.p, dev_s, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dCoef.p, coefT.data(), sizeof(double) * coefT.size(), hipMemcpyHostToDevice));
-    }
+    csim::ChainArgs a{};
+    fr.fill(a, n, F, B);
+    DeviceTable dev;
+    if (const int rc = uploadDevices(M, B, dev_d, dev_g, dev_s, coef, dev, a)) return rc;
+    DevBuf dJ2;                                             // J2 [B][n] complex -> [B][re [n], im [n]]
     if (J2) {
         std::vector<double> planar((size_t)2 * n * B);
         for (int b = 0; b < B; ++b)
@@ -1353,18 +1354,10 @@ int csim_imd_solve_batch(int32_t device, int32_t n, int32_t B, const double* G, 
         HIPCHK(hipMemcpy(dJ2.p, planar.data(), sizeof(double) * planar.size(), hipMemcpyHostToDevice));
     }
     HostOutputs outs(F, B);
-    csim::ImdArgs a{};
-    fr.fill(a, n, F, B);
     a.omega2 = a.omega + F;
     a.j2 = J2 ? dJ2.as<double>() : nullptr;
-    a.M = M;
     a.outP = out_p; a.outM = out_m;
-    a.devD = dD.as<int32_t>();
-    a.devG = dG.as<int32_t>();
-    a.devS = dS.as<int32_t>();
-    a.coef = dCoef.as<double>();
-    a.coefStride = (size_t)B;
-    a.im = outs.add(im, csim::IMD_NRATIO, 1);
+    a.ratio = outs.add(im, csim::IMD_NRATIO, 1);
     a.h = outs.add(h, csim::IMD_NSOLVE * n, 2);
     if (outs.rc) return outs.rc;
     HIPCHK(csim::launchImdSweep(fr.which, a, dev_d, dev_g, dev_s, nullptr));

@@ -189,47 +189,33 @@ struct SpNoiseArgs {
 };
 hipError_t launchSpNoiseSweep(int which, const SpNoiseArgs& a, hipStream_t stream);
 
-// Distortion analysis (kernels_disto.hip) on the systems launchAcAssemble leaves: three factorisations per (instance,
-// frequency), at w, 2 w and 3 w.  Coefficient k of device m of chunk instance c is at
-// coef[(m * 7 + k) * coefStride + coefOff + c].  Device terminals are checked by the callers, the output pair by the
-// launcher: they index LDS.  Wave and packed shapes only.
-struct DistoArgs {
+// Distortion (kernels_disto.hip) and intermodulation analysis (kernels_imd.hip) on the systems launchAcAssemble leaves:
+// a chain of dependent factorisations per (instance, point), each after the first ones with a right-hand side of MOSFET
+// mixing currents of earlier solutions (ac_chain.hpp).  Distortion: three, at w, 2 w and 3 w (ac_disto.hpp), one tone.
+// Intermodulation: six, at w1, w2, w1 + w2, w1 - w2, 2 w1 and 2 w1 - w2 (ac_imd.hpp), two tones.  Coefficient k of
+// device m of chunk instance c is at coef[(m * 7 + k) * coefStride + coefOff + c].  The output pair and the device
+// terminals (hostD, hostG, hostS: the host's copy of the table) are checked by the launchers: they index LDS.  Wave and
+// packed shapes only.
+struct ChainArgs {
     int N, F, M, B, b0, Bc;
     int outP, outM;                     // v = x[outP] - x[outM] (-1: ground)
     double eps;
     const double* sys;
-    const double* omega;
+    const double* omega;                // [F] the tone, or the first of two
+    const double* omega2;               // [F] second tone; one tone: null, never read
+    const double* j2;                   // two tones: [Bc][2 N] (re [N], im [N]) excitation of the second, or null: that of the first
     const int32_t *devD, *devG, *devS;  // [M] drain, gate, source equations (-1 ground)
     const double* coef;
     size_t coefStride, coefOff;
-    double* h;                          // [F][3][N][B] complex or null: x1, x2, x3
-    double* hd;                         // [F][2][B]: HD2, HD3
+    double* h;                          // [F][solves][N][B] complex or null: x1, x2, x3, or x0 .. x5
+    double* ratio;                      // [F][2][B]: HD2, HD3, or [F][3][B]: IM2+, IM2-, IM3
     uint32_t* status;                   // [B], OR-ed
 };
 hipError_t launchDistoCoef(const GenPlan& pl, const int32_t* dDevElem, int M, const double* dParams, int B, int b0, int Bc,
                            const double* dXop, double* dCoef, size_t coefStride, size_t coefOff, hipStream_t stream);
-hipError_t launchDistoSweep(int which, const DistoArgs& a, hipStream_t stream);
-
-// Intermodulation analysis (kernels_imd.hip) on the systems launchAcAssemble leaves: six factorisations per (instance,
-// tone pair), at w1, w2, w1 + w2, w1 - w2, 2 w1 and 2 w1 - w2 (ac_imd.hpp).  Coefficients as DistoArgs.  The output
-// pair and the device terminals (hostD, hostG, hostS: the host's copy of the table) are checked by the launcher: they
-// index LDS.  Wave and packed shapes only.
-struct ImdArgs {
-    int N, F, M, B, b0, Bc;
-    int outP, outM;                     // v = x[outP] - x[outM] (-1: ground)
-    double eps;
-    const double* sys;
-    const double* omega;                // [F] first tone
-    const double* omega2;               // [F] second tone
-    const double* j2;                   // [Bc][2 N] (re [N], im [N]) excitation of the second tone, or null: that of the first
-    const int32_t *devD, *devG, *devS;  // [M] drain, gate, source equations (-1 ground)
-    const double* coef;
-    size_t coefStride, coefOff;
-    double* h;                          // [F][6][N][B] complex or null: x0 .. x5
-    double* im;                         // [F][3][B]: IM2+, IM2-, IM3
-    uint32_t* status;                   // [B], OR-ed
-};
-hipError_t launchImdSweep(int which, const ImdArgs& a, const int32_t* hostD, const int32_t* hostG, const int32_t* hostS,
+hipError_t launchDistoSweep(int which, const ChainArgs& a, const int32_t* hostD, const int32_t* hostG, const int32_t* hostS,
+                            hipStream_t stream);
+hipError_t launchImdSweep(int which, const ChainArgs& a, const int32_t* hostD, const int32_t* hostG, const int32_t* hostS,
                           hipStream_t stream);
 
 // Loop-gain analysis (kernels_stb.hip) on the systems launchAcAssemble leaves (their J is not read): one factorisation

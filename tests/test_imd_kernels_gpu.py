@@ -62,6 +62,21 @@ def test_kernels_equal_reference_bitwise(n, M):
         assert np.array_equal(_bits(r["h"]), _bits(want_h[:nb])) and np.array_equal(_bits(r["im"]), _bits(want_im[:nb]))
 
 
+@pytest.mark.parametrize("n,M", ic.CASES, ids=["n%d-M%d" % c for c in ic.CASES])
+def test_the_solves_shared_with_the_single_tone_chain_are_its_bits(n, M):
+    """x0 (at w1, driven by J) and x4 (at 2.0 w1, driven by disto_i2 of x0) are the single-tone chain's x1 and x2 at
+    w = w1: the same body computes both, so the bits are the same"""
+    from circuitsimulator_amd import disto_solve_batch
+    c = ic.case(n, M)
+    for kernel in _kernels(n):
+        two = _run(c, ic.OMEGA1, ic.OMEGA2, kernel)
+        one = disto_solve_batch(c["G"], c["C"], c["J"], c["dev_d"], c["dev_g"], c["dev_s"], c["coef"], c["out"], ic.OMEGA1,
+                                kernel=kernel)
+        assert np.all(two["flags"] == 0) and np.all(one["flags"] == 0), (n, M, kernel)
+        assert np.array_equal(_bits(two["h"][:, :, 0]), _bits(one["h"][:, :, 0])), (n, M, kernel)
+        assert np.array_equal(_bits(two["h"][:, :, 4]), _bits(one["h"][:, :, 1])), (n, M, kernel)
+
+
 @pytest.mark.parametrize("n,M", ic.J2_CASES, ids=["n%d-M%d" % c for c in ic.J2_CASES])
 def test_a_second_excitation(n, M):
     c = ic.case(n, M)
